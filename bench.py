@@ -13,6 +13,12 @@ the max-over-ranks time.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29500 \
         bench.py --gpus 8 --steps 20 --warmup 3
     python bench.py --devices-in-process 8        # the same sharding inside ONE process: one host thread + contexts per device
+    python bench.py --gpus 1 --steps 20 --warmup 3 --full                # + everything beyond the headline (fields below)
+    python bench.py --gpus 1 --steps 20 --warmup 3 --dump-outputs DIR    # + the last timed step's results as DIR/*.npy
+
+A plain run sets up, warms up, times the steps and prints the line: `value`, `ms_per_step` and the fields of the timed region.  `--full` adds
+the per-kernel profile and rooflines, the CPU baselines, the end-to-end and multi-GPU entry points and the other workloads (the `--no-*` options
+switch single parts of it off again); without it those fields are null.
 
 Rank 0 prints ONE JSON line (see DESIGN.md "Measurement" for the definition of every field):
   value              resident-frames rate of the timed region (the contract's number: inputs already in HBM, results left in HBM;
@@ -332,6 +338,67 @@ def run_timed(pipes, steps, warmup, barrier, sync_all):
     return el
 
 
+DUMP_BYTES_PER_KEYPOINT = 7 * 8 + 32 * 4 + 8 + 2 * 4     # keypoint row (float64) + descriptor (float32) + match (float64) + stereo (2 x float32)
+
+
+def dump_outputs(pipe, out_dir, budget=56 << 20, max_sample=128, seed=20240611):
+    """What the timed path left for its caller after the last step: every context holds the results of its last sub-batch (round rounds-1, last
+    pass).  Writes out_dir/*.npy (float32 / float64 only): per-frame keypoint and match counts of all those frames, and for a fixed, seeded sample
+    of them (the sample size depends on the configuration only, so that it stays below `budget` bytes) the keypoints, descriptors, matches and --
+    when the step runs them -- the stereo and SparseImgAlign results.  Frames are numbered by their index in the resident clip."""
+    w, h = pipe.w, pipe.h
+    S, sub, last = len(pipe.exs), pipe.sub, pipe.rounds - 1
+    unit = 2 if pipe.stereo else 1                       # a stereo pair is sampled as a whole
+    stride = max(pipe.exs[0].max_keypoints(w, h), 1)
+    units = S * sub // unit
+    k_units = max(1, min(units, max_sample // unit, budget // (unit * stride * DUMP_BYTES_PER_KEYPOINT)))
+    pick = np.sort(np.random.default_rng(seed).choice(units, k_units, replace=False))
+    sample = [u * unit + j for u in pick for j in range(unit)]                         # positions in the (context, frame) order
+    clip_index = lambda i: (last * S + i // sub) * sub + i % sub
+    res = [e.batch_fetch_all(sub) for e in pipe.exs]
+    n_kp = np.concatenate([r[2] for r in res]).astype(np.float64)
+    out = {"frames": np.array([clip_index(i) for i in range(S * sub)], np.float64), "keypoint_counts": n_kp}
+    if pipe.match:
+        out["match_counts"] = np.concatenate([e.match_counts() for e in pipe.exs]).astype(np.float64)
+    ncol = len(res[0][0].dtype.names)                   # x, y, size, angle, response, octave, class_id
+    kps, desc, match, off, ur, dp, sia_T, sia_info, sia_ret = [], [], [], [0], [], [], [], [], []
+    for i in sample:
+        s, f = divmod(i, sub)
+        n = int(res[s][2][f])
+        k = res[s][0][f, :n]
+        kps.append(np.stack([k[c].astype(np.float64) for c in k.dtype.names], -1))
+        desc.append(res[s][1][f, :n].astype(np.float32))
+        off.append(off[-1] + n)
+        if pipe.match:
+            match.append(pipe.exs[s].match_fetch(f)[0][:n].astype(np.float64))
+        if pipe.stereo and f % 2 == 0:
+            u, d = pipe.exs[s].stereo_fetch(f // 2)
+            ur.append(u[:n].astype(np.float32))
+            dp.append(d[:n].astype(np.float32))
+        if pipe.align:
+            ret, T, info = pipe.exs[s].align_fetch(f)
+            sia_ret.append(ret)
+            sia_T.append(T.astype(np.float64))
+            sia_info.append(info.astype(np.float64))
+    out["sample_frames"] = np.array([clip_index(i) for i in sample], np.float64)
+    out["sample_keypoint_offsets"] = np.array(off, np.float64)
+    out["sample_keypoints"] = np.concatenate(kps).reshape(-1, ncol)
+    out["sample_descriptors"] = np.concatenate(desc).reshape(-1, 32)
+    if pipe.match:
+        out["sample_matches"] = np.concatenate(match)
+    if pipe.stereo:                                      # left frames of the sampled pairs, in sample order
+        out["sample_stereo_u_right"] = np.concatenate(ur)
+        out["sample_stereo_depth"] = np.concatenate(dp)
+    if pipe.align:
+        out["sample_align_ret"] = np.array(sia_ret, np.float64)
+        out["sample_align_Tcr"] = np.array(sia_T, np.float64).reshape(-1, 7)
+        out["sample_align_info"] = np.array(sia_info, np.float64).reshape(-1, 2)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def end_to_end(pipe, min_seconds=1.2, depth=2, host_pitch=None):
     """SURVEY 8(d) 'end-to-end': page-locked host frames in (H2D), kernels, every keypoint + descriptor + count out (D2H) -- `depth` contexts
     software-pipelined: while one sub-batch is in its kernels the next ones' frames go up and the previous one's results come down (the
@@ -633,13 +700,22 @@ def main():
                     help="TEST ONLY, with --share-gpu: still try to bring up the RCCL communicator (two ranks on one device: it is expected to refuse) so that "
                          "the all-ranks-together fallback to gloo is exercised on a one-GPU box")
     ap.add_argument("--other-steps", type=int, default=0, help="timed steps of every other_workloads entry (default: max(20, --steps), i.e. >= 1 s each; tests shorten it)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beyond the headline as well: per-kernel profile and rooflines, CPU baselines, value_end_to_end, host_stream, "
+                         "the multi-GPU entry point and other_workloads (a plain run only sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (counts of every frame of the contexts' last sub-batches; "
+                         "keypoints, descriptors, matches of a fixed, seeded sample of them) as DIR/<name>.npy, float32 / float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events in the timed region")
-    ap.add_argument("--no-extras", action="store_true", help="skip value_end_to_end and other_workloads")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not bracket kernels with HIP events in the timed region")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip value_end_to_end and other_workloads")
     ap.add_argument("--plumbing-selftest", action="store_true",
                     help="CPU-only check of the multi-process plumbing (gloo): no GPU work, output is NOT a measurement")
     args = ap.parse_args()
+    cpu_baselines = args.full and not args.no_cpu_baseline
+    profile = args.full and not args.no_profile
+    extras = args.full and not args.no_extras
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -759,7 +835,7 @@ def main():
     # utilisation sampler sees it, instead of being followed by ~18 s of host-only work
     frames0 = make_frames(min(S * sub, args.distinct) if args.distinct > 0 else S * sub, w, h, seed0=1000 + 97 * (rank * ndev))
     cpu_base = cpu_ref = anchor = None
-    if rank == 0 and world * ndev == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world * ndev == 1 and cpu_baselines:
         cpu_base = cpu_baseline(frames0, cfg, args.cpu_seconds)
         cpu_ref = cpu_baseline_reference(frames0, cfg, min(6.0, args.cpu_seconds))
         anchor = libfast_anchor(frames0)
@@ -775,7 +851,7 @@ def main():
     pipes = [Pipeline(d, args.workload, sub, rounds, S, 1000 + 97 * (rank * ndev + i), args.align, args.stereo, frames=frames0 if i == 0 else None, passes=passes,
                       distinct=args.distinct if args.distinct > 0 else None)
              for i, d in enumerate(devices)]
-    if not args.no_profile:
+    if profile:
         pipes[0].passes = 1
         pipes[0].step(); pipes[0].sync()           # first-touch allocations out of the way before events are recorded
         pipes[0].passes = passes
@@ -795,8 +871,10 @@ def main():
 
     pipe = pipes[0]
     fast_plan_id = pipe.exs[0].fast_plan()   # before the contexts are released further down
+    if args.dump_outputs and rank == 0:      # before anything else launches on these contexts
+        dump_outputs(pipe, args.dump_outputs)
     kernels, iso = {}, {}
-    if not args.no_profile:
+    if profile:
         prof = pipe.profile_read()
         pipe.profile(False)
         # the profile covers warm-up + timed steps of device 0 (same launches; events are only read here, after the region)
@@ -809,7 +887,7 @@ def main():
 
     # ---- end-to-end (PCIe inclusive) on every rank at once ----
     e2e = None
-    if not args.no_extras:
+    if extras:
         barrier()
         nfr, sec, link = end_to_end(pipe)
         sec = max_over_ranks(sec)
@@ -819,7 +897,7 @@ def main():
 
     # ---- what the host's memory can feed (no GPU work): the 8-GPU transfers-included rate needs eight links' worth of DRAM reads at once ----
     host_stream = None
-    if not args.no_extras and rank == 0:
+    if extras and rank == 0:
         from orb_ygz_slam_amd.capi import host_stream_probe
         nthr = min(effective_cores(), 16)
         gbs = host_stream_probe(devices[0], nthr, 256 << 20, 1.0)
@@ -831,12 +909,12 @@ def main():
                                "when that exceeds what ALL the node's cores can stream (this probe used only the cores this process may use)"}
 
     mgpu = mgpu_lit = None
-    if not args.no_extras and world == 1:
+    if extras and world == 1:
         mgpu = mgpu_end_to_end(devices, cfg, frames0)
 
     # ---- short runs of the other BASELINE configurations (their own contexts; each rank its own clip) ----
     others = {}
-    if not args.no_extras and args.workload == "euroc752x480_8lvl_1000feat" and not args.align and not args.stereo:
+    if extras and args.workload == "euroc752x480_8lvl_1000feat" and not args.align and not args.stereo:
         for p in pipes:
             for e in p.exs:
                 e.close()
@@ -886,7 +964,7 @@ def main():
                      "kernels_isolated_avg_us": oiso,
                      "keypoints_per_frame": round(float(okp.mean()), 1),
                      "matches_per_frame": round(float(np.concatenate([e.match_counts() for e in ps[0].exs]).mean()), 1) if o_match else None}
-            if rank == 0 and world * ndev == 1 and not args.no_cpu_baseline:
+            if rank == 0 and world * ndev == 1 and cpu_baselines:
                 # the CPU beside it, on this workload's own clip (north_star: "timed on the node's own host cores in the same run")
                 entry["cpu_baseline"] = cpu_baseline(ps[0].frames, WORKLOADS[wl], seconds_budget=min(args.cpu_seconds, 6.0 if "uhd" in wl else 4.0),
                                                      match=o_match, align=o_align, stereo=o_stereo, one_thread=False)
@@ -907,7 +985,7 @@ def main():
             del ps
             torch.cuda.empty_cache()
 
-    if not args.no_extras and world == 1 and args.workload == "euroc752x480_8lvl_1000feat" and not args.align and not args.stereo:
+    if extras and world == 1 and args.workload == "euroc752x480_8lvl_1000feat" and not args.align and not args.stereo:
         mgpu_lit = mgpu_literal_configs(devices)
 
     if rank == 0:

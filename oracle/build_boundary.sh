@@ -1,5 +1,5 @@
 #!/bin/bash
-# tests/cpp/build_boundary.sh -- builds tests/cpp/bin/boundary_frame: the REFERENCE's own src/Frame.cc, compiled where it lies with the real
+# oracle/build_boundary.sh -- builds oracle/_ref/boundary/boundary_frame: the REFERENCE's own src/Frame.cc, compiled where it lies with the real
 # include/Frame.h, on top of the PRODUCT's class shells (orb_ygz_slam_amd/csrc/host) and libygzf.so.  This is the drop-in recipe of
 # INTEGRATION.md executed for real:
 #   * orb_ygz_slam_amd/csrc/host/ORBextractor.h takes the place of the reference's include/ORBextractor.h (same include guard; here it
@@ -16,13 +16,14 @@
 #   * OpenCV, Eigen and Sophus are not installed in this environment: oracle/ref_shim stands in for their headers (test infrastructure);
 #     its compute primitives are replaced by aborting bodies (tests/cpp/mini_cv_nocompute.cpp), the pose algebra behind the Sophus stand-in
 #     is oracle_align.cpp's.
-# Needs the reference checkout (REF, default /root/reference); the binary travels to the GPU box (tests/cpp/bin is git-ignored only).
+# Needs the reference checkout (REF below); like the rest of oracle/_ref the outputs are git-ignored build products, kept where the checkout is
+# absent (tests/test_gpu_boundary.py runs them).
 set -e
-ROOT=$(cd "$(dirname "$0")/../.." && pwd)
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 REF=${REF:-/root/reference}
 H=$ROOT/orb_ygz_slam_amd/csrc/host
 S=$ROOT/oracle/ref_shim
-OUT=$ROOT/tests/cpp/bin
+OUT=$ROOT/oracle/_ref/boundary
 if [ ! -f "$REF/src/Frame.cc" ]; then echo "reference checkout absent: keeping prebuilt $OUT/boundary_frame (if any)"; exit 0; fi
 mkdir -p "$OUT"
 FLAGS="-O2 -std=c++14 -msse4.2 -pthread -w -ffp-contract=off -DYGZ_REF_TRACKING -DYGZ_REF_MATCHER -DYGZ_REF_FRAME -DYGZ_BOUNDARY_BUILD -DYGZ_REAL_DBOW2 -DYGZF_WITH_REFERENCE_HEADERS"
@@ -87,7 +88,7 @@ rm -f "$OUT/ref_ORBmatcher.o" "$OUT/ref_ORBmatcher_orig.o" "$OUT/ref_Align.o" "$
 nm -C "$OUT/boundary_frame" | grep -E " [TW] ygz::(ORBmatcher::(SearchByProjection|SearchByBoW|SearchForInitialization|FindDirectProjection|Fuse|SearchBySim3|SearchForTriangulation|DescriptorDistance)|SparseImgAlign::run|ORBextractor::operator\(\)|Frame::ComputeStereoMatches|Tracking::(TrackWithSparseAlignment|TrackWithMotionModel|SearchLocalPoints|MonocularInitialization|Relocalization|SearchLocalPointsDirect|TrackReferenceKeyFrame))\(" | sed 's/^[0-9a-f]* //' | sort > "$OUT/boundary_frame.symbols"
 echo "built $OUT/boundary_frame"
 
-# ---- second target: tests/cpp/bin/libboundary_mappoint.so -- the reference's own src/MapPoint.cc with the REAL include/MapPoint.h (the recipe of
+# ---- second target: oracle/_ref/boundary/libboundary_mappoint.so -- the reference's own src/MapPoint.cc with the REAL include/MapPoint.h (the recipe of
 # oracle/Makefile's ref_mappoint) under the product's MapPointBatch.cc: strong MapPoint::ComputeDistinctiveDescriptors + the batch front end; the
 # reference's body stays reachable as ygz_ref_MapPoint_ComputeDistinctiveDescriptors (tests/cpp/boundary_mappoint.cc compares the three forms).
 MFLAGS="-O2 -std=c++14 -msse4.2 -fPIC -pthread -w -ffp-contract=off -DYGZ_REF_MATCHER -DYGZ_REF_MAPPOINT -DYGZF_WITH_REFERENCE_HEADERS"

@@ -1,8 +1,8 @@
-// oracle/ref_shim/tracking/tracking_stubs.h -- TEST INFRASTRUCTURE (boundary build only, tests/cpp/build_boundary.sh): what the reference's
+// oracle/ref_shim/tracking/tracking_stubs.h -- TEST INFRASTRUCTURE (boundary build only, oracle/build_boundary.sh): what the reference's
 // src/Tracking.cc needs from the classes OUTSIDE the hot path -- System, Viewer, FrameDrawer, MapDrawer, Initializer, Optimizer, PnPsolver,
 // LocalMapping, LoopClosing, KeyFrameDatabase, ConfigParam -- as DECLARATIONS, so that the file compiles where it lies, unchanged, against the
 // product's ORBextractor.h and the reference's own ORBmatcher.h / SparseImageAlign.h / Frame.h.  No member has a body here (except the two
-// trivial getters the constructor calls): the linker resolves them to one aborting stand-in (tests/cpp/build_boundary.sh generates the alias
+// trivial getters the constructor calls): the linker resolves them to one aborting stand-in (oracle/build_boundary.sh generates the alias
 // list from the link's own undefined-symbol report).  The test drives only the Tracking members whose callees are the hot path
 // (TrackWithSparseAlignment, SearchLocalPoints).  These files shadow the reference headers of the same names through the include order.
 #ifndef YGZ_ORACLE_REF_SHIM_TRACKING_STUBS_H

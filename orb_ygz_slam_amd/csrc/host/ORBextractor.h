@@ -4,7 +4,7 @@
 // (include/ORBextractor.h:45-109: constructor, both operator() overloads, the six getters, the public mvImagePyramid, ComputePyramid,
 // the two enums) and the reference's protected data members, so that Frame.h / Frame.cc / Tracking.cc compile against it unchanged.
 // In the reference tree this file replaces include/ORBextractor.h and ORBextractor.cc replaces src/ORBextractor.cc (the
-// boundary test builds exactly that: tests/cpp/build_boundary.sh compiles the reference's own src/Frame.cc against this header).
+// boundary test builds exactly that: oracle/build_boundary.sh compiles the reference's own src/Frame.cc against this header).
 // What is not carried over are the protected CPU helpers (ComputeKeyPointsOctTree, DistributeOctTree, ... and class ExtractorNode): they
 // are implementation details of the file this one replaces, nothing outside src/ORBextractor.cc refers to them.
 //

@@ -1,7 +1,7 @@
 // tests/cpp/boundary_frame.cc -- TEST DRIVER of the drop-in boundary: the REFERENCE's own src/Frame.cc (compiled where it lies, real
 // include/Frame.h) runs on top of the PRODUCT's class shells (orb_ygz_slam_amd/csrc/host: ygz::ORBextractor replaces include/ORBextractor.h +
 // src/ORBextractor.cc, ygz::ORBmatcher's hot-path members replace those of src/ORBmatcher.cc) and libygzf.  Built by
-// tests/cpp/build_boundary.sh; OpenCV / Eigen / Sophus are the stand-ins of oracle/ref_shim (not installed here), whose compute primitives
+// oracle/build_boundary.sh; OpenCV / Eigen / Sophus are the stand-ins of oracle/ref_shim (not installed here), whose compute primitives
 // abort in this build (tests/cpp/mini_cv_nocompute.cpp).  tests/test_gpu_boundary.py compares everything dumped here with the oracle.
 //
 // What runs, in the reference's own code:
@@ -19,7 +19,7 @@
 //   and the shell's device ComputeStereoMatches(F) beside the reference's CPU one.
 // Round 4: the BATCH bindings (orb_ygz_slam_amd/csrc/host/TrackingBatched.cc, FrameStereo.cc) are linked as the strong definitions of
 //   Tracking::SearchLocalPoints, Tracking::SearchLocalPointsDirect and Frame::ComputeStereoMatches; the reference's own bodies of the three stay
-//   callable under other names (ygz_ref_*: a renamed, all-weak second copy of the objects, tests/cpp/build_boundary.sh).  Both forms run here on the
+//   callable under other names (ygz_ref_*: a renamed, all-weak second copy of the objects, oracle/build_boundary.sh).  Both forms run here on the
 //   same objects -- identical mvpMapPoints / MapPoint tracking fields / appended keys / mvMatchedFrom / cache / mvuRight / mvDepth are demanded in
 //   this process, and the medians of both forms are printed ("latency ..." lines).
 // usage: boundary_frame <dir>   reads <dir>/left.u8 right.u8 next.u8 (W x H u8, sizes in <dir>/size.i32), writes *.bin
@@ -29,7 +29,7 @@
 #define protected public
 #include "ORBmatcher.h"          // the reference's: pulls the real Frame.h (whose ORBextractor.h is the product's, same guard)
 #include "SparseImageAlign.h"    // the reference's
-#include "Tracking.h"            // the reference's: src/Tracking.cc itself is in the link, compiled where it lies (tests/cpp/build_boundary.sh)
+#include "Tracking.h"            // the reference's: src/Tracking.cc itself is in the link, compiled where it lies (oracle/build_boundary.sh)
 #undef private
 #undef protected
 
@@ -73,7 +73,7 @@ int MapPoint::PredictScale(const float &, KeyFrame *) { yr_unsupported("MapPoint
 long unsigned int KeyFrame::nNextId = 0;
 void Map::SetReferenceMapPoints(const std::vector<MapPoint *> &) {}   // "This is for visualization" (src/Tracking.cc:1603): the first line of UpdateLocalMap
 }  // namespace ygz
-// the reference's OWN bodies of the three members the batch bindings replace (renamed copies, tests/cpp/build_boundary.sh)
+// the reference's OWN bodies of the three members the batch bindings replace (renamed copies, oracle/build_boundary.sh)
 extern "C" void ygz_ref_Tracking_SearchLocalPoints(ygz::Tracking *);
 extern int ygzf_host_device_frustum_min;   // orb_ygz_slam_amd/csrc/host/TrackingBatched.cc
 extern "C" void ygz_ref_Tracking_SearchLocalPointsDirect(ygz::Tracking *);

@@ -1,4 +1,4 @@
-// tests/cpp/boundary_mappoint.cc -- TEST DRIVER (built by tests/cpp/build_boundary.sh into tests/cpp/bin/libboundary_mappoint.so): the REFERENCE's own
+// tests/cpp/boundary_mappoint.cc -- TEST DRIVER (built by oracle/build_boundary.sh into oracle/_ref/boundary/libboundary_mappoint.so): the REFERENCE's own
 // src/MapPoint.cc, compiled where it lies with the REAL include/MapPoint.h (private members, mutexes and all; KeyFrame / Frame / Map are the plain
 // stand-ins of oracle/ref_shim), linked with the product's MapPointBatch.cc -- whose strong MapPoint::ComputeDistinctiveDescriptors replaces the
 // reference's body -- and libygzf.  The reference's own body stays callable under another name (a renamed, all-weak copy of the object), so the

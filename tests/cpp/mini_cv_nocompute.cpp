@@ -1,4 +1,4 @@
-// tests/cpp/mini_cv_nocompute.cpp -- TEST INFRASTRUCTURE for the boundary build (tests/cpp/build_boundary.sh).
+// tests/cpp/mini_cv_nocompute.cpp -- TEST INFRASTRUCTURE for the boundary build (oracle/build_boundary.sh).
 // oracle/ref_shim/mini_cv.h stands in for the OpenCV headers (OpenCV is not installed here).  In the oracle's builds of the reference its
 // compute primitives (cv::resize, cv::GaussianBlur, cv::FAST, cv::fastAtan2, cv::copyMakeBorder) are bodies on top of the oracle's
 // restatements; in the BOUNDARY build the reference's src/ORBextractor.cc is replaced by the product's class shell over libygzf, so none

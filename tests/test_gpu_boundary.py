@@ -1,7 +1,7 @@
-"""GPU test of the drop-in boundary: tests/cpp/bin/boundary_frame is the REFERENCE's own src/Frame.cc (real include/Frame.h, its
+"""GPU test of the drop-in boundary: oracle/_ref/boundary/boundary_frame is the REFERENCE's own src/Frame.cc (real include/Frame.h, its
 constructors, ExtractFeatures with its two extraction threads, ComputeStereoMatches, AssignFeaturesToGrid, isInFrustum) linked against the
 PRODUCT's class shells (orb_ygz_slam_amd/csrc/host: ORBextractor.h in place of the reference's header, ORBmatcher.cc / SparseImageAlign.cc
-defining the members of the reference's own, unchanged class declarations) and libygzf.so -- built by tests/cpp/build_boundary.sh where the
+defining the members of the reference's own, unchanged class declarations) and libygzf.so -- built by oracle/build_boundary.sh (from build()) where the
 reference checkout exists.  The OpenCV stand-in's compute primitives abort in that binary, so every pyramid, keypoint and descriptor below
 came out of the HIP library.  Everything the reference code produced through that path must equal the oracle."""
 import os
@@ -15,13 +15,13 @@ from orb_ygz_slam_amd.scene import two_view_scene
 from tests.conftest import ROOT
 
 pytestmark = pytest.mark.gpu
-EXE = os.path.join(ROOT, "tests", "cpp", "bin", "boundary_frame")
+BIN = os.path.join(ROOT, "oracle", "_ref", "boundary")
+EXE = os.path.join(BIN, "boundary_frame")
+MAPPOINT_LIB = os.path.join(BIN, "libboundary_mappoint.so")
 
 
 def test_reference_frame_over_product_shells(oracle, tmp_path):
-    if os.path.isdir("/root/reference"):
-        subprocess.check_call([os.path.join(ROOT, "tests", "cpp", "build_boundary.sh")])
-    assert os.path.exists(EXE), "tests/cpp/bin/boundary_frame missing: run tests/cpp/build_boundary.sh where /root/reference exists"
+    assert os.path.exists(EXE), "oracle/_ref/boundary/boundary_frame missing: build() makes it where the reference checkout exists"
     from orb_ygz_slam_amd import load_library
     load_library()
     w, h, NF, L, depth = 752, 480, 1000, 8, np.float32(4.0)
@@ -215,16 +215,14 @@ def test_reference_frame_over_product_shells(oracle, tmp_path):
 
 
 def test_reference_mappoint_over_product_batch(oracle):
-    """tests/cpp/bin/libboundary_mappoint.so: the reference's own src/MapPoint.cc (REAL include/MapPoint.h: private members, mutexes) under the product's
+    """oracle/_ref/boundary/libboundary_mappoint.so: the reference's own src/MapPoint.cc (REAL include/MapPoint.h: private members, mutexes) under the product's
     MapPointBatch.cc.  On the same MapPoint objects: the reference's own CPU body of ComputeDistinctiveDescriptors, the product's strong member called
     per point (one device call each) and ygz::ComputeDistinctiveDescriptorsBatch (ONE device call) must pick the same observation -- and the oracle's.
     Includes points without observations, with one, with bad KeyFrames among them, with identical descriptors (first minimum wins) and with more
     than 256 observations (the histogram kernel)."""
     import ctypes as C
-    if os.path.isdir("/root/reference"):
-        subprocess.check_call([os.path.join(ROOT, "tests", "cpp", "build_boundary.sh")])
-    lib = os.path.join(ROOT, "tests", "cpp", "bin", "libboundary_mappoint.so")
-    assert os.path.exists(lib), "tests/cpp/bin/libboundary_mappoint.so missing: run tests/cpp/build_boundary.sh where /root/reference exists"
+    lib = MAPPOINT_LIB
+    assert os.path.exists(lib), "oracle/_ref/boundary/libboundary_mappoint.so missing: build() makes it where the reference checkout exists"
     from orb_ygz_slam_amd import load_library
     load_library()
     B = C.CDLL(lib)
@@ -265,7 +263,7 @@ def test_shell_failures_are_observable():
     """The reference's signatures have no error channel, so a shell whose device call fails can only return "nothing": ygzf_host::failure_count() /
     last_failure() / set_failure_callback make that visible.  Provoked here with a device that does not exist."""
     import ctypes as C
-    lib = os.path.join(ROOT, "tests", "cpp", "bin", "libboundary_mappoint.so")
+    lib = MAPPOINT_LIB
     assert os.path.exists(lib)
     from orb_ygz_slam_amd import load_library
     load_library()

@@ -195,7 +195,8 @@ def test_bench_two_ranks_on_one_gpu():
     per-rank extras of the REAL bench path (the end-to-end pipeline, the other workloads) run in two processes -- what cannot be tried here is RCCL itself."""
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29571",
-           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--batch", "768", "--passes", "1", "--other-steps", "2"]
+           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "2", "--warmup", "1", "--batch", "768", "--passes", "1", "--other-steps", "2",
+           "--full"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=1500, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-4000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

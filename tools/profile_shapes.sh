@@ -19,7 +19,7 @@ for s in $SHAPES; do
     fhd)   W="--workload fhd1920x1080_8lvl_4000feat --distinct 24";;
     align) W="--align";;
   esac
-  BENCH="python $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extras $W"
+  BENCH="python $REPO/bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --no-extras $W"
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/${s}_stats -o stats -- $BENCH > $OUT/${s}_stats.log 2>&1
   timeout 300 rocprofv3 --pmc FETCH_SIZE --kernel-trace --output-format csv -d $OUT/${s}_fetch -o fetch -- $BENCH > $OUT/${s}_fetch.log 2>&1
   timeout 300 rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $OUT/${s}_write -o write -- $BENCH > $OUT/${s}_write.log 2>&1
