@@ -121,7 +121,11 @@ int ygzf_phase_clocks(ygzf_ctx *ctx, int kernel, unsigned long long *out16, int 
  * follows, and it counts as an extraction for the batch calls' "previous frame" (ygzf_match_batch_prev / ygzf_align_batch_prev). */
 int ygzf_set_extract_ahead(ygzf_ctx *ctx, int on);
 /* The carried "previous frame" (default on).  Every batch extraction first copies the last frame of the batch before it into slot 0 of the result arrays: the
- * Last frame of pair 0 in ygzf_match_batch_prev / ygzf_align_batch_prev (the reference: Tracking keeps mLastFrame, src/Tracking.cc:1262).  A caller that only
+ * Last frame of pair 0 in ygzf_match_batch_prev / ygzf_align_batch_prev (the reference: Tracking keeps mLastFrame, src/Tracking.cc:1262).  "The batch before
+ * it" is the last frame the context extracted, by whichever entry point: ygzf_extract, ygzf_extract_batch_*, ygzf_extract_resident (a ygzf_compute_pyramid
+ * in between does not change it).  A call of another image size than the context's previous one carries nothing: pair 0 of its match has an empty Last
+ * frame (no matches), and the call after it carries again; the same after the calls that take the context's device buffers for their own inputs
+ * (ygzf_extract_dso and its multi-level form, ygzf_extract_fast_keypoint, ygzf_compute_stereo_matches).  A caller that only
  * extracts (or only pairs stereo eyes) can switch it off: one launch less per extraction, and a host-frame call's upload no longer waits behind it.  While it is
  * off ygzf_match_batch_prev and ygzf_align_batch_prev return YGZF_ERR_STATE; switched on again, the next extraction carries the then-last frame as usual. */
 int ygzf_set_carry_previous(ygzf_ctx *ctx, int on);
@@ -335,7 +339,8 @@ int ygzf_search_by_projection_mappoints(ygzf_ctx *ctx, const ygzf_frame_view *F,
                                         int check_level, float nnratio, uint8_t *owner, int *match, int *nmatches);
 
 /* Batched, device-resident form chained behind ygzf_extract_batch_*: frame f of the batch is CurrentFrame, frame f-1 is
- * LastFrame (for f == 0: the last frame of the previous batch of this context, or an empty frame).  Identity relative
+ * LastFrame (for f == 0: the last frame of the previous batch of this context, or an empty frame -- the first batch, the first after a change of image
+ * size: ygzf_set_carry_previous).  Identity relative
  * pose; every Last keypoint carries a MapPoint at its unit-depth back-projection ((x-cx)/fx, (y-cy)/fy, 1) whose
  * descriptor is the keypoint's own -- the synthetic scenario of the extract+match metric. */
 int ygzf_match_batch_prev(ygzf_ctx *ctx, const ygzf_camera *cam, float th, int b_mono, int check_level, int check_orientation);

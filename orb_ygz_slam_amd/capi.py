@@ -283,6 +283,7 @@ class Extractor:
         outs = [np.zeros(self.level_size(w, h, l)[::-1], np.uint8) for l in range(self.nlevels)]
         arr = (C.c_void_p * self.nlevels)(*[o.ctypes.data for o in outs])
         self._ck(self.L.ygzf_compute_pyramid(self.h, _p(img), w, h, w, arr))
+        self._wh = (w, h, 1)                    # (with extract-ahead the extraction of this frame is the context's last batch)
         return outs
 
     def extract(self, img):
@@ -295,6 +296,7 @@ class Extractor:
         d = np.zeros((max(cap, 1), 32), np.uint8)
         n = C.c_int()
         self._ck(self.L.ygzf_extract(self.h, img.ctypes.data_as(C.c_void_p), w, h, int(img.strides[0]), _p(k), _p(d), cap, C.byref(n)))
+        self._wh = (w, h, 1)                    # a batch of one frame: what match_batch_prev / match_counts then see
         return k[:n.value].copy(), d[:n.value].copy()
 
     def extract_resident(self, w, h):
@@ -304,6 +306,7 @@ class Extractor:
         d = np.zeros((max(cap, 1), 32), np.uint8)
         n = C.c_int()
         self._ck(self.L.ygzf_extract_resident(self.h, _p(k), _p(d), cap, C.byref(n)))
+        self._wh = (w, h, 1)
         return k[:n.value].copy(), d[:n.value].copy()
 
     def extract_batch_host(self, imgs):

@@ -1599,6 +1599,10 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         __syncthreads();
         if (!s_flagA) {                        // (uniform) nobody came: the whole level again, alone
             alone = true;
+            if (dbg && tid == 0) {
+                atomicAdd((unsigned long long *) &dbg[kOctDbgAlone + l], 1ull);
+                if (f < 64) atomicOr((unsigned long long *) &dbg[kOctDbgAloneFrames], 1ull << f);
+            }
             __syncthreads();
             goto restart;
         }

@@ -354,6 +354,7 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
         c->pyrHeld = false;
         c->aheadPending = false;
         c->carryValid = false;
+        c->carrySlot = 0;
         c->lastFrames = 0;
         HIPCHECK(c, hipStreamSynchronize(c->stream));
         rc = ensure(c, c->dGeom, sizeof(LevelGeom) * L);
@@ -505,13 +506,14 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
     if (c->octGlobalNodes && (rc = ensure(c, c->dOctNodes, B * L * 19 * (size_t) G.kpCapMax * sizeof(int) + 64))) return rc;
     const size_t kp = std::max<size_t>(B * G.kpStride, 16);
     const size_t kp1 = std::max<size_t>((B + 1) * G.kpStride, 16);  // + carry slot
-    void *oldCnt = c->dOutCnt.p, *oldKp = c->dOutKp.p;
+    // (a buffer that grows loses its contents -- the carried frame with them -- even where the new allocation lands at the old address)
+    const size_t oldCnt = c->dOutCnt.bytes, oldKp = c->dOutKp.bytes, oldDesc = c->dOutDesc.bytes;
     if ((rc = ensure(c, c->dLvlXY, kp * sizeof(unsigned))) || (rc = ensure(c, c->dLvlScore, kp)) ||
         (rc = ensure(c, c->dLvlCnt, B * L * sizeof(int))) || (rc = ensure(c, c->dLvlBase, B * kMaxLevels * sizeof(int))) || (rc = ensure(c, c->dProcOrder, kp * sizeof(uint2))) || (rc = ensure(c, c->dLvlCand, B * L * sizeof(int))) ||
         (rc = ensure(c, c->dOutKp, kp1 * sizeof(ygzf_kp))) || (rc = ensure(c, c->dOutDesc, kp1 * 32)) ||
         (rc = ensure(c, c->dOutCnt, (B + 1) * sizeof(int))))
         return rc;
-    if (oldCnt != c->dOutCnt.p || oldKp != c->dOutKp.p) c->carryValid = false;
+    if (oldCnt != c->dOutCnt.bytes || oldKp != c->dOutKp.bytes || oldDesc != c->dOutDesc.bytes) c->carryValid = false;
     return YGZF_OK;
 }
 
@@ -596,7 +598,7 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady,
     if (!c->carryLaunched) {
         if (c->carryOff) c->slot0Stale = true;
         else {
-            launch_carry_slot(c->stream, outKp, outDesc, outCnt, (c->carryValid && c->lastFrames > 0 && G.kpStride > 0) ? (long long) c->lastFrames : 0, G.kpStride);
+            launch_carry_slot(c->stream, outKp, outDesc, outCnt, (c->carryValid && c->carrySlot > 0 && G.kpStride > 0) ? (long long) c->carrySlot : 0, G.kpStride);
             c->slot0Stale = false;
         }
     }
@@ -694,6 +696,7 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady,
             odbg = (long long *) c->dTmpA.p;
             HIPCHECK(c, hipMemsetAsync(odbg, 0, kOctDbgWords * sizeof(long long), c->stream));
         }
+        int smallHelpers = 0;   // workgroups per (level, frame) of the small plan's launch (0: another plan)
         {
             hipStream_t so = c->stream;
             ProfScope ps(c, KK_OCTREE, so);
@@ -708,19 +711,25 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady,
                 int *gHist = nullptr, *gDone = nullptr;
                 if (helpers > 1) {
                     const size_t words = (size_t) nFrames * L * (helpers - 1) * grp.histBins, bytes = (words + 64) * sizeof(int) + (size_t) nFrames * L * sizeof(int);
-                    void *old = c->dOctHist.p;
                     int rcH = ensure(c, c->dOctHist, bytes);
                     if (rcH) return rcH;
-                    // the counters only grow -- by helpers - 1 per launch -- and are zeroed once per layout
-                    if (old != c->dOctHist.p || c->octHistWords != words || c->octDoneTarget > (1 << 30)) {
-                        HIPCHECK(c, hipMemsetAsync((int *) c->dOctHist.p + words, 0, (size_t) nFrames * L * sizeof(int), so));
-                        c->octHistWords = words;
+                    // The counters only grow -- by helpers - 1 per launch, each of the nFrames * L that the launch addresses -- and are zeroed once per
+                    // layout.  The layout is everything that decides which counters a launch bumps and by how much: frames, helpers, bins and the
+                    // allocation (ensure() only ever reallocates to a larger size, which may come back at the same address).  words alone is not a
+                    // key: 6 frames x 5 helpers and 8 x 4 give the same (256 CUs, 8 levels), and after 8, 6, 8 frames counters 48..63 would lag
+                    // the target for good.  Everything behind the helpers' slices is cleared, not only the launch's counters (the slices are
+                    // written before they are read).
+                    const ygzf_ctx::OctHistLayout lay{nFrames, helpers, grp.histBins, c->dOctHist.bytes};
+                    if (!(lay == c->octHistLayout) || c->octDoneTarget > (1 << 30)) {
+                        HIPCHECK(c, hipMemsetAsync((int *) c->dOctHist.p + words, 0, c->dOctHist.bytes - words * sizeof(int), so));
+                        c->octHistLayout = lay;
                         c->octDoneTarget = 0;
                     }
                     c->octDoneTarget += helpers - 1;
                     gHist = (int *) c->dOctHist.p;
                     gDone = gHist + words;
                 }
+                smallHelpers = helpers;
                 launch_octree(so, dGeom, L, grp.l0, grp.n, (const unsigned short *) c->dCellCnt.p, (const unsigned *) c->dSlots.p,
                               G.totalCells, G.totalSlots, (unsigned *) c->dK0.p, (unsigned *) c->dV0.p, (unsigned *) c->dK1.p,
                               (unsigned *) c->dV1.p, (unsigned *) c->dXY.p, G.candStride, (unsigned *) c->dLvlXY.p,
@@ -763,6 +772,11 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady,
                 for (int l = 0; l < L; l++) fprintf(stderr, " %lld", st[16 * 8 + l]);
                 fprintf(stderr, "]\n");
             }
+            if (smallHelpers) {
+                fprintf(stderr, "[ygzf octree small plan: %d frames, %d workgroups per level; workgroups 0 that gave up waiting for their helpers, per level:", nFrames, smallHelpers);
+                for (int l = 0; l < L; l++) fprintf(stderr, " %lld", st[kOctDbgAlone + l]);
+                fprintf(stderr, "; frames mask 0x%llx]\n", (unsigned long long) st[kOctDbgAloneFrames]);
+            }
         }
         {
             ProfScope ps(c, KK_DESCRIBE);
@@ -779,6 +793,7 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady,
     c->pyrHeldW = G.w;
     c->pyrHeldH = G.h;
     c->lastFrames = nFrames;
+    c->carrySlot = nFrames;
     c->lastFs = fs;
     c->carryValid = true;
     c->lastMatchPairs = 0;
@@ -1255,7 +1270,7 @@ static void carry_early(ygzf_ctx *c) {
     if (c->carryOff) { c->slot0Stale = true; return; }
     c->slot0Stale = false;
     launch_carry_slot(c->stream, (ygzf_kp *) c->dOutKp.p, (uint8_t *) c->dOutDesc.p, (int *) c->dOutCnt.p,
-                      (c->carryValid && c->lastFrames > 0 && G.kpStride > 0) ? (long long) c->lastFrames : 0, G.kpStride);
+                      (c->carryValid && c->carrySlot > 0 && G.kpStride > 0) ? (long long) c->carrySlot : 0, G.kpStride);
     c->carryLaunched = true;
 }
 

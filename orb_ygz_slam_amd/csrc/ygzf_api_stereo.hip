@@ -76,6 +76,11 @@ int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf) {
     if (!(mb > 0)) return fail(l, YGZF_ERR_INVALID, "baseline mb must be positive");
     const Geometry &G = l->geo;
     if (G.kpStride != r->geo.kpStride || G.w != r->geo.w || G.h != r->geo.h) return fail(l, YGZF_ERR_STATE, "the two eyes differ in geometry");
+    // (the pairing reads both eyes' keypoints with the left context's scale tables and level layout: equal sizes are not enough)
+    const ygzf_extractor_cfg &cl = l->tab.cfg, &cr = r->tab.cfg;
+    if (cl.nlevels != cr.nlevels || cl.scale_factor != cr.scale_factor || cl.nfeatures != cr.nfeatures || cl.cv_mode != cr.cv_mode)
+        return fail(l, YGZF_ERR_STATE, "the two eyes' extractors differ (nlevels %d / %d, scale factor %g / %g, nfeatures %d / %d, cv mode %d / %d)", cl.nlevels,
+                    cr.nlevels, (double) cl.scale_factor, (double) cr.scale_factor, cl.nfeatures, cr.nfeatures, cl.cv_mode, cr.cv_mode);
     if (G.kpStride > 65535) return fail(l, YGZF_ERR_UNSUPPORTED, "more than 65535 keypoints per frame");
     int rc;
     const size_t per = (size_t) G.kpStride;

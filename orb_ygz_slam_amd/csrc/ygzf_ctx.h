@@ -78,6 +78,9 @@ struct ygzf_ctx {
     int lastAlignPairs = 0;
     std::vector<unsigned char> alKey;   // cache key of the uploaded SiaLevel tables
     bool carryValid = false;
+    // the output slot that holds the last frame an extraction produced (0: none), which the next extraction carries into slot 0.  Not lastFrames:
+    // ygzf_compute_pyramid ends the batch (its pyramid replaces frame 0's) but leaves the keypoints -- the Frame path's ygzf_extract_resident carries them
+    int carrySlot = 0;
     int lastMatchPairs = 0;
     int identityPoses = 0;
     void *identityPosesPtr = nullptr;
@@ -91,8 +94,12 @@ struct ygzf_ctx {
     bool haveOctSmall = false;
     bool carryOff = false;     // ygzf_set_carry_previous(0): extractions do not carry the previous batch's last frame into slot 0 ...
     bool slot0Stale = false;   // ... and slot 0 no longer holds it: the batch matchers refuse until an extraction has carried again
-    size_t octHistWords = 0;
-    int octDoneTarget = 0;     // what the launches so far have brought every (level, frame) counter of dOctHist to   // layout dOctHist's counters were last cleared for (k_octree's helper workgroups)
+    struct OctHistLayout {     // what dOctHist's hand-over counters were last cleared for (k_octree's helper workgroups)
+        int frames = 0, helpers = 0, histBins = 0;
+        size_t bytes = 0;      // the allocation: ensure() reallocates only to a larger size
+        bool operator==(const OctHistLayout &o) const { return frames == o.frames && helpers == o.helpers && histBins == o.histBins && bytes == o.bytes; }
+    } octHistLayout;
+    int octDoneTarget = 0;     // what the launches since that clear have brought every (level, frame) counter of the layout to
     static constexpr int octSmallWgs = 128;   // launches of up to this many workgroups take it (752x480: 16 frames 0.211 against 0.221 ms, 64 frames 0.439 against 0.430)
     Buf dOctNodes;
     // FAST threshold plan (extract_kernels.hip, fast_cell): 0 = chosen per batch from the statistics the kernel leaves behind, 1 = one pass at

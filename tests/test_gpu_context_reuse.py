@@ -1,0 +1,240 @@
+"""One long-lived context across changing launches: a tracking thread keeps its context for a whole sequence and the multi-GPU entry points hand
+a slot's context chunks of changing length (csrc/ygzf_mgpu.hip: the last chunk of a call is shorter).  Whatever a context keeps from one launch
+to the next -- the octree's helper hand-over counters (keyed on the launch's layout), the plans chosen by frame count (k_pyr_strips up to
+pyrStripFrames, the small octree plan up to 128 workgroups, the one-frame pyramid graph), the geometry and the carried previous frame -- must
+give every call the bytes of the CPU oracle, whichever launch came before.  Every call is checked: keypoints (all fields), descriptors and the
+matches of ygzf_match_batch_prev (pair 0 against the last frame the context extracted)."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+from tests.test_gpu_mgpu import _clip
+
+pytestmark = pytest.mark.gpu
+
+W, H, NF, NL, TH = 1920, 1080, 4000, 8, 15.0
+
+
+class _env:
+    """YGZF_FORCE / YGZF_DEBUG (csrc/ygzf_internal.h) while a context is created: both are read there"""
+    def __init__(self, debug=None, **force):
+        self.debug, self.force = debug, force
+
+    def __enter__(self):
+        from orb_ygz_slam_amd.capi import force_env
+        self.old = {k: os.environ.get(k) for k in ("YGZF_FORCE", "YGZF_DEBUG")}
+        os.environ["YGZF_FORCE"] = force_env(**self.force)
+        if self.debug:
+            os.environ["YGZF_DEBUG"] = self.debug
+        else:
+            os.environ.pop("YGZF_DEBUG", None)
+
+    def __exit__(self, *a):
+        for k, v in self.old.items():
+            if v is None:
+                os.environ.pop(k, None)
+            else:
+                os.environ[k] = v
+
+
+class _Oracle:
+    """the oracle's keypoints / descriptors per image and its SearchByProjection(Cur, Last) per (cur, last) pair, each computed once"""
+    def __init__(self, oracle):
+        from orb_ygz_slam_amd import EUROC
+        self.O, self.cam = oracle, EUROC
+        self.oex = oracle.Extractor(NF, 1.2, NL, 20, 7)
+        self.sf = self.oex.tables()["scale"]
+        self.kd, self.mt = {}, {}
+
+    def extract(self, key, img):
+        if key not in self.kd:
+            self.kd[key] = self.oex.extract(img)
+        return self.kd[key]
+
+    def match(self, cur, last, w, h):
+        if (cur, last) not in self.mt:
+            (k, d), (pk, pd) = self.kd[cur], self.kd[last]
+            c = self.cam
+            world = np.stack([(pk["x"] - np.float32(c["cx"])) / np.float32(c["fx"]), (pk["y"] - np.float32(c["cy"])) / np.float32(c["fy"]),
+                              np.ones(len(pk), np.float32)], -1).astype(np.float32)
+            I, z = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
+            self.mt[(cur, last)] = self.O.search_by_projection_last(k, d, self.sf, w, h, c, pk, world, pd, I, z, I, z, TH, True, True, True)
+        return self.mt[(cur, last)]
+
+
+_IMGS = {}
+
+
+def _images(w, h, n=4):
+    """n distinct frames of one scene, a few pixels apart (tests/test_gpu_mgpu.py's clip): matches between any two of them"""
+    if (w, h, n) not in _IMGS:
+        _IMGS[(w, h, n)] = _clip(n, w, h)
+    return _IMGS[(w, h, n)]
+
+
+@pytest.fixture(scope="module")
+def orc(oracle):
+    return _Oracle(oracle)
+
+
+def _check(ex, orc, keys, last, w, h, tag):
+    """the context's last extraction held the frames `keys` (key = (w, h, index into _images)); pair 0 of the matcher must pair the first
+    with `last` -- the key of the frame the context extracted before them, or None: an empty Last frame, no matches"""
+    from orb_ygz_slam_amd import make_camera
+    imgs = _images(w, h)
+    ex.match_batch_prev(make_camera(w, h), TH, True, True, True)
+    counts = ex.match_counts()
+    assert len(counts) == len(keys)
+    for f, key in enumerate(keys):
+        k, d = ex.batch_fetch(f)
+        ok, od = orc.extract(key, imgs[key[2]])
+        assert len(k) == len(ok) and (k == ok).all() and (d == od).all(), (tag, f, "keypoints / descriptors")
+        m, o = ex.match_fetch(f)
+        prev = last if f == 0 else keys[f - 1]
+        if prev is None:
+            assert counts[f] == 0, (tag, f, "an empty Last frame")
+            continue
+        n, em, eo = orc.match(key, prev, w, h)
+        assert counts[f] == n and (m[:len(k)] == em).all() and (o[:len(k)] == eo).all(), (tag, f, prev, "matches")
+
+
+def _run(ex, orc, sizes, w=W, h=H, t0=0, last=None, after=None):
+    """consecutive batches of the given sizes on ex; frame t of the stream is image t % 4.  -> (next t, key of the last frame)"""
+    imgs = _images(w, h)
+    t = t0
+    for i, n in enumerate(sizes):
+        keys = [(w, h, (t + j) % len(imgs)) for j in range(n)]
+        ex.extract_batch_host(np.stack([imgs[k[2]] for k in keys]))
+        _check(ex, orc, keys, last, w, h, (w, h, sizes, i))
+        if after:
+            after(n)
+        t, last = t + n, keys[-1]
+    return t, last
+
+
+# launch sizes whose octree hand-over layout words = frames x levels x (helpers - 1) x bins collides on 256 CUs (6 / 8, 3 / 7, 2 / 14), and a walk
+# across the small-octree limit (16 -> 17 frames of 8 levels) and pyrStripFrames in both directions, from and back to one-frame launches
+SEQS = [[8, 6, 8, 8], [6, 8, 6], [3, 7, 3, 7], [2, 14, 2], [1, 4, 9, 16, 17, 20, 16, 9, 1]]
+
+
+@pytest.mark.parametrize("seq", SEQS, ids=["-".join(map(str, s)) for s in SEQS])
+def test_batch_size_sequences_on_one_context(orc, seq):
+    """1920x1080 / 8 levels / 4000 features, the library's own plans: every call of the sequence equals the oracle"""
+    from orb_ygz_slam_amd import Extractor
+    with _env():
+        ex = Extractor(NF, 1.2, NL, 20, 7, max_width=W, max_height=H, max_batch=20)
+    _run(ex, orc, seq)
+    ex.close()
+
+
+_SMALL = re.compile(r"\[ygzf octree small plan: (\d+) frames, (\d+) workgroups per level; workgroups 0 that gave up waiting for their helpers, "
+                    r"per level:([ \d]+); frames mask (0x[0-9a-f]+)\]")
+
+
+@pytest.mark.parametrize("seq", SEQS, ids=["-".join(map(str, s)) for s in SEQS])
+def test_no_workgroup_gives_up_on_its_helpers(orc, seq, capfd):
+    """The same sequences on a context with YGZF_DEBUG=oct: k_octree counts the workgroups 0 that stopped waiting for their helper workgroups and
+    computed a level alone, and the library prints the counts of every small-plan launch.  Nothing else runs on the device, so every helper starts
+    at once: a give-up can only mean hand-over counters that lag the target the host passes (stale from an earlier launch of another layout)."""
+    from orb_ygz_slam_amd import Extractor
+    with _env(debug="oct"):
+        ex = Extractor(NF, 1.2, NL, 20, 7, max_width=W, max_height=H, max_batch=20)
+    capfd.readouterr()
+    seen = []
+
+    def after(n):
+        lines = _SMALL.findall(capfd.readouterr().err)
+        if n * NL <= 128:                                       # the small plan's launches (ygzf_ctx.h, octSmallWgs)
+            assert len(lines) == 1, (seq, n, lines)
+        for frames, helpers, per_level, mask in lines:
+            assert int(frames) == n
+            seen.append(int(helpers))
+            gave_up = [int(v) for v in per_level.split()]
+            assert len(gave_up) == NL
+            assert sum(gave_up) == 0 and int(mask, 16) == 0, "workgroups 0 gave up on their helpers: %d frames, %d per (level, frame), per level %s, frames mask %s" % (
+                n, int(helpers), gave_up, mask)
+    _run(ex, orc, seq, after=after)
+    ex.close()
+    assert max(seen) > 1                                        # the sequence did take the helpers' plan (1920x1080 on a device of >= 128 CUs)
+
+
+def test_image_size_switches_on_one_context(orc):
+    """One context created for 1920x1080 takes 1920x1080 -> 752x480 -> 1280x720 -> 1920x1080 with changing batch sizes.  A new size rebuilds the
+    geometry: the first match after it has an empty Last frame for pair 0 (include/ygzf.h), the next call carries again."""
+    from orb_ygz_slam_amd import Extractor
+    with _env():
+        ex = Extractor(NF, 1.2, NL, 20, 7, max_width=W, max_height=H, max_batch=20)
+    last = None
+    for (w, h), sizes in (((W, H), [8, 3]), ((752, 480), [5, 1, 12]), ((1280, 720), [2, 9, 4]), ((W, H), [6, 8, 1])):
+        _, last = _run(ex, orc, sizes, w, h, t0=1, last=None)   # (last=None: the size changed, nothing is carried into the first call)
+    assert last is not None
+    ex.close()
+
+
+def test_entry_points_interleaved(orc):
+    """ygzf_extract (one frame), ygzf_extract_batch_host and ygzf_compute_pyramid + ygzf_extract_resident on one 1920x1080 context: after each,
+    pair 0 of ygzf_match_batch_prev pairs the first frame with the last frame the context extracted -- whichever entry point extracted it."""
+    from orb_ygz_slam_amd import Extractor
+    imgs = _images(W, H)
+    with _env():
+        ex = Extractor(NF, 1.2, NL, 20, 7, max_width=W, max_height=H, max_batch=20)
+    key = lambda i: (W, H, i)
+    last = None
+
+    def one(i):
+        k, d = ex.extract(imgs[i])
+        ok, od = orc.extract(key(i), imgs[i])
+        assert len(k) == len(ok) and (k == ok).all() and (d == od).all()
+
+    def resident(i):
+        ex.compute_pyramid(imgs[i])
+        k, d = ex.extract_resident(W, H)
+        ok, od = orc.extract(key(i), imgs[i])
+        assert len(k) == len(ok) and (k == ok).all() and (d == od).all()
+
+    for step, (kind, idx) in enumerate([("one", [0]), ("batch", [1, 2, 3]), ("resident", [0]), ("one", [1]), ("resident", [2]),
+                                        ("resident", [3]), ("batch", [0, 1]), ("resident", [2]), ("batch", [3, 0, 1, 2, 3])]):
+        if kind == "one":
+            one(idx[0])
+        elif kind == "resident":
+            resident(idx[0])
+        else:
+            ex.extract_batch_host(np.stack([imgs[i] for i in idx]))
+        keys = [key(i) for i in idx]
+        _check(ex, orc, keys, last, W, H, (step, kind))
+        last = keys[-1]
+    ex.close()
+
+
+def _mgpu_check(orc, frames, got, unit, tag):
+    k, d, c, m, nm = got
+    for f in range(len(frames)):
+        ok, od = orc.extract(("mgpu", f), frames[f])
+        n = c[f]
+        assert n == len(ok) and (k[f, :n] == ok).all() and (d[f, :n] == od).all(), (tag, f, "keypoints / descriptors")
+        if f % unit == 0:
+            assert nm[f] == -1, (tag, f)                        # the first frame of a unit has no predecessor
+            continue
+        en, em, _ = orc.match(("mgpu", f), ("mgpu", f - 1), frames.shape[2], frames.shape[1])
+        assert nm[f] == en and (m[f, :n] == em).all(), (tag, f, "matches")
+
+
+def test_mgpu_tail_chunks_on_one_slot(orc):
+    """ygzf_mgpu_extract_match on one device slot with chunks of 8 frames.  Long units (unit = the call's frames): every chunk on context 0 of the
+    slot -- 14 frames as 8 + 6, again, then 16 as 8 + 8.  Short units (unit 2 <= chunk): chunks alternate between the slot's two contexts -- 22
+    frames as 8 / 8 / 6, context 0 takes 8 then 6."""
+    from orb_ygz_slam_amd import MultiGpu, make_camera
+    frames = _clip(22, W, H)
+    cam = make_camera(W, H)
+    with _env(mgpu_chunk=8):
+        mg = MultiGpu([0], NF, 1.2, NL, 20, 7, max_width=W, max_height=H, max_frames_per_device=22)
+    assert mg.chunk_frames() == 8
+    for i, n in enumerate((14, 14, 16)):
+        got = mg.extract_match(frames[:n], unit=n, cam=cam, th=TH)
+        _mgpu_check(orc, frames[:n], got, n, ("long unit", i, n))
+    for i in range(2):
+        got = mg.extract_match(frames, unit=2, cam=cam, th=TH)
+        _mgpu_check(orc, frames, got, 2, ("short units", i))
+    mg.close()

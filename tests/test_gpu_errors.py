@@ -150,6 +150,16 @@ def test_round6_entry_points_report_misuse():
     assert n > 50 and (ur[:n] >= 0).sum() > n // 4
     k0, d0 = a.batch_fetch(0)
     assert len(k0) == n
+    # two eyes of one size from extractors that differ: another scale factor (the pairing reads both with the left eye's scale tables), another
+    # blur generation (the same level layout and keypoint stride: only the extractors' settings tell them apart)
+    for other in (Extractor(300, 1.3, 4, 20, 7, max_width=w, max_height=h, max_batch=2),
+                  Extractor(300, 1.2, 4, 20, 7, max_width=w, max_height=h, max_batch=2, cv_mode=2)):
+        assert L.ygzf_stereo_pair_host(*args(a.h, other.h, p(img), p(right), w)) == -5  # YGZF_ERR_STATE
+        assert b"differ" in L.ygzf_last_error(a.h)
+        other.close()
+    assert b"extractors differ" in L.ygzf_last_error(a.h)                            # (the blur generation: nothing but the settings differs)
+    assert L.ygzf_stereo_pair_host(*args(a.h, b.h, p(img), p(right), w)) == 0         # the pair of equal extractors still works
+    assert int(hl[:4].view(np.int32)[0]) == n
     # the probe and the phase clocks
     with pytest.raises(YgzfError):
         host_stream_probe(0, 0, 1 << 26, 0.1)
