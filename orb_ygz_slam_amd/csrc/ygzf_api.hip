@@ -350,12 +350,8 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
         // c->geo is committed only after every fallible step below has succeeded: a failed attempt leaves (w, h) unset, so that a retry
         // runs the whole setup again instead of continuing on partial device tables
         c->geo.w = c->geo.h = 0;
-        c->pyrResident = false;
-        c->pyrHeld = false;
-        c->aheadPending = false;
-        c->carryValid = false;
-        c->carrySlot = 0;
-        c->lastFrames = 0;
+        forget_outputs(c);
+        forget_image(c);
         HIPCHECK(c, hipStreamSynchronize(c->stream));
         rc = ensure(c, c->dGeom, sizeof(LevelGeom) * L);
         if (rc) return rc;
@@ -496,7 +492,12 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
     const Geometry &G = c->geo;
     const size_t B = (size_t) nFrames;
     int rc = 0;
-    if ((rc = ensure(c, c->dPyr, std::max<size_t>(B * G.pyrBytes, 16) + 256))) return rc;
+    // (a buffer that grows loses its contents -- the image and pyramid, the carried frame with the outputs -- even where the new allocation lands
+    // at the old address or fails)
+    const size_t oldPyr = c->dPyr.bytes;
+    rc = ensure(c, c->dPyr, std::max<size_t>(B * G.pyrBytes, 16) + 256);
+    if (oldPyr != c->dPyr.bytes) forget_image(c);
+    if (rc) return rc;
     if ((rc = ensure(c, c->dCellCnt, std::max<size_t>(B * G.totalCells * sizeof(unsigned short), 16)))) return rc;
     if ((rc = ensure(c, c->dSlots, std::max<size_t>(B * G.totalSlots * sizeof(unsigned), 16)))) return rc;
     const size_t cb = std::max<size_t>(B * G.candStride * sizeof(unsigned), 16);
@@ -506,15 +507,13 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
     if (c->octGlobalNodes && (rc = ensure(c, c->dOctNodes, B * L * 19 * (size_t) G.kpCapMax * sizeof(int) + 64))) return rc;
     const size_t kp = std::max<size_t>(B * G.kpStride, 16);
     const size_t kp1 = std::max<size_t>((B + 1) * G.kpStride, 16);  // + carry slot
-    // (a buffer that grows loses its contents -- the carried frame with them -- even where the new allocation lands at the old address)
     const size_t oldCnt = c->dOutCnt.bytes, oldKp = c->dOutKp.bytes, oldDesc = c->dOutDesc.bytes;
     if ((rc = ensure(c, c->dLvlXY, kp * sizeof(unsigned))) || (rc = ensure(c, c->dLvlScore, kp)) ||
-        (rc = ensure(c, c->dLvlCnt, B * L * sizeof(int))) || (rc = ensure(c, c->dLvlBase, B * kMaxLevels * sizeof(int))) || (rc = ensure(c, c->dProcOrder, kp * sizeof(uint2))) || (rc = ensure(c, c->dLvlCand, B * L * sizeof(int))) ||
-        (rc = ensure(c, c->dOutKp, kp1 * sizeof(ygzf_kp))) || (rc = ensure(c, c->dOutDesc, kp1 * 32)) ||
-        (rc = ensure(c, c->dOutCnt, (B + 1) * sizeof(int))))
+        (rc = ensure(c, c->dLvlCnt, B * L * sizeof(int))) || (rc = ensure(c, c->dLvlBase, B * kMaxLevels * sizeof(int))) || (rc = ensure(c, c->dProcOrder, kp * sizeof(uint2))) || (rc = ensure(c, c->dLvlCand, B * L * sizeof(int))))
         return rc;
-    if (oldCnt != c->dOutCnt.bytes || oldKp != c->dOutKp.bytes || oldDesc != c->dOutDesc.bytes) c->carryValid = false;
-    return YGZF_OK;
+    if (!(rc = ensure(c, c->dOutKp, kp1 * sizeof(ygzf_kp))) && !(rc = ensure(c, c->dOutDesc, kp1 * 32))) rc = ensure(c, c->dOutCnt, (B + 1) * sizeof(int));
+    if (oldCnt != c->dOutCnt.bytes || oldKp != c->dOutKp.bytes || oldDesc != c->dOutDesc.bytes) forget_outputs(c);
+    return rc;
 }
 
 // The launch sequence of ORBextractor::operator()(image...) for a batch resident on the device.
@@ -578,45 +577,25 @@ int pyramid_chain(ygzf_ctx *c, const FrameSet &fs, int nFrames) {
 int mark_pyramid_done(ygzf_ctx *c) {
     if (!c->evPyrDone) HIPCHECK(c, hipEventCreateWithFlags(&c->evPyrDone, hipEventDisableTiming));
     HIPCHECK(c, hipEventRecord(c->evPyrDone, c->stream));
-    c->evPyrDoneValid = true;
     return YGZF_OK;
 }
 
 // pyramidReady: dPyr already holds the pyramid of the frame to extract (ygzf_compute_pyramid / ygzf_extract_resident) -- the previous
-// extraction's pyramid is gone from it, so the pyramid carry of ygzf_align_batch_prev is valid only when the caller copied it out BEFORE
-// overwriting dPyr (pyramidCarried; ygzf_compute_pyramid in extract-ahead mode does).
-int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady, bool pyramidCarried) {
+// extraction's pyramid is gone from it: the pyramid carry of ygzf_align_batch_prev is what ygzf_compute_pyramid saved before overwriting dPyr
+// (in extract-ahead mode; none otherwise).
+int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady) {
     const Geometry &G = c->geo;
-    c->pyrResident = false;
-    c->aheadPending = false;
+    pyramid_taken(c);
     const int L = c->tab.cfg.nlevels;
     const LevelGeom *dGeom = (const LevelGeom *) c->dGeom.p;
-    // slot 0 of the output arrays carries the last frame of the previous batch (Last frame of pair 0 in ygzf_match_batch_prev)
-    ygzf_kp *outKp = (ygzf_kp *) c->dOutKp.p;
-    uint8_t *outDesc = (uint8_t *) c->dOutDesc.p;
-    int *outCnt = (int *) c->dOutCnt.p;
-    if (!c->carryLaunched) {
-        if (c->carryOff) c->slot0Stale = true;
-        else {
-            launch_carry_slot(c->stream, outKp, outDesc, outCnt, (c->carryValid && c->carrySlot > 0 && G.kpStride > 0) ? (long long) c->carrySlot : 0, G.kpStride);
-            c->slot0Stale = false;
-        }
-    }
-    c->carryLaunched = false;
-    outKp += G.kpStride;
-    outDesc += (size_t) G.kpStride * 32;
-    outCnt += 1;
-    if (c->alignCarry && !c->carryOff && G.pyrBytes > 0) {   // the previous batch's last pyramid is the reference of pair 0 in ygzf_align_batch_prev
-        int rc2 = ensure(c, c->dCarryPyr, (size_t) G.pyrBytes + 256);
-        if (rc2) return rc2;
-        c->carryPyrValid = c->carryValid && c->lastFrames > 0 && (!pyramidReady || pyramidCarried);
-        if (c->carryPyrValid && !pyramidReady)
-            HIPCHECK(c, hipMemcpyAsync(c->dCarryPyr.p, (uint8_t *) c->dPyr.p + (size_t) (c->lastFrames - 1) * G.pyrBytes, (size_t) G.pyrBytes,
-                                       hipMemcpyDeviceToDevice, c->stream));
-    }
+    // slot 0 of the output arrays carries the last frame of the previous batch (Last frame of pair 0 in ygzf_match_batch_prev); frame f goes to slot f + 1
+    queue_carry(c, false);
+    ygzf_kp *outKp = (ygzf_kp *) c->dOutKp.p + G.kpStride;
+    uint8_t *outDesc = (uint8_t *) c->dOutDesc.p + (size_t) G.kpStride * 32;
+    int *outCnt = (int *) c->dOutCnt.p + 1;
     if (!pyramidReady) {
-        int rcP = pyramid_chain(c, fs, nFrames);
-        if (rcP || (rcP = mark_pyramid_done(c))) return rcP;
+        int rcP = save_carry_pyramid(c);
+        if (rcP || (rcP = pyramid_chain(c, fs, nFrames)) || (rcP = mark_pyramid_done(c))) return rcP;
     }
     if (G.totalCells > 0) {
         int groupBase[kMaxLevels];
@@ -789,16 +768,7 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady,
         HIPCHECK(c, hipMemsetAsync(c->dLvlCand.p, 0, sizeof(int) * nFrames * L, c->stream));
     }
     HIPCHECK(c, hipGetLastError());
-    c->pyrHeld = fs.img0 == (const uint8_t *) c->dImg0.p && fs.pyr == (uint8_t *) c->dPyr.p;   // frame 0 of the context's own buffers
-    c->pyrHeldW = G.w;
-    c->pyrHeldH = G.h;
-    c->lastFrames = nFrames;
-    c->carrySlot = nFrames;
-    c->lastFs = fs;
-    c->carryValid = true;
-    c->lastMatchPairs = 0;
-    c->lastAlignPairs = 0;
-    c->lastStereoPairs = 0;
+    extracted(c, fs, nFrames);
     return YGZF_OK;
 }
 
@@ -822,12 +792,11 @@ int upload_rows(ygzf_ctx *c, void *dst, size_t dstPitch, const uint8_t *src, siz
 
 int upload_frames(ygzf_ctx *c, const uint8_t *imgs, int nFrames, int w, int h, int row_pitch, size_t frame_stride,
                          FrameSet *fs) {
-    c->pyrResident = false;
-    c->aheadPending = false;
-    c->pyrHeld = false;
+    forget_image(c);
     const int pitch = align_up(w, 64);
     int rc = ensure(c, c->dImg0, (size_t) nFrames * pitch * h);
     if (rc) return rc;
+    *fs = own_frames(c, w, h);
     if (nFrames == 1) {
         hipPointerAttribute_t at;
         memset(&at, 0, sizeof at);
@@ -840,11 +809,6 @@ int upload_frames(ygzf_ctx *c, const uint8_t *imgs, int nFrames, int w, int h, i
             L.addr[0] = (unsigned long long) (uintptr_t) at.devicePointer;
             launch_gather_host_frames(c->stream, L, 1, (size_t) row_pitch, (uint8_t *) c->dImg0.p, (size_t) pitch, (size_t) pitch * h, w, h);
             HIPCHECK(c, hipGetLastError());
-            fs->img0 = (const uint8_t *) c->dImg0.p;
-            fs->img0_stride = (long long) pitch * h;
-            fs->img0_pitch = pitch;
-            fs->pyr = (uint8_t *) c->dPyr.p;
-            fs->pyr_stride = c->geo.pyrBytes;
             return YGZF_OK;
         }
         if (pageable) {
@@ -868,11 +832,6 @@ int upload_frames(ygzf_ctx *c, const uint8_t *imgs, int nFrames, int w, int h, i
             HIPCHECK(c, hipGetLastError());
             HIPCHECK(c, hipEventRecord(c->evIn, c->stream));
             c->evInPending = true;
-            fs->img0 = (const uint8_t *) c->dImg0.p;
-            fs->img0_stride = (long long) pitch * h;
-            fs->img0_pitch = pitch;
-            fs->pyr = (uint8_t *) c->dPyr.p;
-            fs->pyr_stride = c->geo.pyrBytes;
             return YGZF_OK;
         }
     }
@@ -892,11 +851,6 @@ int upload_frames(ygzf_ctx *c, const uint8_t *imgs, int nFrames, int w, int h, i
                 return rc;
         }
     }
-    fs->img0 = (const uint8_t *) c->dImg0.p;
-    fs->img0_stride = (long long) pitch * h;
-    fs->img0_pitch = pitch;
-    fs->pyr = (uint8_t *) c->dPyr.p;
-    fs->pyr_stride = c->geo.pyrBytes;
     return YGZF_OK;
 }
 
@@ -1072,7 +1026,7 @@ int ygzf_set_extract_ahead(ygzf_ctx *c, int on) {
         HIPCHECK(c, hipEventCreateWithFlags(&c->evPyramid, hipEventDisableTiming));
     }
     c->extractAhead = on != 0;
-    if (!on) c->aheadPending = false;
+    if (!on) ahead_dropped(c);
     return YGZF_OK;
 }
 
@@ -1179,21 +1133,12 @@ int ygzf_compute_pyramid(ygzf_ctx *c, const uint8_t *img, int w, int h, int stri
     FrameSet fs;
     // extract-ahead counts as an extraction for ygzf_align_batch_prev: the previous extraction's last pyramid (the reference image of pair 0)
     // leaves dPyr before this frame's pyramid is written over it
-    bool pyramidCarried = false;
-    if (c->extractAhead && c->streamCopy && c->alignCarry && !c->carryOff && c->geo.pyrBytes > 0 && c->carryValid && c->lastFrames > 0) {
-        if ((rc = ensure(c, c->dCarryPyr, (size_t) c->geo.pyrBytes + 256))) return rc;
-        HIPCHECK(c, hipMemcpyAsync(c->dCarryPyr.p, (uint8_t *) c->dPyr.p + (size_t) (c->lastFrames - 1) * c->geo.pyrBytes, (size_t) c->geo.pyrBytes,
-                                   hipMemcpyDeviceToDevice, c->stream));
-        pyramidCarried = true;
-    }
+    if (c->extractAhead && c->streamCopy && (rc = save_carry_pyramid(c))) return rc;
     if ((rc = upload_frames(c, img, 1, w, h, stride, 0, &fs))) return rc;
     const Geometry &G = c->geo;
     const int L = c->tab.cfg.nlevels;
     if ((rc = pyramid_chain(c, fs, 1)) || (rc = mark_pyramid_done(c))) return rc;
     HIPCHECK(c, hipGetLastError());
-    c->pyrHeld = true;
-    c->pyrHeldW = w;
-    c->pyrHeldH = h;
     // The levels go back tight (pitch = width) into caller memory that is pageable as a rule (cv::Mat buffers).  Eight pitched device-to-host
     // copies took 10-13 ms for a 752x480 pyramid (the copy engine works an odd-width pitched copy off row by row, into page-locked memory
     // as well): the levels are packed on the device and leave in one linear copy through the context's page-locked staging buffer.
@@ -1226,22 +1171,12 @@ int ygzf_compute_pyramid(ygzf_ctx *c, const uint8_t *img, int w, int h, int stri
         launch_pack_levels(rd, fs, (const LevelGeom *) c->dGeom.p, 1, L, offs, (uint8_t *) c->hStageDev);
         HIPCHECK(c, hipGetLastError());
     } else if (total) HIPCHECK(c, hipMemcpyAsync(c->hStage, c->dTmpC.p, total, hipMemcpyDeviceToHost, rd));
-    if (ahead && (rc = run_extract(c, fs, 1, true, pyramidCarried))) return rc;   // (queued after the copy so that the copy starts while these launches are issued)
+    if (ahead && (rc = run_extract(c, fs, 1, true))) return rc;   // (queued after the copy so that the copy starts while these launches are issued)
     if (levels_out[0] != img || stride != w)
         for (int y = 0; y < h; y++) memcpy(levels_out[0] + (size_t) y * w, img + (size_t) y * stride, (size_t) w);
     HIPCHECK(c, hipStreamSynchronize(rd));
     for (int l = 1; l < L; l++) memcpy(levels_out[l], c->hStage + offs[l], offs[l + 1] - offs[l]);
-    if (ahead) {
-        c->pyrResident = true;
-        c->aheadPending = true;
-        c->pyrResW = w;
-        c->pyrResH = h;
-        return YGZF_OK;
-    }
-    c->lastFrames = 0;
-    c->pyrResident = true;
-    c->pyrResW = w;
-    c->pyrResH = h;
+    pyramid_computed(c, w, h, ahead);
     return YGZF_OK;
 }
 
@@ -1262,25 +1197,13 @@ int ygzf_extract_batch_device(ygzf_ctx *c, const uint8_t *d_imgs, int n_frames, 
     return run_extract(c, fs, n_frames);
 }
 
-// The carry (last frame of the previous batch -> slot 0 of the outputs) depends on nothing an upload brings: queued BEFORE the host frames, it runs
-// while they cross the link instead of between their arrival and the pyramid (6 us of a one-frame call).  run_extract then skips its own.
-static void carry_early(ygzf_ctx *c) {
-    const Geometry &G = c->geo;
-    c->carryLaunched = true;
-    if (c->carryOff) { c->slot0Stale = true; return; }
-    c->slot0Stale = false;
-    launch_carry_slot(c->stream, (ygzf_kp *) c->dOutKp.p, (uint8_t *) c->dOutDesc.p, (int *) c->dOutCnt.p,
-                      (c->carryValid && c->carrySlot > 0 && G.kpStride > 0) ? (long long) c->carrySlot : 0, G.kpStride);
-    c->carryLaunched = true;
-}
-
 int ygzf_extract_batch_host(ygzf_ctx *c, const uint8_t *imgs, int n_frames, int w, int h, int row_pitch, size_t frame_stride) {
     if (!c || !imgs) return fail(c, YGZF_ERR_INVALID, "null argument");
     if (row_pitch < w) return fail(c, YGZF_ERR_INVALID, "row_pitch %d < width %d", row_pitch, w);
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = apply_geometry(c, w, h, n_frames);
     if (rc) return rc;
-    carry_early(c);
+    queue_carry(c, true);
     FrameSet fs;
     if ((rc = upload_frames(c, imgs, n_frames, w, h, row_pitch, frame_stride, &fs))) return rc;
     return run_extract(c, fs, n_frames);
@@ -1298,10 +1221,8 @@ int ygzf_extract_batch_host_frames(ygzf_ctx *c, const uint8_t *const *frames, in
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = apply_geometry(c, w, h, n_frames);
     if (rc) return rc;
-    carry_early(c);
-    c->pyrResident = false;
-    c->aheadPending = false;
-    c->pyrHeld = false;
+    queue_carry(c, true);
+    forget_image(c);
     const int pitch = align_up(w, 64);
     if ((rc = ensure(c, c->dImg0, (size_t) n_frames * pitch * h))) return rc;
     {
@@ -1366,27 +1287,21 @@ int ygzf_extract_batch_host_frames(ygzf_ctx *c, const uint8_t *const *frames, in
         HIPCHECK(c, hipGetLastError());
     }
 uploaded:
-    FrameSet fs;
-    fs.img0 = (const uint8_t *) c->dImg0.p;
-    fs.img0_stride = (long long) pitch * h;
-    fs.img0_pitch = pitch;
-    fs.pyr = (uint8_t *) c->dPyr.p;
-    fs.pyr_stride = c->geo.pyrBytes;
-    return run_extract(c, fs, n_frames);
+    return run_extract(c, own_frames(c, w, h), n_frames);
 }
 
 int ygzf_batch_counts(ygzf_ctx *c, int *n_kp) {
     if (!c || !n_kp) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    HIPCHECK(c, hipMemcpyAsync(n_kp, (int *) c->dOutCnt.p + 1, sizeof(int) * c->lastFrames, hipMemcpyDeviceToHost, c->stream));
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    HIPCHECK(c, hipMemcpyAsync(n_kp, (int *) c->dOutCnt.p + 1, sizeof(int) * c->held.frames, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
 
 int ygzf_batch_fetch(ygzf_ctx *c, int frame, ygzf_kp *kps, uint8_t *desc, int cap, int *n_out) {
     if (!c || !n_out) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    if (frame < 0 || frame >= c->lastFrames) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    if (frame < 0 || frame >= c->held.frames) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
     int n = 0;
     HIPCHECK(c, hipMemcpyAsync(&n, (int *) c->dOutCnt.p + frame + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -1402,9 +1317,9 @@ int ygzf_batch_fetch(ygzf_ctx *c, int frame, ygzf_kp *kps, uint8_t *desc, int ca
 
 int ygzf_batch_fetch_all(ygzf_ctx *c, ygzf_kp *kps, uint8_t *desc, int *n_kp, int stride) {
     if (!c || !kps || !desc || !n_kp) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
     if (stride < c->geo.kpStride) return fail(c, YGZF_ERR_INVALID, "stride %d < %d (ygzf_max_keypoints)", stride, c->geo.kpStride);
-    const int B = c->lastFrames, ks = c->geo.kpStride;
+    const int B = c->held.frames, ks = c->geo.kpStride;
     HIPCHECK(c, hipMemcpyAsync(n_kp, (int *) c->dOutCnt.p + 1, sizeof(int) * B, hipMemcpyDeviceToHost, c->stream));
     // slot f + 1 holds frame f; rows of `stride` keypoints on the host side, kpStride on the device side
     HIPCHECK(c, hipMemcpy2DAsync(kps, sizeof(ygzf_kp) * (size_t) stride, (ygzf_kp *) c->dOutKp.p + ks, sizeof(ygzf_kp) * (size_t) ks,
@@ -1417,8 +1332,8 @@ int ygzf_batch_fetch_all(ygzf_ctx *c, ygzf_kp *kps, uint8_t *desc, int *n_kp, in
 
 // queues the gather kernel and the ONE copy of ygzf_batch_fetch_packed on the context's stream; the caller synchronises
 int queue_packed_fetch(ygzf_ctx *c, void *host, size_t host_bytes, size_t *off_kps, size_t *off_desc, int *row_entries, size_t *bytes_out) {
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    const size_t B = (size_t) c->lastFrames, ks = (size_t) c->geo.kpStride;
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    const size_t B = (size_t) c->held.frames, ks = (size_t) c->geo.kpStride;
     const size_t oK = (B * sizeof(int) + 255) & ~(size_t) 255, oD = oK + ((B * ks * sizeof(ygzf_kp) + 255) & ~(size_t) 255), total = oD + B * ks * 32;
     if (total > host_bytes) return fail(c, YGZF_ERR_INVALID, "packed results need %zu bytes, %zu given", total, host_bytes);
     if (total >= (1ull << 32)) return fail(c, YGZF_ERR_UNSUPPORTED, "packed results of %zu bytes: use ygzf_batch_fetch_all", total);
@@ -1470,8 +1385,8 @@ int ygzf_stereo_pair_host(ygzf_ctx *l, ygzf_ctx *r, const uint8_t *left, const u
     if ((rc = apply_geometry(r, w, h, 1))) { l->err = r->err; return rc; }
     if (!l->evShare) HIPCHECK(l, hipEventCreateWithFlags(&l->evShare, hipEventDisableTiming));
     if (!r->evShare) HIPCHECK(l, hipEventCreateWithFlags(&r->evShare, hipEventDisableTiming));
-    carry_early(l);
-    carry_early(r);
+    queue_carry(l, true);
+    queue_carry(r, true);
     FrameSet fl, fr;
     if ((rc = upload_frames(l, left, 1, w, h, row_pitch, 0, &fl))) return rc;
     HIPCHECK(l, hipEventRecord(l->evShare, l->stream));                 // the left eye is on the device ...
@@ -1536,31 +1451,23 @@ int ygzf_extract(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, ygzf
 int ygzf_extract_resident(ygzf_ctx *c, ygzf_kp *kps, uint8_t *desc, int cap, int *n_out) {
     if (!c || !n_out) return fail(c, YGZF_ERR_INVALID, "null argument");
     *n_out = 0;
-    if (!c->pyrResident) return fail(c, YGZF_ERR_STATE, "no resident pyramid (ygzf_compute_pyramid must be the context's previous image operation)");
+    if (!pyramid_resident(c)) return fail(c, YGZF_ERR_STATE, "no resident pyramid (ygzf_compute_pyramid must be the context's previous image operation)");
     HIPCHECK(c, hipSetDevice(c->device));
-    const int w = c->pyrResW, h = c->pyrResH;
+    const int w = c->held.w, h = c->held.h;
     int rc = apply_geometry(c, w, h, 1);   // same geometry as the compute_pyramid call: no reallocation
     if (rc) return rc;
-    FrameSet fs;
-    fs.img0 = (const uint8_t *) c->dImg0.p;
-    fs.img0_pitch = align_up(w, 64);
-    fs.img0_stride = (long long) fs.img0_pitch * h;
-    fs.pyr = (uint8_t *) c->dPyr.p;
-    fs.pyr_stride = c->geo.pyrBytes;
-    if (c->aheadPending) {   // queued by ygzf_compute_pyramid (ygzf_set_extract_ahead): nothing to launch
-        c->aheadPending = false;
-        c->pyrResident = false;
-    } else if ((rc = run_extract(c, fs, 1, true))) return rc;
+    if (c->held.image == Held::PyramidAhead) pyramid_taken(c);   // queued by ygzf_compute_pyramid (ygzf_set_extract_ahead): nothing to launch
+    else if ((rc = run_extract(c, own_frames(c, w, h), 1, true))) return rc;
     return fetch_frame0_packed(c, kps, desc, cap, n_out);
 }
 
 int ygzf_batch_fetch_level(ygzf_ctx *c, int frame, int level, uint8_t *out) {
     if (!c || !out) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    if (frame < 0 || frame >= c->lastFrames || level < 0 || level >= c->tab.cfg.nlevels) return fail(c, YGZF_ERR_INVALID, "bad frame/level");
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    if (frame < 0 || frame >= c->held.frames || level < 0 || level >= c->tab.cfg.nlevels) return fail(c, YGZF_ERR_INVALID, "bad frame/level");
     int pitch;
     const LevelGeom &g = c->geo.lv[level];
-    const uint8_t *p = level_ptr(c->lastFs, g, level, frame, &pitch);
+    const uint8_t *p = level_ptr(c->held.fs, g, level, frame, &pitch);
     // packed on the device, then one linear copy (a pitched copy of an odd-width level is executed row by row)
     const size_t bytes = (size_t) g.w * g.h;
     int rc = ensure(c, c->dTmpC, bytes + 64);
@@ -1574,8 +1481,8 @@ int ygzf_batch_fetch_level(ygzf_ctx *c, int frame, int level, uint8_t *out) {
 
 int ygzf_batch_fetch_candidates(ygzf_ctx *c, int frame, int level, int *xs, int *ys, int *scores, int cap, int *n_out) {
     if (!c || !n_out) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    if (frame < 0 || frame >= c->lastFrames || level < 0 || level >= c->tab.cfg.nlevels) return fail(c, YGZF_ERR_INVALID, "bad frame/level");
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    if (frame < 0 || frame >= c->held.frames || level < 0 || level >= c->tab.cfg.nlevels) return fail(c, YGZF_ERR_INVALID, "bad frame/level");
     const Geometry &G = c->geo;
     const LevelGeom &g = G.lv[level];
     const int nc = g.nCols * g.nRows;
@@ -1606,9 +1513,9 @@ int ygzf_batch_fetch_candidates(ygzf_ctx *c, int frame, int level, int *xs, int 
 
 int ygzf_batch_fetch_level_keypoints(ygzf_ctx *c, int frame, int level, int *xs, int *ys, int *scores, int cap, int *n_out) {
     if (!c || !n_out) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
     const int L = c->tab.cfg.nlevels;
-    if (frame < 0 || frame >= c->lastFrames || level < 0 || level >= L) return fail(c, YGZF_ERR_INVALID, "bad frame/level");
+    if (frame < 0 || frame >= c->held.frames || level < 0 || level >= L) return fail(c, YGZF_ERR_INVALID, "bad frame/level");
     const Geometry &G = c->geo;
     const LevelGeom &g = G.lv[level];
     int n = 0;

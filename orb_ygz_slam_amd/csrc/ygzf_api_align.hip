@@ -230,7 +230,7 @@ int ygzf_image_cache_put_resident(ygzf_ctx *c, int slot, ygzf_ctx *src) {
     if (c->cacheSlots <= 0) return fail(c, YGZF_ERR_STATE, "image cache not reserved");
     if (slot < 0 || slot >= c->cacheSlots) return fail(c, YGZF_ERR_INVALID, "slot %d outside 0..%d", slot, c->cacheSlots - 1);
     if (src == c || src->device != c->device) return fail(c, YGZF_ERR_INVALID, "the source must be another context on the same device");
-    if (!src->pyrHeld || src->pyrHeldW != c->cacheW || src->pyrHeldH != c->cacheH || src->geo.w != c->cacheW || src->geo.h != c->cacheH)
+    if (!holds_image(src, c->cacheW, c->cacheH) || src->geo.w != c->cacheW || src->geo.h != c->cacheH)
         return fail(c, YGZF_ERR_STATE, "the source context holds no %dx%d image with its pyramid", c->cacheW, c->cacheH);
     HIPCHECK(c, hipSetDevice(c->device));
     int rc = apply_geometry(c, c->cacheW, c->cacheH, 1);
@@ -244,7 +244,7 @@ int ygzf_image_cache_put_resident(ygzf_ctx *c, int slot, ygzf_ctx *src) {
     const size_t imgBytes = (size_t) c->cachePitch * c->cacheH;   // both sides: pitch = width rounded up to 64
     if (!c->evShare) HIPCHECK(c, hipEventCreateWithFlags(&c->evShare, hipEventDisableTiming));
     // order: the source's pending work (its pyramid kernels) -> the copies on this context's stream -> the source's later work
-    if (src->evPyrDoneValid) HIPCHECK(c, hipStreamWaitEvent(c->stream, src->evPyrDone, 0));   // (not the end of its stream: see mark_pyramid_done)
+    if (src->evPyrDone) HIPCHECK(c, hipStreamWaitEvent(c->stream, src->evPyrDone, 0));   // (not the end of its stream: see mark_pyramid_done)
     else {
         HIPCHECK(c, hipEventRecord(c->evShare, src->stream));
         HIPCHECK(c, hipStreamWaitEvent(c->stream, c->evShare, 0));
@@ -259,7 +259,7 @@ int ygzf_image_cache_put_resident(ygzf_ctx *c, int slot, ygzf_ctx *src) {
 }
 
 int ygzf_has_resident_image(const ygzf_ctx *c, int w, int h) {
-    return c && c->pyrHeld && c->pyrHeldW == w && c->pyrHeldH == h ? 1 : 0;
+    return c && holds_image(c, w, h) ? 1 : 0;
 }
 
 int ygzf_find_direct_projection_batch(ygzf_ctx *c, const ygzf_camera *cam, int cur_slot, const float *cur_Tcw7, int n, const int *ref_slot,
@@ -329,17 +329,16 @@ int ygzf_find_direct_projection_batch(ygzf_ctx *c, const ygzf_camera *cam, int c
 // ---- SparseImgAlign over a resident batch ---------------------------------------------------------------------------------
 int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, int min_level, int n_iter) {
     if (!c || !cam) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    if (c->slot0Stale) return fail(c, YGZF_ERR_STATE, "the previous frame was not carried (ygzf_set_carry_previous is off)");
+    int rc = need_carried_batch(c);
+    if (rc) return rc;
     const int L = c->tab.cfg.nlevels;
     if (min_level < 1 || max_level < min_level || max_level >= L)
         return fail(c, YGZF_ERR_INVALID, "level range [%d,%d] (the resident form aligns on pyramid levels >= 1, as Tracking does)", min_level, max_level);
     HIPCHECK(c, hipSetDevice(c->device));
     const Geometry &G = c->geo;
-    const int B = c->lastFrames;
+    const int B = c->held.frames;
     if (G.kpStride == 0) return fail(c, YGZF_ERR_STATE, "configuration yields no keypoints");
     c->alignCarry = true;
-    int rc;
     ygzf_ctx::Buf *S = c->dAl;   // 0 level tables, 1 poses, 2 caches, 3 out, (world = dWorld)
     if ((rc = ensure(c, c->dWorld, (size_t) (B + 1) * G.kpStride * 3 * sizeof(float))) ||
         (rc = ensure(c, S[0], (size_t) B * 2 * kMaxLevels * sizeof(SiaLevel))) || (rc = ensure(c, S[1], (size_t) B * 14 * sizeof(float))) ||
@@ -352,7 +351,7 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
     {
         const void *parts[] = {c->dPyr.p, c->dCarryPyr.p, S[0].p, S[1].p};
         key.insert(key.end(), (const unsigned char *) parts, (const unsigned char *) parts + sizeof parts);
-        const int ints[] = {B, G.w, G.h, c->carryPyrValid ? 1 : 0};
+        const int ints[] = {B, G.w, G.h, c->held.carryPyr ? 1 : 0};
         key.insert(key.end(), (const unsigned char *) ints, (const unsigned char *) ints + sizeof ints);
     }
     if (key != c->alKey) {
@@ -405,8 +404,8 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
         A.visible = A.levelFlags + nLv * slots;
     }
     A.out = (float *) S[3].p;
-    const int first = c->carryPyrValid ? 0 : 1;   // without a carried pyramid frame 0 has no reference image
-    if (!c->carryPyrValid) HIPCHECK(c, hipMemsetAsync(S[3].p, 0, 48 * sizeof(float), c->stream));
+    const int first = c->held.carryPyr ? 0 : 1;   // without a carried pyramid frame 0 has no reference image
+    if (!c->held.carryPyr) HIPCHECK(c, hipMemsetAsync(S[3].p, 0, 48 * sizeof(float), c->stream));
     if (B - first > 0) {
         SiaArgs A2 = A;
         A2.keys += (size_t) first * G.kpStride;
@@ -445,14 +444,14 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
         launch_sia(c->stream, A2, B - first, sl);
     }
     HIPCHECK(c, hipGetLastError());
-    c->lastAlignPairs = B;
+    set_align_pairs(c, B);
     return YGZF_OK;
 }
 
 int ygzf_align_fetch(ygzf_ctx *c, int frame, float *TCR_out, size_t *ret, float *info) {
     if (!c || !TCR_out || !ret) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastAlignPairs < 1) return fail(c, YGZF_ERR_STATE, "no aligned batch");
-    if (frame < 0 || frame >= c->lastAlignPairs) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
+    if (c->held.alignPairs < 1) return fail(c, YGZF_ERR_STATE, "no aligned batch");
+    if (frame < 0 || frame >= c->held.alignPairs) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
     float out[48];
     HIPCHECK(c, hipMemcpyAsync(out, (float *) c->dAl[3].p + (size_t) frame * 48, sizeof out, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));

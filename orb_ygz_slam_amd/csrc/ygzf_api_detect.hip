@@ -66,8 +66,8 @@ static int key_level_position(ygzf_ctx *c, const ygzf_kp &k, int i, int *px, int
 
 int ygzf_describe_keys(ygzf_ctx *c, int frame, const ygzf_kp *keys, int n, int recompute_angle, float *angles_out, uint8_t *desc) {
     if (!c || (n > 0 && (!keys || !desc))) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    if (frame < 0 || frame >= c->lastFrames) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    if (frame < 0 || frame >= c->held.frames) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
     if (n <= 0) return YGZF_OK;
     HIPCHECK(c, hipSetDevice(c->device));
     std::vector<int> list4((size_t) 4 * n);
@@ -85,7 +85,7 @@ int ygzf_describe_keys(ygzf_ctx *c, int frame, const ygzf_kp *keys, int n, int r
     HIPCHECK(c, hipMemcpyAsync(c->dDso[5].p, list4.data(), 16 * (size_t) n, hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, KK_DESCRIBE);
-        launch_describe_list(c->stream, c->lastFs, (const LevelGeom *) c->dGeom.p, c->dDso[5].p, n, frame, (float *) c->dDso[7].p, (uint8_t *) c->dTmpC.p, c->tab.cfg.cv_mode);
+        launch_describe_list(c->stream, c->held.fs, (const LevelGeom *) c->dGeom.p, c->dDso[5].p, n, frame, (float *) c->dDso[7].p, (uint8_t *) c->dTmpC.p, c->tab.cfg.cv_mode);
     }
     HIPCHECK(c, hipGetLastError());
     if (angles_out) HIPCHECK(c, hipMemcpyAsync(angles_out, c->dDso[7].p, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
@@ -112,8 +112,7 @@ int ygzf_extract_dso(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, 
         ProfScope ps(c, KK_PYR);
         launch_pyr_resize(c->stream, fs, dGeom, G.lv[l], l, 1, pyr_tabs(c));
     }
-    c->lastFrames = 0;
-    c->carryValid = false;
+    forget_outputs(c);
     // existing keys: occupancy at cvRound(pt) on level 0 (:1286-1291), describe position cvRound(pt * invScale[octave]) (:1104-1112, :1380-1383)
     std::vector<unsigned> occXY(n_existing);
     std::vector<int> list4((size_t) 4 * n_existing);
@@ -223,8 +222,7 @@ static int grid_extract_begin(ygzf_ctx *c, const uint8_t *img, int w, int h, int
         ProfScope ps(c, KK_PYR);
         launch_pyr_resize(c->stream, *fs, dGeom, G.lv[l], l, 1, pyr_tabs(c));
     }
-    c->lastFrames = 0;
-    c->carryValid = false;
+    forget_outputs(c);
     list4->assign((size_t) 4 * n_existing, 0);
     for (int i = 0; i < n_existing; i++) {
         int px, py;

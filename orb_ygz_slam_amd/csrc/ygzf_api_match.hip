@@ -68,13 +68,12 @@ static int plan_match_lds(ygzf_ctx *c, MatchArgs &A, int nPairs, size_t *ldsByte
 
 int ygzf_match_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, float th, int b_mono, int check_level, int check_orientation) {
     if (!c || !cam) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastFrames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
-    if (c->slot0Stale) return fail(c, YGZF_ERR_STATE, "the previous frame was not carried (ygzf_set_carry_previous is off)");
+    int rc = need_carried_batch(c);
+    if (rc) return rc;
     HIPCHECK(c, hipSetDevice(c->device));
     const Geometry &G = c->geo;
-    const int B = c->lastFrames;
+    const int B = c->held.frames;
     if (G.kpStride == 0) return fail(c, YGZF_ERR_STATE, "configuration yields no keypoints");
-    int rc;
     if ((rc = ensure(c, c->dWorld, (size_t) (B + 1) * G.kpStride * 3 * sizeof(float))) ||
         (rc = ensure(c, c->dOwner, (size_t) B * G.kpStride)) || (rc = ensure(c, c->dMatch, (size_t) B * G.kpStride * sizeof(int))) ||
         (rc = ensure(c, c->dNMatch, (size_t) B * sizeof(int))) || (rc = ensure(c, c->dPoses, (size_t) B * 24 * sizeof(float))))
@@ -143,7 +142,7 @@ int ygzf_match_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, float th, int b_m
         fprintf(stderr, "[ygzf match pair %d, 100MHz ticks] grid %lld  proj %lld  spec %lld  seq %lld  tail %lld  rescans %lld of %lld queries\n", pp,
                 st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6], st[7]);
     }
-    c->lastMatchPairs = B;
+    set_match_pairs(c, B);
     return YGZF_OK;
 }
 
@@ -159,16 +158,16 @@ int ygzf_match_fallbacks(ygzf_ctx *c, unsigned *pairs) {
 
 int ygzf_match_counts(ygzf_ctx *c, int *nmatches) {
     if (!c || !nmatches) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastMatchPairs < 1) return fail(c, YGZF_ERR_STATE, "no matched batch");
-    HIPCHECK(c, hipMemcpyAsync(nmatches, c->dNMatch.p, sizeof(int) * c->lastMatchPairs, hipMemcpyDeviceToHost, c->stream));
+    if (c->held.matchPairs < 1) return fail(c, YGZF_ERR_STATE, "no matched batch");
+    HIPCHECK(c, hipMemcpyAsync(nmatches, c->dNMatch.p, sizeof(int) * c->held.matchPairs, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
 
 int ygzf_match_fetch(ygzf_ctx *c, int frame, int *cur_match, uint8_t *cur_owner, int cap) {
     if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastMatchPairs < 1) return fail(c, YGZF_ERR_STATE, "no matched batch");
-    if (frame < 0 || frame >= c->lastMatchPairs) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
+    if (c->held.matchPairs < 1) return fail(c, YGZF_ERR_STATE, "no matched batch");
+    if (frame < 0 || frame >= c->held.matchPairs) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
     int n = 0;
     HIPCHECK(c, hipMemcpyAsync(&n, (int *) c->dOutCnt.p + frame + 1, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -182,8 +181,8 @@ int ygzf_match_fetch(ygzf_ctx *c, int frame, int *cur_match, uint8_t *cur_owner,
 
 int ygzf_match_fetch_all(ygzf_ctx *c, int *match, int stride) {
     if (!c || !match) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastMatchPairs < 1) return fail(c, YGZF_ERR_STATE, "no matched batch");
-    const int B = c->lastMatchPairs, ks = c->geo.kpStride;
+    if (c->held.matchPairs < 1) return fail(c, YGZF_ERR_STATE, "no matched batch");
+    const int B = c->held.matchPairs, ks = c->geo.kpStride;
     if (stride < ks) return fail(c, YGZF_ERR_INVALID, "stride %d < %d (ygzf_max_keypoints)", stride, ks);
     HIPCHECK(c, hipMemcpy2DAsync(match, sizeof(int) * (size_t) stride, c->dMatch.p, sizeof(int) * (size_t) ks, sizeof(int) * (size_t) ks, B,
                                  hipMemcpyDeviceToHost, c->stream));
@@ -276,7 +275,7 @@ int ygzf_search_by_projection_last(ygzf_ctx *c, const ygzf_frame_view *cur, cons
         fprintf(stderr, "[ygzf match (cur, last), 100MHz ticks] grid %lld  proj %lld  spec %lld  seq %lld  tail %lld  rescans %lld of %lld queries\n",
                 st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6], st[7]);
     }
-    c->lastMatchPairs = 0;
+    set_match_pairs(c, 0);
     return YGZF_OK;
 }
 
@@ -493,7 +492,7 @@ static int projected_match(ygzf_ctx *c, int mode, const ygzf_frame_view *F, cons
                 st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6], st[7]);
     }
     if ((rc = P.download())) return rc;
-    c->lastMatchPairs = 0;
+    set_match_pairs(c, 0);
     return YGZF_OK;
 }
 
@@ -535,7 +534,7 @@ int ygzf_search_by_bow(ygzf_ctx *c, int n_nodes, const int *kf_off, const int *k
     HIPCHECK(c, hipGetLastError());
     if ((rc = P.download())) return rc;
     *nmatches = tail[0];
-    c->lastMatchPairs = 0;
+    set_match_pairs(c, 0);
     return YGZF_OK;
 }
 
@@ -612,7 +611,7 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
     HIPCHECK(c, hipGetLastError());
     if ((rc = P.download())) return rc;
     *nmatches = tail[0];
-    c->lastMatchPairs = 0;
+    set_match_pairs(c, 0);
     return YGZF_OK;
 }
 

@@ -24,11 +24,11 @@ static void fill_stereo_common(ygzf_ctx *c, StereoArgs &A, float mb, float mbf, 
 
 int ygzf_stereo_batch(ygzf_ctx *c, float mb, float mbf) {
     if (!c) return YGZF_ERR_INVALID;
-    if (c->lastFrames < 2 || (c->lastFrames & 1)) return fail(c, YGZF_ERR_STATE, "stereo needs an extracted batch of (left, right) frame pairs");
+    if (c->held.frames < 2 || (c->held.frames & 1)) return fail(c, YGZF_ERR_STATE, "stereo needs an extracted batch of (left, right) frame pairs");
     if (!(mb > 0)) return fail(c, YGZF_ERR_INVALID, "baseline mb must be positive");
     HIPCHECK(c, hipSetDevice(c->device));
     const Geometry &G = c->geo;
-    const int P = c->lastFrames / 2;
+    const int P = c->held.frames / 2;
     if (G.kpStride > 65535) return fail(c, YGZF_ERR_UNSUPPORTED, "more than 65535 keypoints per frame");
     int rc;
     const size_t per = (size_t) G.kpStride;
@@ -47,7 +47,7 @@ int ygzf_stereo_batch(ygzf_ctx *c, float mb, float mbf) {
     A.cntStride = 2;
     A.cntOffL = 1;
     A.cntOffR = 2;
-    A.fs = c->lastFs;
+    A.fs = c->held.fs;
     A.frame0 = 0;
     A.frameStep = 2;
     fill_stereo_common(c, A, mb, mbf, G.h);
@@ -63,7 +63,7 @@ int ygzf_stereo_batch(ygzf_ctx *c, float mb, float mbf) {
         launch_stereo(c->stream, A, P, G.kpStride, G.kpStride);
     }
     HIPCHECK(c, hipGetLastError());
-    c->lastStereoPairs = P;
+    set_stereo_pairs(c, P);
     return YGZF_OK;
 }
 
@@ -72,7 +72,7 @@ int ygzf_stereo_batch(ygzf_ctx *c, float mb, float mbf) {
 // ComputeStereoMatches of ONE pair whose left eye is frame 0 of context l's last extraction and whose right eye is frame 0 of context r's
 // (ygzf_stereo_pair_host); queued on l's stream, which the caller has made wait for r's extraction.  Results where ygzf_stereo_batch leaves pair 0's.
 int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf) {
-    if (l->lastFrames != 1 || r->lastFrames != 1) return fail(l, YGZF_ERR_STATE, "stereo across contexts needs one extracted frame in each");
+    if (l->held.frames != 1 || r->held.frames != 1) return fail(l, YGZF_ERR_STATE, "stereo across contexts needs one extracted frame in each");
     if (!(mb > 0)) return fail(l, YGZF_ERR_INVALID, "baseline mb must be positive");
     const Geometry &G = l->geo;
     if (G.kpStride != r->geo.kpStride || G.w != r->geo.w || G.h != r->geo.h) return fail(l, YGZF_ERR_STATE, "the two eyes differ in geometry");
@@ -101,8 +101,8 @@ int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf) {
     A.cntStride = 1;
     A.cntOffL = 1;
     A.cntOffR = 1;
-    A.fs = l->lastFs;
-    A.fsR = r->lastFs;                            // the kernels address the right image as frame frame0 + 1: one frame back, so that this is r's frame 0
+    A.fs = l->held.fs;
+    A.fsR = r->held.fs;                            // the kernels address the right image as frame frame0 + 1: one frame back, so that this is r's frame 0
     A.fsR.img0 -= A.fsR.img0_stride;
     A.fsR.pyr -= A.fsR.pyr_stride;
     A.frame0 = 0;
@@ -120,7 +120,7 @@ int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf) {
         launch_stereo(l->stream, A, 1, G.kpStride, G.kpStride);
     }
     HIPCHECK(l, hipGetLastError());
-    l->lastStereoPairs = 1;
+    set_stereo_pairs(l, 1);
     return YGZF_OK;
 }
 
@@ -128,7 +128,7 @@ extern "C" {
 
 int ygzf_stereo_fetch(ygzf_ctx *c, int pair, float *u_right, float *depth, int cap) {
     if (!c || !u_right || !depth) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (pair < 0 || pair >= c->lastStereoPairs) return fail(c, YGZF_ERR_STATE, "pair %d: no stereo result", pair);
+    if (pair < 0 || pair >= c->held.stereoPairs) return fail(c, YGZF_ERR_STATE, "pair %d: no stereo result", pair);
     int n = 0;
     HIPCHECK(c, hipMemcpyAsync(&n, (int *) c->dOutCnt.p + 1 + 2 * pair, sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -144,8 +144,8 @@ int ygzf_stereo_fetch(ygzf_ctx *c, int pair, float *u_right, float *depth, int c
 // every pair of the last ygzf_stereo_batch at once: rows of `stride` floats (>= ygzf_max_keypoints), pair p's first n_kp[2 p] entries valid
 int ygzf_stereo_fetch_all(ygzf_ctx *c, float *u_right, float *depth, int stride) {
     if (!c || !u_right || !depth) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (c->lastStereoPairs < 1) return fail(c, YGZF_ERR_STATE, "no stereo result");
-    const int ks = c->geo.kpStride, P = c->lastStereoPairs;
+    if (c->held.stereoPairs < 1) return fail(c, YGZF_ERR_STATE, "no stereo result");
+    const int ks = c->geo.kpStride, P = c->held.stereoPairs;
     if (stride < ks) return fail(c, YGZF_ERR_INVALID, "stride %d < %d (ygzf_max_keypoints)", stride, ks);
     HIPCHECK(c, hipMemcpy2DAsync(u_right, 4 * (size_t) stride, c->dSt[1].p, 4 * (size_t) ks, 4 * (size_t) ks, P, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipMemcpy2DAsync(depth, 4 * (size_t) stride, c->dSt[2].p, 4 * (size_t) ks, 4 * (size_t) ks, P, hipMemcpyDeviceToHost, c->stream));
@@ -181,8 +181,7 @@ int ygzf_compute_stereo_matches(ygzf_ctx *c, const uint8_t *img_left, const uint
         ProfScope ps(c, KK_PYR);
         launch_pyr_resize(c->stream, fs, (const LevelGeom *) c->dGeom.p, G.lv[l], l, 2, pyr_tabs(c));
     }
-    c->lastFrames = 0;
-    c->carryValid = false;
+    forget_outputs(c);
     const size_t nk = (size_t) n_left + n_right;
     int counts[2] = {n_left, n_right};
     if ((rc = ensure(c, c->dSt[0], sizeof(StereoRec) * (size_t) (n_right + 1))) || (rc = ensure(c, c->dSt[1], 4 * (size_t) n_left)) ||
@@ -229,7 +228,7 @@ int ygzf_compute_stereo_matches(ygzf_ctx *c, const uint8_t *img_left, const uint
     HIPCHECK(c, hipMemcpyAsync(u_right, c->dSt[1].p, 4 * (size_t) n_left, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipMemcpyAsync(depth, c->dSt[2].p, 4 * (size_t) n_left, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
-    c->lastStereoPairs = 0;
+    set_stereo_pairs(c, 0);
     return YGZF_OK;
 }
 

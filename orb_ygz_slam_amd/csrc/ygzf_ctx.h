@@ -53,6 +53,28 @@ struct Geometry {
 
 using namespace ygzf;
 
+// What a context's device buffers hold from one call to the next (include/ygzf.h states the rules; ygzf_set_carry_previous / _extract_ahead
+// and the pyramid carry's switch stay settings of ygzf_ctx).  Invariants:
+//   - frames > 0: output slots 1 .. frames hold the extracted batch `fs` and its levels; 0 after any call that takes the output buffers
+//     for its own inputs, a geometry change or output growth.
+//   - carry: the slot the next extraction copies into slot 0 (0: none, an empty slot), the last batch's last frame: carry == frames while
+//     frames > 0, and it stays when a plain ygzf_compute_pyramid ends the batch (the Frame path's ygzf_extract_resident carries it).
+//   - slot0Stale: the last extraction ran with the carry off, slot 0 does not hold its predecessor (the batch matchers refuse).
+//   - carryQueued: k_carry_slot is already queued for the extraction being set up (ahead of its upload); false between calls.
+//   - carryPyr: dCarryPyr holds the pyramid of the frame in slot 0 (pair 0's reference in ygzf_align_batch_prev).
+//   - matchPairs / alignPairs / stereoPairs: results of the last ygzf_match_batch_prev / _align_batch_prev / _stereo_batch still valid.
+//   - image: dImg0 / dPyr frame 0 hold one w x h image with its complete pyramid (Extracted and up); Pyramid: ygzf_compute_pyramid was the
+//     previous image operation (ygzf_extract_resident's input); PyramidAhead: and it already queued the extraction (ygzf_set_extract_ahead).
+struct Held {
+    int frames = 0;
+    FrameSet fs{};
+    int carry = 0;
+    bool slot0Stale = false, carryQueued = false, carryPyr = false;
+    int matchPairs = 0, alignPairs = 0, stereoPairs = 0;
+    enum Image { None, Extracted, Pyramid, PyramidAhead } image = None;
+    int w = 0, h = 0;
+};
+
 struct ygzf_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -72,16 +94,8 @@ struct ygzf_ctx {
     int cacheSlots = 0, cacheW = 0, cacheH = 0, cachePitch = 0;
     long long cachePyrBytes = 0;
     std::vector<unsigned char> cacheFilled;
-    int lastStereoPairs = 0;
     bool alignCarry = false;      // keep the last frame's pyramid across batches (enabled by the first ygzf_align_batch_prev)
-    bool carryPyrValid = false;
-    int lastAlignPairs = 0;
     std::vector<unsigned char> alKey;   // cache key of the uploaded SiaLevel tables
-    bool carryValid = false;
-    // the output slot that holds the last frame an extraction produced (0: none), which the next extraction carries into slot 0.  Not lastFrames:
-    // ygzf_compute_pyramid ends the batch (its pyramid replaces frame 0's) but leaves the keypoints -- the Frame path's ygzf_extract_resident carries them
-    int carrySlot = 0;
-    int lastMatchPairs = 0;
     int identityPoses = 0;
     void *identityPosesPtr = nullptr;
     size_t octLds = 0;
@@ -92,8 +106,7 @@ struct ygzf_ctx {
     std::vector<OctGroup> octGroups;
     OctGroup octSmall;                     // all levels in ONE histogram-plan launch: launches of a few frames (see run_extract)
     bool haveOctSmall = false;
-    bool carryOff = false;     // ygzf_set_carry_previous(0): extractions do not carry the previous batch's last frame into slot 0 ...
-    bool slot0Stale = false;   // ... and slot 0 no longer holds it: the batch matchers refuse until an extraction has carried again
+    bool carryOff = false;     // ygzf_set_carry_previous(0): extractions do not carry the previous batch's last frame into slot 0
     struct OctHistLayout {     // what dOctHist's hand-over counters were last cleared for (k_octree's helper workgroups)
         int frames = 0, helpers = 0, histBins = 0;
         size_t bytes = 0;      // the allocation: ensure() reallocates only to a larger size
@@ -118,14 +131,9 @@ struct ygzf_ctx {
     Buf dFastCtr;                          // eight draw counters of k_fast_tab_persist (one per XCD), zeroed before every launch
     int cuCount = 256;
     Buf dResPack;                          // [counts | keypoint rows | descriptor rows] of a small launch, contiguous (ygzf_batch_fetch_packed)
-    bool carryLaunched = false;            // k_carry_slot already queued for the extraction being set up (ahead of its upload)
     Buf dUpStage;                          // linear landing area of uploads that are re-pitched on the device (upload_rows)
-    bool pyrHeld = false;                  // dImg0 / dPyr frame 0 hold ONE image (pyrHeldW x pyrHeldH) and its complete pyramid (ygzf_image_cache_put_resident)
-    int pyrHeldW = 0, pyrHeldH = 0;
-    hipEvent_t evShare = nullptr, evPyrDone = nullptr;
-    bool evPyrDoneValid = false;
-    bool pyrResident = false;              // dImg0 / dPyr frame 0 hold the image and pyramid of the last ygzf_compute_pyramid (pyrResW x pyrResH)
-    int pyrResW = 0, pyrResH = 0;
+    hipEvent_t evShare = nullptr;
+    hipEvent_t evPyrDone = nullptr;        // recorded by mark_pyramid_done, which creates it (null: no pyramid computed yet)
     // one-frame uploads from pageable caller memory (a cv::Mat): the rows are copied into this page-locked, device-visible buffer by the host and
     // read from there by a kernel that writes them at the context's pitch -- the runtime's own pageable path (pin / stage / blit) cost ~50 us for a
     // 752x480 frame, this ~25.  evIn marks the moment the kernel has read the buffer (the next upload waits for it before overwriting).
@@ -137,9 +145,7 @@ struct ygzf_ctx {
     uint8_t *hStage = nullptr;             // page-locked staging for results that go back to pageable caller memory in many small pieces
     size_t hStageBytes = 0;
     void *hStageDev = nullptr;             // the same memory as the device addresses it (kernels write small results straight into it)
-    // batch state
-    int lastFrames = 0;
-    FrameSet lastFs{};
+    Held held;                             // what the buffers hold between calls (the transitions below ygzf_ctx are its only writers)
     int img0Pitch = 0;
     // timing
     hipEvent_t tStart = nullptr, tStop = nullptr;
@@ -149,7 +155,7 @@ struct ygzf_ctx {
     int pyrStripFrames = (int) forced("pyr_strip_frames", 16);   // k_pyr_strips up to this many frames per launch (0: never)
     PyrChainGraph pyrGraph = {};
     const void *pyrGraphKey[6] = {nullptr};   // geometry tables + size the graph was built for
-    bool extractAhead = false, aheadPending = false;
+    bool extractAhead = false;
     hipStream_t streamCopy = nullptr;
     hipEvent_t evPyramid = nullptr;
     bool profile = false;
@@ -204,10 +210,9 @@ static int fail(ygzf_ctx *c, int code, const char *fmt, ...) {
                                           __FILE__, __LINE__);                                                    \
     } while (0)
 
+// a buffer that grows loses its contents (the caller forgets what it held: apply_geometry, upload_frames)
 static int ensure(ygzf_ctx *c, ygzf_ctx::Buf &b, size_t bytes) {
     if (bytes <= b.bytes) return YGZF_OK;
-    // a buffer that grows loses its contents: whatever ygzf_compute_pyramid left in the image / pyramid buffers is gone with them
-    if (&b == &c->dImg0 || &b == &c->dPyr) { c->pyrResident = false; c->pyrHeld = false; }
     if (b.p) HIPCHECK(c, hipFree(b.p));
     b.p = nullptr;
     b.bytes = 0;
@@ -217,6 +222,91 @@ static int ensure(ygzf_ctx *c, ygzf_ctx::Buf &b, size_t bytes) {
 }
 
 static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
+
+// ---- the transitions of ygzf_ctx::held (its only writers) ----------------------------------------------------------------------------
+static void forget_outputs(ygzf_ctx *c) { c->held.frames = 0; c->held.carry = 0; }
+static void forget_image(ygzf_ctx *c) { c->held.image = Held::None; }
+// the resident pyramid is taken (an extraction runs on dPyr, or collects what compute_pyramid queued): the image stays, ygzf_extract_resident's input is gone
+static void pyramid_taken(ygzf_ctx *c) { if (c->held.image > Held::Extracted) c->held.image = Held::Extracted; }
+// ygzf_set_extract_ahead(0): a queued extraction is not collected -- ygzf_extract_resident extracts the pyramid again, without a carried pyramid
+static void ahead_dropped(ygzf_ctx *c) {
+    if (c->held.image != Held::PyramidAhead) return;
+    c->held.image = Held::Pyramid;
+    c->held.carryPyr = false;
+}
+static void set_match_pairs(ygzf_ctx *c, int n) { c->held.matchPairs = n; }
+static void set_align_pairs(ygzf_ctx *c, int n) { c->held.alignPairs = n; }
+static void set_stereo_pairs(ygzf_ctx *c, int n) { c->held.stereoPairs = n; }
+
+// Slot 0 of the outputs <- the carried frame (k_carry_slot; an empty slot when there is none), once per extraction.  early: queued ahead of the
+// host frames' upload by the entry point (it depends on nothing the upload brings: it runs while they cross the link -- 6 us of a one-frame
+// call); run_extract's own call then queues nothing.
+static void queue_carry(ygzf_ctx *c, bool early) {
+    Held &s = c->held;
+    if (!s.carryQueued) {
+        s.slot0Stale = c->carryOff;
+        const int ks = c->geo.kpStride;
+        if (!c->carryOff) launch_carry_slot(c->stream, (ygzf_kp *) c->dOutKp.p, (uint8_t *) c->dOutDesc.p, (int *) c->dOutCnt.p, ks > 0 ? s.carry : 0, ks);
+    }
+    s.carryQueued = early;
+}
+
+// dCarryPyr <- the pyramid of the frame the next extraction carries (pair 0's reference in ygzf_align_batch_prev), before dPyr is overwritten
+static int save_carry_pyramid(ygzf_ctx *c) {
+    const Geometry &G = c->geo;
+    if (!c->alignCarry || c->carryOff || G.pyrBytes <= 0) return YGZF_OK;
+    int rc = ensure(c, c->dCarryPyr, (size_t) G.pyrBytes + 256);
+    if (rc) return rc;
+    Held &s = c->held;
+    s.carryPyr = s.carry > 0 && s.frames > 0;
+    if (s.carryPyr)
+        HIPCHECK(c, hipMemcpyAsync(c->dCarryPyr.p, (uint8_t *) c->dPyr.p + (size_t) (s.carry - 1) * G.pyrBytes, (size_t) G.pyrBytes, hipMemcpyDeviceToDevice, c->stream));
+    return YGZF_OK;
+}
+
+// the end of run_extract: the outputs hold the batch fs; the image buffers hold its frame 0 when fs lies in them
+static void extracted(ygzf_ctx *c, const FrameSet &fs, int nFrames) {
+    Held &s = c->held;
+    s.frames = s.carry = nFrames;
+    s.fs = fs;
+    s.matchPairs = s.alignPairs = s.stereoPairs = 0;
+    s.image = fs.img0 == (const uint8_t *) c->dImg0.p && fs.pyr == (uint8_t *) c->dPyr.p ? Held::Extracted : Held::None;
+    s.w = c->geo.w;
+    s.h = c->geo.h;
+}
+
+// the end of ygzf_compute_pyramid: a w x h image and its pyramid in the buffers.  Ahead: its extraction is queued (and is the batch);
+// plain: the batch ends, and the carried pyramid with it -- the carried frame's keypoints stay
+static void pyramid_computed(ygzf_ctx *c, int w, int h, bool ahead) {
+    Held &s = c->held;
+    if (!ahead) {
+        s.frames = 0;
+        s.carryPyr = false;
+    }
+    s.image = ahead ? Held::PyramidAhead : Held::Pyramid;
+    s.w = w;
+    s.h = h;
+}
+
+// ---- readers whose check is a rule ----
+static bool holds_image(const ygzf_ctx *c, int w, int h) { return c->held.image != Held::None && c->held.w == w && c->held.h == h; }
+static bool pyramid_resident(const ygzf_ctx *c) { return c->held.image >= Held::Pyramid; }
+// ygzf_match_batch_prev / ygzf_align_batch_prev: pair 0 is (slot 0, frame 0)
+static int need_carried_batch(ygzf_ctx *c) {
+    if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
+    if (c->held.slot0Stale) return fail(c, YGZF_ERR_STATE, "the previous frame was not carried (ygzf_set_carry_previous is off)");
+    return YGZF_OK;
+}
+// the FrameSet of the context's own buffers (frames of w x h at the context's pitch)
+static FrameSet own_frames(const ygzf_ctx *c, int w, int h) {
+    FrameSet fs;
+    fs.img0_pitch = align_up(w, 64);
+    fs.img0 = (const uint8_t *) c->dImg0.p;
+    fs.img0_stride = (long long) fs.img0_pitch * h;
+    fs.pyr = (uint8_t *) c->dPyr.p;
+    fs.pyr_stride = c->geo.pyrBytes;
+    return fs;
+}
 
 static int ensure_stage(ygzf_ctx *c, size_t bytes) {
     if (bytes <= c->hStageBytes) return YGZF_OK;
@@ -345,7 +435,7 @@ YGZF_HIDDEN int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames);
 YGZF_HIDDEN int pyramid_chain(ygzf_ctx *c, const ygzf::FrameSet &fs, int nFrames);
 YGZF_HIDDEN int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf);   // ygzf_api_stereo.hip
 YGZF_HIDDEN int mark_pyramid_done(ygzf_ctx *c);
-YGZF_HIDDEN int run_extract(ygzf_ctx *c, const ygzf::FrameSet &fs, int nFrames, bool pyramidReady = false, bool pyramidCarried = false);
+YGZF_HIDDEN int run_extract(ygzf_ctx *c, const ygzf::FrameSet &fs, int nFrames, bool pyramidReady = false);
 YGZF_HIDDEN int upload_rows(ygzf_ctx *c, void *dst, size_t dstPitch, const uint8_t *src, size_t srcPitch, int w, size_t rows);
 YGZF_HIDDEN int upload_frames(ygzf_ctx *c, const uint8_t *imgs, int nFrames, int w, int h, int row_pitch, size_t frame_stride, ygzf::FrameSet *fs);
 #endif

@@ -46,12 +46,17 @@ class _Oracle:
         self.O, self.cam = oracle, EUROC
         self.oex = oracle.Extractor(NF, 1.2, NL, 20, 7)
         self.sf = self.oex.tables()["scale"]
-        self.kd, self.mt = {}, {}
+        self.kd, self.mt, self.pyr = {}, {}, {}
 
     def extract(self, key, img):
         if key not in self.kd:
             self.kd[key] = self.oex.extract(img)
         return self.kd[key]
+
+    def pyramid(self, key, img):
+        if key not in self.pyr:
+            self.pyr[key] = self.oex.pyramid(img)
+        return self.pyr[key]
 
     def match(self, cur, last, w, h):
         if (cur, last) not in self.mt:
@@ -173,15 +178,15 @@ def test_image_size_switches_on_one_context(orc):
     ex.close()
 
 
-def test_entry_points_interleaved(orc):
-    """ygzf_extract (one frame), ygzf_extract_batch_host and ygzf_compute_pyramid + ygzf_extract_resident on one 1920x1080 context: after each,
-    pair 0 of ygzf_match_batch_prev pairs the first frame with the last frame the context extracted -- whichever entry point extracted it."""
-    from orb_ygz_slam_amd import Extractor
+def _interleaved(orc, ahead=False):
+    from orb_ygz_slam_amd import Extractor, make_camera, EUROC
     imgs = _images(W, H)
     with _env():
         ex = Extractor(NF, 1.2, NL, 20, 7, max_width=W, max_height=H, max_batch=20)
+    ex.set_extract_ahead(ahead)
     key = lambda i: (W, H, i)
     last = None
+    aligned = 0
 
     def one(i):
         k, d = ex.extract(imgs[i])
@@ -194,17 +199,142 @@ def test_entry_points_interleaved(orc):
         ok, od = orc.extract(key(i), imgs[i])
         assert len(k) == len(ok) and (k == ok).all() and (d == od).all()
 
+    def align_pair0(i, step):
+        """pair 0 of ygzf_align_batch_prev: the carried frame `last` (keys at unit depth, its pyramid) against frame i -- extract-ahead saved the
+        carried pyramid before frame i's overwrote it.  The first call only switches the pyramid carry on: no reference image yet."""
+        nonlocal aligned
+        ex.align_batch_prev(make_camera(W, H), NL - 1, 1, 10)
+        ret, T, _ = ex.align_fetch(0)
+        if not aligned:
+            assert ret == 0, (step, ret)
+        else:
+            pk, _ = orc.extract(last, imgs[last[2]])
+            world = np.stack([(pk["x"] - np.float32(EUROC["cx"])) / np.float32(EUROC["fx"]),
+                              (pk["y"] - np.float32(EUROC["cy"])) / np.float32(EUROC["fy"]), np.ones(len(pk), np.float32)], -1).astype(np.float32)
+            ident = np.array([0, 0, 0, 1, 0, 0, 0], np.float32)
+            o = orc.O.sparse_img_align(pk, world, ident, orc.pyramid(last, imgs[last[2]]), ident, orc.pyramid(key(i), imgs[i]),
+                                       orc.oex.tables()["inv_scale"], EUROC, NL - 1, 1, device_order=True)
+            assert ret == o[0] and ret > 100, (step, ret, o[0])
+            assert np.abs(T - o[1]).max() <= 1e-5, (step, T, o[1])
+        aligned += 1
+
     for step, (kind, idx) in enumerate([("one", [0]), ("batch", [1, 2, 3]), ("resident", [0]), ("one", [1]), ("resident", [2]),
                                         ("resident", [3]), ("batch", [0, 1]), ("resident", [2]), ("batch", [3, 0, 1, 2, 3])]):
         if kind == "one":
             one(idx[0])
         elif kind == "resident":
             resident(idx[0])
+            if ahead:
+                align_pair0(idx[0], step)
         else:
             ex.extract_batch_host(np.stack([imgs[i] for i in idx]))
         keys = [key(i) for i in idx]
         _check(ex, orc, keys, last, W, H, (step, kind))
         last = keys[-1]
+    assert aligned == (4 if ahead else 0)
+    ex.close()
+
+
+def test_entry_points_interleaved(orc):
+    """ygzf_extract (one frame), ygzf_extract_batch_host and ygzf_compute_pyramid + ygzf_extract_resident on one 1920x1080 context: after each,
+    pair 0 of ygzf_match_batch_prev pairs the first frame with the last frame the context extracted -- whichever entry point extracted it."""
+    _interleaved(orc)
+
+
+def test_entry_points_interleaved_extract_ahead(orc):
+    """The same with ygzf_set_extract_ahead: ygzf_compute_pyramid queues the extraction and ygzf_extract_resident collects it.  After every
+    resident step pair 0 of ygzf_align_batch_prev aligns against the carried frame's pyramid, which compute_pyramid saved first."""
+    _interleaved(orc, ahead=True)
+
+
+def _make(max_batch=20):
+    from orb_ygz_slam_amd import Extractor
+    with _env():
+        return Extractor(NF, 1.2, NL, 20, 7, max_width=W, max_height=H, max_batch=max_batch)
+
+
+def _own_input_call(ex, orc, kind):
+    imgs = _images(W, H)
+    if kind == "dso":
+        ex.extract_dso(imgs[0])
+    elif kind == "dso_multilevel":
+        ex.extract_dso_multilevel(imgs[0])
+    elif kind == "fast_keypoint":
+        ex.extract_fast_keypoint(imgs[0])
+    else:
+        (kl, dl), (kr, dr) = orc.extract((W, H, 0), imgs[0]), orc.extract((W, H, 1), imgs[1])
+        ex.compute_stereo_matches(imgs[0], imgs[1], kl, dl, kr, dr, 0.11, 0.11 * 435.0)
+
+
+OWN_INPUT = ["dso", "dso_multilevel", "fast_keypoint", "stereo_matches"]
+
+
+@pytest.mark.parametrize("kind", OWN_INPUT)
+def test_calls_that_take_the_buffers_end_the_batch(orc, kind):
+    """ygzf_extract_dso (and its multi-level form), ygzf_extract_fast_keypoint and ygzf_compute_stereo_matches take the output buffers for their
+    own inputs: no extracted batch afterwards, the next extraction carries nothing (pair 0 has an empty Last frame), the one after it carries again."""
+    from orb_ygz_slam_amd import make_camera
+    from orb_ygz_slam_amd.capi import YgzfError
+    ex = _make()
+    t, last = _run(ex, orc, [2])
+    _own_input_call(ex, orc, kind)
+    with pytest.raises(YgzfError):
+        ex.match_batch_prev(make_camera(W, H), TH, True, True, True)
+    _run(ex, orc, [2, 1], t0=t, last=None)
+    ex.close()
+
+
+def test_carry_switched_off_and_on(orc):
+    """ygzf_set_carry_previous(0): an extraction returns the oracle's bytes, the batch matcher and aligner refuse; switched on again, the next
+    extraction carries the then-last frame."""
+    from orb_ygz_slam_amd import make_camera
+    from orb_ygz_slam_amd.capi import YgzfError
+    imgs = _images(W, H)
+    ex = _make()
+    t, _ = _run(ex, orc, [2])
+    ex.set_carry_previous(False)
+    for idx in ([2], [3, 0]):
+        ex.extract_batch_host(np.stack([imgs[i] for i in idx]))
+        for f, i in enumerate(idx):
+            k, d = ex.batch_fetch(f)
+            ok, od = orc.extract((W, H, i), imgs[i])
+            assert len(k) == len(ok) and (k == ok).all() and (d == od).all()
+        with pytest.raises(YgzfError):
+            ex.match_batch_prev(make_camera(W, H), TH, True, True, True)
+        with pytest.raises(YgzfError):
+            ex.align_batch_prev(make_camera(W, H), NL - 1, 1, 10)
+    ex.set_carry_previous(True)
+    _run(ex, orc, [2, 3], t0=1, last=(W, H, 0))
+    ex.close()
+
+
+def test_has_resident_image_after_each_entry_point(orc):
+    """ygzf_has_resident_image (include/ygzf.h): the context holds an image with its pyramid after ygzf_compute_pyramid, ygzf_extract and
+    ygzf_extract_resident -- and after the batch extractions from host memory, whose frame 0 lies in the same buffers -- for that size only; not
+    after a call that takes the buffers for its own inputs, nor on a new context."""
+    imgs = _images(W, H)
+    small = _images(752, 480)
+    ex = _make()
+    held = lambda: (ex.has_resident_image(W, H), ex.has_resident_image(752, 480))
+    assert held() == (False, False)
+    steps = [("extract", lambda: ex.extract(imgs[0]), (True, False)),
+             ("extract_batch_host", lambda: ex.extract_batch_host(np.stack(imgs[1:3])), (True, False)),
+             ("extract_dso", lambda: ex.extract_dso(imgs[0]), (False, False)),
+             ("extract_batch_host_frames", lambda: ex.extract_batch_host_frames([imgs[3], imgs[0]]), (True, False)),
+             ("compute_pyramid", lambda: ex.compute_pyramid(imgs[1]), (True, False)),
+             ("extract_resident", lambda: ex.extract_resident(W, H), (True, False)),
+             ("extract_fast_keypoint", lambda: ex.extract_fast_keypoint(imgs[2]), (False, False)),
+             ("compute_pyramid", lambda: ex.compute_pyramid(imgs[2]), (True, False)),
+             ("size change", lambda: ex.extract(small[0]), (False, True)),
+             ("compute_stereo_matches", lambda: _own_input_call(ex, orc, "stereo_matches"), (False, False)),
+             ("ahead on", lambda: ex.set_extract_ahead(True), (False, False)),
+             ("compute_pyramid ahead", lambda: ex.compute_pyramid(imgs[3]), (True, False)),
+             ("extract_resident ahead", lambda: ex.extract_resident(W, H), (True, False)),
+             ("extract_dso", lambda: ex.extract_dso(imgs[0]), (False, False)),
+             ("compute_pyramid ahead", lambda: ex.compute_pyramid(small[1]), (False, True))]
+    for name, call, want in steps:
+        call()
+        assert held() == want, (name, held(), want)
     ex.close()
 
 
