@@ -314,6 +314,33 @@ int ygzf_search_for_triangulation(ygzf_ctx *ctx, int n_nodes, const int *off1, c
                                   const float *level_sigma2_2, const float *F12, const float *Cw1, const float *R2w, const float *t2w,
                                   const ygzf_camera *cam2, int only_stereo, int check_orientation, int *match12, int *nmatches);
 
+/* ---- ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint*> &vpMapPoints, const float th)   src/ORBmatcher.cc:748-886, the candidate
+ *      search of :764-868 (LocalMapping::SearchInNeighbors, src/LocalMapping.cc:1259-1304) over n_kf keyframes x n_points MapPoints ----------
+ * Per keyframe (ygzf_fuse_kf): view = mvKeys, mDescriptors, mvuRight (NULL: all -1), mvScaleFactors (NULL: the context's tables) and
+ * nlevels = mnScaleLevels; cam = fx fy cx cy mbf and min_x .. max_y = mnMinX .. mnMaxY (KeyFrame::IsInImage, half-open :811-813, and the
+ * 64 x 48 grid of KeyFrame::GetFeaturesInArea :774-809); inv_level_sigma2 = mvInvLevelSigma2; Rcw / tcw / Ow = GetRotation / GetTranslation /
+ * GetCameraCenter (row-major, passed as the keyframe holds them); log_scale_factor = mfLogScaleFactor (MapPoint::PredictScale(dist, pKF),
+ * src/MapPoint.cc:343-357).  Per point (ygzf_fuse_points): GetWorldPos, GetNormal, GetMaxDistanceInvariance, GetMinDistanceInvariance, the
+ * private mfMaxDistance (PredictScale's numerator) and GetDescriptor.  skip (n_kf x n_points bytes, NULL = none): nonzero = no search (the
+ * caller's isBad / IsInKeyFrame tests of :770).
+ * Outputs, row = keyframe: best_idx[k * n_points + i] = the bestIdx the reference's loop ends with (-1: none), best_dist = its bestDist (256:
+ * none), BEFORE the map updates of :868-883 -- the caller applies those in the reference's order (orb_ygz_slam_amd/csrc/host/FuseApply.h).
+ * The call uses scratch buffers only: a context in the middle of a batch (extracted, carry queued) keeps its state.  n_kf = 0 or
+ * n_points = 0: nothing to do.  At most about 34 000 keys per keyframe (its grid lives in LDS). */
+typedef struct ygzf_fuse_kf {
+    ygzf_frame_view view;
+    ygzf_camera cam;
+    const float *inv_level_sigma2;
+    float Rcw[9], tcw[3], Ow[3];
+    float log_scale_factor;
+} ygzf_fuse_kf;
+typedef struct ygzf_fuse_points {
+    const float *world, *normal, *max_dist_inv, *min_dist_inv, *mf_max_distance;   /* n x 3, n x 3, n, n, n */
+    const uint8_t *desc;                                                             /* n x 32 */
+} ygzf_fuse_points;
+int ygzf_fuse_candidates(ygzf_ctx *ctx, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
+                         int *best_idx, int *best_dist);
+
 /* ---- Frame::ComputeBoW()   src/Frame.cc:495-500 -> ORBVocabulary::transform(features, BowVector, FeatureVector, levelsup = 4), i.e.
  *      DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>::transform   Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1151-1283 ---
  * The vocabulary tree lives on the device.  ygzf_vocabulary_set uploads it as the reference's loaders build it (loadFromTextFile

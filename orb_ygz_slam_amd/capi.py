@@ -39,6 +39,16 @@ class FrustumIn(C.Structure):
                 ("log_scale_factor", C.c_float), ("viewing_cos_limit", C.c_float)]
 
 
+class FuseKf(C.Structure):
+    _fields_ = [("view", FrameView), ("cam", Camera), ("inv_level_sigma2", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3),
+                ("Ow", C.c_float * 3), ("log_scale_factor", C.c_float)]
+
+
+class FusePoints(C.Structure):
+    _fields_ = [("world", C.c_void_p), ("normal", C.c_void_p), ("max_dist_inv", C.c_void_p), ("min_dist_inv", C.c_void_p),
+                ("mf_max_distance", C.c_void_p), ("desc", C.c_void_p)]
+
+
 class SiaFrame(C.Structure):
     _fields_ = [("n", C.c_int), ("keys", C.c_void_p), ("mp_valid", C.c_void_p), ("outlier", C.c_void_p), ("mp_world", C.c_void_p),
                 ("Tcw", C.c_float * 7), ("nlevels", C.c_int), ("levels", C.POINTER(C.c_void_p)), ("level_w", C.c_void_p),
@@ -139,6 +149,7 @@ def load_library(build_if_missing=True):
     L.ygzf_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, vp, ip]
     L.ygzf_search_for_triangulation.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(FrameView), vp, C.POINTER(FrameView), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(Camera), C.c_int, C.c_int, vp, ip]
+    L.ygzf_fuse_candidates.argtypes = [vp, C.c_int, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
     L.ygzf_compute_stereo_matches.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp]
     L.ygzf_stereo_batch.argtypes = [vp, C.c_float, C.c_float]
     L.ygzf_stereo_fetch.argtypes = [vp, C.c_int, vp, vp, C.c_int]
@@ -590,6 +601,39 @@ class Extractor:
                                                       None if sg is None else _p(sg), _p(Fm), _p(Cw), _p(Rm), _p(tm), C.byref(cam), int(only_stereo),
                                                       int(check_ori), _p(match), C.byref(n)))
         return n.value, match[:f1.n]
+
+    def fuse_candidates(self, kfs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=3.0, skip=None):
+        """ORBmatcher::Fuse(KeyFrame*, MapPoints, th) candidate search over K keyframes x P points -> (best_idx, best_dist), K x P int32
+        (-1 / 256: none).  kfs: dicts with keys (KP_DTYPE), desc, u_right (None: monocular), scale_factors (None: the context's tables),
+        inv_level_sigma2, cam (Camera: fx fy cx cy mbf, bounds), Rcw (3x3), tcw, Ow, log_scale_factor.  skip: K x P bytes or None."""
+        keep = []
+        arr = (FuseKf * max(len(kfs), 1))()
+        for k, kf in enumerate(kfs):
+            ck, cd = np.ascontiguousarray(kf["keys"], KP_DTYPE), np.ascontiguousarray(kf["desc"], np.uint8)
+            u = None if kf.get("u_right") is None else np.ascontiguousarray(kf["u_right"], np.float32)
+            sf = None if kf.get("scale_factors") is None else np.ascontiguousarray(kf["scale_factors"], np.float32)
+            ig = np.ascontiguousarray(kf["inv_level_sigma2"], np.float32)
+            keep.extend([ck, cd, u, sf, ig])
+            f = arr[k]
+            f.view = FrameView(len(ck), ck.ctypes.data, cd.ctypes.data, None if u is None else u.ctypes.data,
+                               None if sf is None else sf.ctypes.data, self.nlevels if sf is None else len(sf))
+            f.cam = kf["cam"]
+            f.inv_level_sigma2 = ig.ctypes.data
+            f.Rcw[:] = [float(x) for x in np.asarray(kf["Rcw"], np.float32).reshape(9)]
+            f.tcw[:] = [float(x) for x in np.asarray(kf["tcw"], np.float32).reshape(3)]
+            f.Ow[:] = [float(x) for x in np.asarray(kf["Ow"], np.float32).reshape(3)]
+            f.log_scale_factor = float(kf["log_scale_factor"])
+        w, nr = np.ascontiguousarray(world, np.float32).reshape(-1, 3), np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        mx, mn, mf = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (max_dist_inv, min_dist_inv, mf_max_distance))
+        d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
+        keep.extend([w, nr, mx, mn, mf, d])
+        K, P = len(kfs), len(w)
+        pts = FusePoints(w.ctypes.data, nr.ctypes.data, mx.ctypes.data, mn.ctypes.data, mf.ctypes.data, d.ctypes.data)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, P)
+        bi = np.full((max(K, 1), max(P, 1)), -1, np.int32)
+        bd = np.full((max(K, 1), max(P, 1)), 256, np.int32)
+        self._ck(self.L.ygzf_fuse_candidates(self.h, K, arr, P, C.byref(pts), None if sk is None else _p(sk), th, _p(bi), _p(bd)))
+        return bi[:K, :P].copy(), bd[:K, :P].copy()
 
     @staticmethod
     def _frustum_in(world, normal, max_dist_inv, min_dist_inv, mf_max_distance, Rcw, tcw, Ow, log_scale_factor, viewing_cos_limit, candidate, keep):

@@ -4,7 +4,8 @@
 //   ORBmatcher(float, bool), DescriptorDistance, the three Tracking-side SearchByProjection overloads, SearchByBoW(KeyFrame*, Frame&, ...),
 //   SearchForInitialization, SearchForTriangulation, FindDirectProjection   (src/ORBmatcher.cc:36-133, 155-263, 375-478, 596-741, 1218-1602);
 // the other LocalMapping / LoopClosing members (Fuse x2, SearchBySim3, SearchByProjection(KF, Scw, ...), SearchByBoW(KF, KF, ...)) are
-// outside the hot path and keep their reference bodies (link recipe).
+// outside the hot path and keep their reference bodies (link recipe) -- except Fuse(KeyFrame*, const vector<MapPoint*>&, th),
+// whose device form lives in its own file, ORBmatcherFuse.cc, linked beside this one where wanted.
 #include "ORBextractor.h"   // first: inside the reference tree this is the replacement header (same include guard)
 #include "ORBmatcher.h"     // the reference's own header (reference tree) or standalone/ORBmatcher.h, by include path
 #include "ygz_compat.h"

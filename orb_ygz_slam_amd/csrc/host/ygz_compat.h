@@ -42,6 +42,7 @@ inline int mat_refcount(const cv::Mat &m) {
 }
 }  // namespace ygz_compat
 #else  // ---------------------------------------------------------------------------------------------- stand-alone shim
+#include <algorithm>
 #include <cstdint>
 #include <cmath>
 #include <cstring>
@@ -152,6 +153,20 @@ public:
     inline int PredictScale(const float &currentDist, Frame *pF);
     std::map<KeyFrame *, size_t> mObservations;
     std::map<KeyFrame *, size_t> GetObservations() const { return mObservations; }
+    // read and written by ORBmatcher::Fuse(KeyFrame*, MapPoints, th) (src/ORBmatcher.cc:748-886); bodies below KeyFrame
+    long unsigned int mnId = 0;
+    Vector3f mNormalVector{};
+    int mnVisible = 1, mnFound = 1;
+    MapPoint *mpReplaced = nullptr;
+    Vector3f GetNormal() const { return mNormalVector; }                                        // src/MapPoint.cc:74-77
+    MapPoint *GetReplaced() const { return mpReplaced; }
+    bool IsInKeyFrame(KeyFrame *pKF) const { return mObservations.count(pKF) != 0; }           // :286-289
+    void IncreaseVisible(int n) { mnVisible += n; }                                             // :196-199
+    void IncreaseFound(int n) { mnFound += n; }                                                 // :201-204
+    inline void AddObservation(KeyFrame *pKF, size_t idx);
+    inline void Replace(MapPoint *pMP);
+    inline void ComputeDistinctiveDescriptors();
+    inline int PredictScale(const float &currentDist, KeyFrame *pKF);
 };
 class Frame {  // the members the hot path reads/writes (reference include/Frame.h)
 public:
@@ -202,7 +217,84 @@ public:
     Matrix3f GetRotation() const { return mRcw; }
     Vector3f GetTranslation() const { return mtcw; }
     Vector3f GetCameraCenter() const { return mOw; }
+    // read and written by ORBmatcher::Fuse(KeyFrame*, MapPoints, th) (src/ORBmatcher.cc:748-886; include/KeyFrame.h:289-317)
+    float mbf = 0;
+    int mnScaleLevels = 0;
+    float mfLogScaleFactor = 0;
+    std::vector<float> mvInvLevelSigma2;
+    int mnMinX = 0, mnMinY = 0, mnMaxX = 0, mnMaxY = 0;
+    bool mbBad = false;
+    bool isBad() const { return mbBad; }
+    bool IsInImage(const float &x, const float &y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }   // src/KeyFrame.cc:811-813
+    void AddMapPoint(MapPoint *pMP, const size_t &idx) { mvpMapPoints[idx] = pMP; }             // :428-431
+    void EraseMapPointMatch(const size_t &idx) { mvpMapPoints[idx] = static_cast<MapPoint *>(nullptr); }   // :433-436
+    void ReplaceMapPointMatch(const size_t &idx, MapPoint *pMP) { mvpMapPoints[idx] = pMP; }    // :445-447
 };
+inline void MapPoint::AddObservation(KeyFrame *pKF, size_t idx) {  // src/MapPoint.cc:84-94
+    if (mObservations.count(pKF)) return;
+    mObservations[pKF] = idx;
+    if (pKF->mvuRight[idx] >= 0) nObs += 2;
+    else nObs++;
+}
+inline void MapPoint::Replace(MapPoint *pMP) {  // src/MapPoint.cc:155-188 (the stand-in has no Map: mpMap->EraseMapPoint(this) is left out)
+    if (pMP->mnId == this->mnId) return;
+    std::map<KeyFrame *, size_t> obs = mObservations;
+    mObservations.clear();
+    mbBad = true;
+    const int nvisible = mnVisible, nfound = mnFound;
+    mpReplaced = pMP;
+    for (std::map<KeyFrame *, size_t>::iterator mit = obs.begin(), mend = obs.end(); mit != mend; mit++) {
+        KeyFrame *pKF = mit->first;
+        if (!pMP->IsInKeyFrame(pKF)) {
+            pKF->ReplaceMapPointMatch(mit->second, pMP);
+            pMP->AddObservation(pKF, mit->second);
+        } else {
+            pKF->EraseMapPointMatch(mit->second);
+        }
+    }
+    pMP->IncreaseFound(nfound);
+    pMP->IncreaseVisible(nvisible);
+    pMP->ComputeDistinctiveDescriptors();
+}
+inline void MapPoint::ComputeDistinctiveDescriptors() {  // src/MapPoint.cc:211-271: the observed descriptor of least median distance
+    if (mbBad || mObservations.empty()) return;
+    std::vector<const unsigned char *> vDescriptors;
+    for (std::map<KeyFrame *, size_t>::iterator mit = mObservations.begin(), mend = mObservations.end(); mit != mend; mit++)
+        if (!mit->first->isBad()) vDescriptors.push_back(mit->first->mDescriptors.ptr(mit->second));
+    if (vDescriptors.empty()) return;
+    const size_t N = vDescriptors.size();
+    std::vector<float> Distances(N * N);
+    for (size_t i = 0; i < N; i++) {
+        Distances[i * N + i] = 0;
+        for (size_t j = i + 1; j < N; j++) {
+            int distij = 0;   // ORBmatcher::DescriptorDistance
+            for (int b = 0; b < 32; b++) distij += __builtin_popcount((unsigned) (vDescriptors[i][b] ^ vDescriptors[j][b]));
+            Distances[i * N + j] = (float) distij;
+            Distances[j * N + i] = (float) distij;
+        }
+    }
+    int BestMedian = 0x7fffffff;
+    int BestIdx = 0;
+    for (size_t i = 0; i < N; i++) {
+        std::vector<int> vDists(Distances.begin() + i * N, Distances.begin() + (i + 1) * N);
+        std::sort(vDists.begin(), vDists.end());
+        const int median = vDists[(size_t) (0.5 * (N - 1))];
+        if (median < BestMedian) {
+            BestMedian = median;
+            BestIdx = (int) i;
+        }
+    }
+    cv::Mat best(1, 32, CV_8U);   // vDescriptors[BestIdx].clone()
+    std::memcpy(best.ptr(0), vDescriptors[BestIdx], 32);
+    mDescriptor = best;
+}
+inline int MapPoint::PredictScale(const float &currentDist, KeyFrame *pKF) {  // src/MapPoint.cc:343-357
+    float ratio = mfMaxDistance / currentDist;
+    int nScale = (int) std::ceil(std::log(ratio) / pKF->mfLogScaleFactor);
+    if (nScale < 0) nScale = 0;
+    else if (nScale >= pKF->mnScaleLevels) nScale = pKF->mnScaleLevels - 1;
+    return nScale;
+}
 }  // namespace ygz
 
 namespace ygz_compat {

@@ -307,6 +307,30 @@ struct FiaArgs {                    // Frame::GetFeaturesInArea queries against 
 size_t fia_lds_bytes(int n);
 hipError_t launch_features_in_area(hipStream_t st, const FiaArgs &A);
 
+// ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) candidate search, K keyframes x P points (match_kernels.hip): per pair the
+// bestIdx / bestDist of src/ORBmatcher.cc:764-868 before any map update (-1 / 256: none)
+struct FuseKf {                     // one keyframe; keys / desc / uRight are byte offsets from FuseArgs::base (uRight -1: monocular)
+    long long keys, desc, uRight;
+    int n, nLevels;
+    float Rcw[9], tcw[3], Ow[3];
+    float fx, fy, cx, cy, mbf, minX, minY, maxX, maxY, gridInvW, gridInvH;
+    float levelStep[kMaxLevels];    // PredictScale steps of this keyframe's mfLogScaleFactor / mnScaleLevels (as FrustumArgs::levelStep)
+    float scale[kMaxLevels];        // mvScaleFactors
+    float invSigma2[kMaxLevels];    // mvInvLevelSigma2
+};
+struct FuseArgs {
+    int nKf, nPoints, slice;        // slice = points per workgroup; grid = (ceil(nPoints / slice), nKf)
+    const uint8_t *base;
+    const FuseKf *kfs;
+    const float *world, *normal, *maxDistInv, *minDistInv, *mfMaxDistance;   // n x 3, n x 3, n, n, n
+    const uint8_t *mpDesc;          // n x 32
+    const uint8_t *skip;            // nullable: nKf x nPoints, nonzero = no search
+    float th;
+    int *bestIdx, *bestDist;        // nKf x nPoints
+};
+size_t fuse_lds_bytes(int maxKeys);
+hipError_t launch_fuse(hipStream_t st, const FuseArgs &A, int maxKeys);
+
 struct SiaArgs {
     int ldsFeat;                    // feature slots of the dynamic LDS carve-up (float4 s_feat[ldsFeat] | float2 s_uv[ldsFeat] | float4 s_jac[2*ldsFeat])
     int stageOff, stageBytes;       // byte offset (from the start of dynamic LDS) and size of the staged current-image region

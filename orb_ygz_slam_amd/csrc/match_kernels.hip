@@ -1713,20 +1713,18 @@ static inline size_t al16(size_t b) { return (b + 15) & ~(size_t) 15; }
 // sort; the cells of one grid column are adjacent, so the cells [minCy, maxCy] of column ix are ONE contiguous run of the list) and
 // serves a slice of the queries, one wave per query: 64 list entries per step, ordered append by ballot rank.
 // ------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
-    __shared__ int s_tmp[kMatchBlock / 64];
-    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
-    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
-    int *list = cellFill + GRID_CELLS;               // n
+// Frame::AssignFeaturesToGrid in LDS (one workgroup of kMatchBlock threads): cellStart[GRID_CELLS + 1] holds the exclusive prefix of the cell
+// counts, list[cellStart[c] ..) the keypoint indices of cell c in ascending order (the reference's push_back order); cellFill (GRID_CELLS)
+// and s_tmp (kMatchBlock / 64) are scratch.  Ends with a barrier.
+__device__ void build_grid_lds(const ygzf_kp *__restrict__ keys, int n, float minX, float minY, float gridInvW, float gridInvH, int *cellStart,
+                               int *cellFill, int *list, int *s_tmp) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int n = A.n;
     for (int i = tid; i < GRID_CELLS; i += kMatchBlock) cellFill[i] = 0;
     __syncthreads();
     for (int i = tid; i < n; i += kMatchBlock) {
-        const ygzf_kp k = A.keys[i];
-        const int px = (int) roundf((k.x - A.minX) * A.gridInvW);     // Frame::PosInGrid (round, as the reference)
-        const int py = (int) roundf((k.y - A.minY) * A.gridInvH);
+        const ygzf_kp k = keys[i];
+        const int px = (int) roundf((k.x - minX) * gridInvW);     // Frame::PosInGrid (round, as the reference)
+        const int py = (int) roundf((k.y - minY) * gridInvH);
         if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) atomicAdd(&cellFill[px * GRID_ROWS + py], 1);
     }
     __syncthreads();
@@ -1751,9 +1749,9 @@ __global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
     for (int i = tid; i < GRID_CELLS; i += kMatchBlock) cellFill[i] = cellStart[i];
     __syncthreads();
     for (int i = tid; i < n; i += kMatchBlock) {
-        const ygzf_kp k = A.keys[i];
-        const int px = (int) roundf((k.x - A.minX) * A.gridInvW);
-        const int py = (int) roundf((k.y - A.minY) * A.gridInvH);
+        const ygzf_kp k = keys[i];
+        const int px = (int) roundf((k.x - minX) * gridInvW);
+        const int py = (int) roundf((k.y - minY) * gridInvH);
         if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) list[atomicAdd(&cellFill[px * GRID_ROWS + py], 1)] = i;
     }
     __syncthreads();
@@ -1767,6 +1765,16 @@ __global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
         }
     }
     __syncthreads();
+}
+
+__global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    __shared__ int s_tmp[kMatchBlock / 64];
+    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
+    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
+    int *list = cellFill + GRID_CELLS;               // n
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    build_grid_lds(A.keys, A.n, A.minX, A.minY, A.gridInvW, A.gridInvH, cellStart, cellFill, list, s_tmp);
     const unsigned long long lt = (1ull << lane) - 1ull;
     const int wavesTotal = gridDim.x * (kMatchBlock / 64);
     for (int q = blockIdx.x * (kMatchBlock / 64) + wave; q < A.nq; q += wavesTotal) {
@@ -1820,6 +1828,118 @@ hipError_t launch_features_in_area(hipStream_t st, const FiaArgs &A) {
     const int perWg = kMatchBlock / 64;
     const int wgs = std::max(1, std::min(64, (A.nq + 4 * perWg - 1) / (4 * perWg)));   // >= 4 queries per wave before another workgroup rebuilds the grid
     hipLaunchKernelGGL(k_features_in_area, dim3(wgs), dim3(kMatchBlock), lds, st, A);
+    return hipSuccess;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// ORBmatcher::Fuse(KeyFrame *pKF, const vector<MapPoint *> &vpMapPoints, th), the candidate search of every (keyframe, point) pair
+// (src/ORBmatcher.cc:764-868) from one snapshot; the map updates of :868-883 stay on the host (host/FuseApply.h).  Workgroup = one keyframe
+// (blockIdx.y) x a slice of points: the keyframe's 64x48 grid is rebuilt in LDS (build_grid_lds, as k_features_in_area), then one wave per point
+// walks KeyFrame::GetFeaturesInArea's list (src/KeyFrame.cc:774-809: columns, rows, key index), 64 entries per step.  Each lane keeps the
+// least (dist << 16 | list position) of its entries; the wave minimum is the reference's first minimum under its strict `<`.
+// Arithmetic in the reference's order (-ffp-contract=off); Rcw*P + t and the squared norm as k_frustum.  Where Fuse differs from isInFrustum:
+// x = PcX*invz then fx*x + cx; KeyFrame::IsInImage is half-open (:811-813); the viewing test is PO.Pn < 0.5*dist3D in double; the error
+// gates compare the float product with the double literals 7.8 / 5.99.
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMatchBlock) void k_fuse(FuseArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    __shared__ int s_tmp[kMatchBlock / 64];
+    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
+    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
+    int *list = cellFill + GRID_CELLS;               // n
+    const int kf = blockIdx.y;
+    const FuseKf &K = A.kfs[kf];
+    const ygzf_kp *keys = (const ygzf_kp *) (A.base + K.keys);
+    const uint8_t *kdesc = A.base + K.desc;
+    const float *uRight = K.uRight >= 0 ? (const float *) (A.base + K.uRight) : nullptr;
+    build_grid_lds(keys, K.n, K.minX, K.minY, K.gridInvW, K.gridInvH, cellStart, cellFill, list, s_tmp);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int p0 = blockIdx.x * A.slice, p1 = min(A.nPoints, p0 + A.slice);
+    for (int i = p0 + wave; i < p1; i += kMatchBlock / 64) {
+        const size_t o = (size_t) kf * A.nPoints + i;
+        int bestIdx = -1, bestDist = 256;
+        do {
+            if (A.skip && A.skip[o]) break;
+            const float *P = A.world + 3 * (size_t) i;
+            const float PcX = (K.Rcw[0] * P[0] + K.Rcw[1] * P[1] + K.Rcw[2] * P[2]) + K.tcw[0];
+            const float PcY = (K.Rcw[3] * P[0] + K.Rcw[4] * P[1] + K.Rcw[5] * P[2]) + K.tcw[1];
+            const float PcZ = (K.Rcw[6] * P[0] + K.Rcw[7] * P[1] + K.Rcw[8] * P[2]) + K.tcw[2];
+            if (PcZ < 0.0f) break;
+            const float invz = 1 / PcZ;
+            const float x = PcX * invz, y = PcY * invz;
+            const float u = K.fx * x + K.cx, v = K.fy * y + K.cy;
+            if (!(u >= K.minX && u < K.maxX && v >= K.minY && v < K.maxY)) break;
+            const float ur = u - K.mbf * invz;
+            const float PO[3] = {P[0] - K.Ow[0], P[1] - K.Ow[1], P[2] - K.Ow[2]};
+            const float dist3D = sqrtf(PO[0] * PO[0] + PO[1] * PO[1] + PO[2] * PO[2]);
+            if (dist3D < A.minDistInv[i] || dist3D > A.maxDistInv[i]) break;
+            const float *Pn = A.normal + 3 * (size_t) i;
+            const float dot = PO[0] * Pn[0] + PO[1] * Pn[1] + PO[2] * Pn[2];
+            if ((double) dot < 0.5 * (double) dist3D) break;
+            const float ratio = A.mfMaxDistance[i] / dist3D;
+            int pred = 0;
+            for (int k = 1; k < K.nLevels; k++) pred += (ratio >= K.levelStep[k]) ? 1 : 0;
+            const float r = A.th * K.scale[pred];
+            const int nMinCellX = max(0, (int) floorf((u - K.minX - r) * K.gridInvW));
+            if (nMinCellX >= GRID_COLS) break;
+            const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((u - K.minX + r) * K.gridInvW));
+            if (nMaxCellX < 0) break;
+            const int nMinCellY = max(0, (int) floorf((v - K.minY - r) * K.gridInvH));
+            if (nMinCellY >= GRID_ROWS) break;
+            const int nMaxCellY = min(GRID_ROWS - 1, (int) ceilf((v - K.minY + r) * K.gridInvH));
+            if (nMaxCellY < 0 || nMinCellY > nMaxCellY) break;
+            const uint64_t *md = (const uint64_t *) (A.mpDesc + 32 * (size_t) i);
+            const uint64_t m0 = md[0], m1 = md[1], m2 = md[2], m3 = md[3];
+            unsigned best = 0xFFFFFFFFu;
+            int bestLane = -1;
+            int ord = 0;   // position in GetFeaturesInArea's concatenated cell lists
+            for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
+                const int s = cellStart[ix * GRID_ROWS + nMinCellY], e = cellStart[ix * GRID_ROWS + nMaxCellY + 1];
+                for (int base = s; base < e; base += 64, ord += 64) {
+                    const int j = base + lane;
+                    if (j >= e) continue;
+                    const int idx = list[j];
+                    const ygzf_kp kp = keys[idx];
+                    if (!(fabsf(kp.x - u) < r && fabsf(kp.y - v) < r)) continue;   // GetFeaturesInArea
+                    const int kpLevel = kp.octave;
+                    if (kpLevel < pred - 1 || kpLevel > pred) continue;
+                    const float ex = u - kp.x, ey = v - kp.y;
+                    const float kpr = uRight ? uRight[idx] : -1.0f;
+                    if (kpr >= 0) {
+                        const float er = ur - kpr;
+                        const float e2 = ex * ex + ey * ey + er * er;
+                        if ((double) (e2 * K.invSigma2[kpLevel]) > 7.8) continue;
+                    } else {
+                        const float e2 = ex * ex + ey * ey;
+                        if ((double) (e2 * K.invSigma2[kpLevel]) > 5.99) continue;
+                    }
+                    const uint64_t *d = (const uint64_t *) (kdesc + 32 * (size_t) idx);
+                    const unsigned dist = __popcll(d[0] ^ m0) + __popcll(d[1] ^ m1) + __popcll(d[2] ^ m2) + __popcll(d[3] ^ m3);
+                    if (dist >= 256) continue;   // never below the initial bestDist = 256
+                    const unsigned key = (dist << 16) | (unsigned) (ord + lane);
+                    if (key < best) { best = key; bestLane = idx; }
+                }
+            }
+            const unsigned wbest = wave_min_dpp(best);
+            if (wbest == 0xFFFFFFFFu) break;
+            const unsigned long long owner = __ballot(best == wbest);
+            bestIdx = __shfl(bestLane, (int) __ffsll((long long) owner) - 1);
+            bestDist = (int) (wbest >> 16);
+        } while (false);
+        if (lane == 0) {
+            A.bestIdx[o] = bestIdx;
+            A.bestDist[o] = bestDist;
+        }
+    }
+}
+
+size_t fuse_lds_bytes(int maxKeys) { return fia_lds_bytes(maxKeys); }
+
+hipError_t launch_fuse(hipStream_t st, const FuseArgs &A, int maxKeys) {
+    if (A.nKf <= 0 || A.nPoints <= 0) return hipSuccess;
+    hipError_t e = hipFuncSetAttribute((const void *) k_fuse, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_fuse, dim3((A.nPoints + A.slice - 1) / A.slice, A.nKf), dim3(kMatchBlock), fuse_lds_bytes(maxKeys), st, A);
     return hipSuccess;
 }
 

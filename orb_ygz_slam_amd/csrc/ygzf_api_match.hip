@@ -1,4 +1,4 @@
-// ygzf_api_match.hip -- ORBmatcher's entry points: SearchByProjection (all overloads), SearchByBoW, SearchForInitialization, SearchForTriangulation, the Frame grid, Frame::isInFrustum, MapPoint::ComputeDistinctiveDescriptors, ORBVocabulary::transform (C ABI of libygzf, include/ygzf.h; product code: no CPU fallback, nothing from oracle/ is included or linked).
+// ygzf_api_match.hip -- ORBmatcher's entry points: SearchByProjection (all overloads), SearchByBoW, SearchForInitialization, SearchForTriangulation, Fuse (candidate search), the Frame grid, Frame::isInFrustum, MapPoint::ComputeDistinctiveDescriptors, ORBVocabulary::transform (C ABI of libygzf, include/ygzf.h; product code: no CPU fallback, nothing from oracle/ is included or linked).
 #include "ygzf_ctx.h"
 
 extern "C" {
@@ -613,6 +613,88 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
     *nmatches = tail[0];
     set_match_pairs(c, 0);
     return YGZF_OK;
+}
+
+// ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) candidate search, src/ORBmatcher.cc:764-868 (include/ygzf.h).  Validation
+// first; one packed copy in (every keyframe's keys / descriptors / mvuRight, the point arrays, the skip mask, the per-keyframe tables), one out.
+// Touches nothing in c->held: only the packed staging area is written.
+int ygzf_fuse_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
+                         int *best_idx, int *best_dist) {
+    if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
+    if (n_kf < 0 || n_points < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
+    if (n_kf == 0 || n_points == 0) return YGZF_OK;
+    if (!kfs || !pts || !best_idx || !best_dist) return fail(c, YGZF_ERR_INVALID, "null argument");
+    if (!pts->world || !pts->normal || !pts->max_dist_inv || !pts->min_dist_inv || !pts->mf_max_distance || !pts->desc)
+        return fail(c, YGZF_ERR_INVALID, "null point array");
+    int maxKeys = 0;
+    for (int k = 0; k < n_kf; k++) {
+        const ygzf_fuse_kf &K = kfs[k];
+        const int n = K.view.n;
+        if (n < 0) return fail(c, YGZF_ERR_INVALID, "keyframe %d: negative key count", k);
+        if (n > 0 && (!K.view.keys || !K.view.desc)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null key array", k);
+        if (!K.inv_level_sigma2) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null mvInvLevelSigma2", k);
+        const int L = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
+        if (L < 1 || L > kMaxLevels) return fail(c, YGZF_ERR_INVALID, "keyframe %d: nlevels out of range", k);
+        if (!(K.cam.max_x > K.cam.min_x) || !(K.cam.max_y > K.cam.min_y)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: empty image bounds", k);
+        for (int i = 0; i < n; i++)
+            if (K.view.keys[i].octave < 0 || K.view.keys[i].octave >= L)
+                return fail(c, YGZF_ERR_INVALID, "keyframe %d: keypoint octave outside the scale tables", k);
+        if (fuse_lds_bytes(n) > (size_t) kMaxDynLds)
+            return fail(c, YGZF_ERR_UNSUPPORTED, "keyframe %d: more than %d keypoints in one grid", k, (int) ((kMaxDynLds - 25000) / 4));
+        maxKeys = std::max(maxKeys, n);
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    int rc;
+    PackedTransfer P(c);
+    std::vector<FuseKf> fk((size_t) n_kf);
+    for (int k = 0; k < n_kf; k++) {
+        const ygzf_fuse_kf &K = kfs[k];
+        FuseKf &F = fk[k];
+        memset(&F, 0, sizeof F);
+        const size_t n = (size_t) K.view.n;
+        F.keys = (long long) P.add_in(K.view.keys, sizeof(ygzf_kp) * n);
+        F.desc = (long long) P.add_in(K.view.desc, 32 * n);
+        F.uRight = K.view.u_right ? (long long) P.add_in(K.view.u_right, 4 * n) : -1;
+        F.n = (int) n;
+        F.nLevels = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
+        memcpy(F.Rcw, K.Rcw, 36);
+        memcpy(F.tcw, K.tcw, 12);
+        memcpy(F.Ow, K.Ow, 12);
+        F.fx = K.cam.fx; F.fy = K.cam.fy; F.cx = K.cam.cx; F.cy = K.cam.cy; F.mbf = K.cam.mbf;
+        F.minX = K.cam.min_x; F.minY = K.cam.min_y; F.maxX = K.cam.max_x; F.maxY = K.cam.max_y;
+        F.gridInvW = (float) 64 / (K.cam.max_x - K.cam.min_x);   // mfGridElementWidthInv / HeightInv, src/Frame.cc:302-303
+        F.gridInvH = (float) 48 / (K.cam.max_y - K.cam.min_y);
+        predict_scale_steps(K.log_scale_factor, F.nLevels, F.levelStep);
+        for (int l = 0; l < kMaxLevels; l++) {
+            F.scale[l] = l < F.nLevels ? (K.view.scale_factors ? K.view.scale_factors[l] : c->tab.scale[l]) : 1.f;
+            F.invSigma2[l] = l < F.nLevels ? K.inv_level_sigma2[l] : 1.f;
+        }
+    }
+    const size_t N = (size_t) n_points, KP = (size_t) n_kf * N;
+    const size_t iKf = P.add_in(fk.data(), sizeof(FuseKf) * fk.size()), iW = P.add_in(pts->world, 12 * N), iN = P.add_in(pts->normal, 12 * N),
+                 iMax = P.add_in(pts->max_dist_inv, 4 * N), iMin = P.add_in(pts->min_dist_inv, 4 * N), iMf = P.add_in(pts->mf_max_distance, 4 * N),
+                 iD = P.add_in(pts->desc, 32 * N), iS = P.add_in(skip, skip ? KP : 0);
+    const size_t oI = P.add_out(best_idx, 4 * KP), oD = P.add_out(best_dist, 4 * KP);
+    uint8_t *d;
+    if ((rc = P.upload(&d))) return rc;
+    FuseArgs A;
+    A.nKf = n_kf; A.nPoints = n_points;
+    A.slice = 64;   // points per workgroup (four per wave): a forward pass of 20 keyframes x 1 500 points and a reverse pass of 1 x 30 000 both give ~500 workgroups
+    A.base = d;
+    A.kfs = (const FuseKf *) (d + iKf);
+    A.world = (const float *) (d + iW); A.normal = (const float *) (d + iN);
+    A.maxDistInv = (const float *) (d + iMax); A.minDistInv = (const float *) (d + iMin); A.mfMaxDistance = (const float *) (d + iMf);
+    A.mpDesc = d + iD;
+    A.skip = skip ? d + iS : nullptr;
+    A.th = th;
+    A.bestIdx = (int *) P.d_out(oI);
+    A.bestDist = (int *) P.d_out(oD);
+    {
+        ProfScope ps(c, KK_FUSE);
+        HIPCHECK(c, launch_fuse(c->stream, A, maxKeys));
+    }
+    HIPCHECK(c, hipGetLastError());
+    return P.download();
 }
 
 int ygzf_search_for_initialization(ygzf_ctx *c, const ygzf_frame_view *F1, const ygzf_frame_view *F2, const ygzf_camera *cam, float *prev_matched_xy,
