@@ -80,6 +80,10 @@ int ygzf_pyramid_plan_host(const ygzf_extractor_cfg *cfg, int w, int h, int *n_s
 /* The level the strips of that plan start from: 0 = the image (the whole chain is the one launch); b > 0 (images too large for that: 3840 x 2160): levels
  * 1 .. b come from one launch each and the strips stage level b instead of the image -- rows[..] of the levels below b are zero.  Negative: an error code. */
 int ygzf_pyramid_plan_base_host(const ygzf_extractor_cfg *cfg, int w, int h);
+/* The launches of the octree's sort plan for ONE w x h geometry, without a context or a device (host arithmetic only).  Returns the number of
+ * launches (0: the geometry takes the histogram plan or keeps its node arrays in global memory) or a negative error code; groups[6 i .. 6 i + 5] =
+ * first level, levels, threads per workgroup, list capacity, candidate budget, dynamic LDS bytes (groups_cap ints available; NULL: count only). */
+int ygzf_octree_sort_plan_host(const ygzf_extractor_cfg *cfg, int w, int h, int *groups, int groups_cap);
 
 /* ORBextractor::operator() on the image whose pyramid the context's previous call, ygzf_compute_pyramid, left on the device: FAST, octree,
  * orientation and descriptors without a second upload and a second pyramid (Frame's constructors call ComputePyramid and then the

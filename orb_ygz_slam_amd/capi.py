@@ -239,6 +239,20 @@ def pyramid_plan_host(nfeatures, scale_factor, nlevels, w, h):
             "rows": rows[:n.value * nlevels * 4].astype(np.int64).reshape(n.value, nlevels, 4)}
 
 
+def octree_sort_plan_host(nfeatures, scale_factor, nlevels, w, h):
+    """ygzf_octree_sort_plan_host: the launches of the octree's sort plan for one w x h geometry (host arithmetic only, no device) -- a list of
+    dicts with `l0`, `n`, `block`, `cap`, `lds_cand`, `lds_bytes`; empty when the geometry takes another plan."""
+    L = load_library()
+    L.ygzf_octree_sort_plan_host.argtypes = [C.POINTER(ExtractorCfg), C.c_int, C.c_int, C.c_void_p, C.c_int]
+    cfg = ExtractorCfg(nfeatures, scale_factor, nlevels, 20, 7, 0)
+    out = np.zeros(6 * 16, np.int32)
+    n = L.ygzf_octree_sort_plan_host(C.byref(cfg), w, h, _p(out), out.size)
+    if n < 0:
+        raise YgzfError("ygzf_octree_sort_plan_host failed (%d)" % n)
+    keys = ("l0", "n", "block", "cap", "lds_cand", "lds_bytes")
+    return [dict(zip(keys, (int(v) for v in out[6 * i:6 * i + 6]))) for i in range(n)]
+
+
 class Extractor:
     """Thin object wrapper over a ygzf_ctx (mirrors ygz::ORBextractor's constructor arguments)."""
 

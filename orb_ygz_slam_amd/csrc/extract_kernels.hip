@@ -162,28 +162,30 @@ __device__ __forceinline__ void block_scan_array3(int *a, int *b, int *c, int n,
 
 // Stable LSD radix sort (kRadixBits-bit digits) of n (key,val) pairs on `bits` key bits by the whole block.
 // k0/v0 hold the input; result is left in *rk/*rv (one of the two buffers).  Buffers may be LDS or global.
-// histT: kRadixHist ints of LDS (digit-major, one counter per wave), tmp: 17 ints of LDS.
+// histT: radix_hist_ints(kWaves) ints of LDS (digit-major, one counter per wave), tmp: 17 ints of LDS.  kWaves = the block's waves (<= 16).
 // Seven-bit digits: the octree's 21-bit path keys take three passes (4-bit digits took six, at ~3.4 us of mostly barrier time each).
 constexpr int kRadixBits = 7;
-constexpr int kRadixHist = (1 << kRadixBits) * 16;   // up to 16 waves
+constexpr int radix_hist_ints(int waves) { return (1 << kRadixBits) * waves; }
+template <int kWaves>
 __device__ void block_radix_sort(unsigned *k0, unsigned *v0, unsigned *k1, unsigned *v1, int n, int bits,
                                  volatile int *histT, int *tmp, unsigned **rk, unsigned **rv) {
+    static_assert(kWaves >= 1 && kWaves <= 16, "block_excl_scan's scratch holds up to 16 waves");
     const int lane = lane_id(), wave = wave_id();
-    const int nw = blockDim.x >> 6;  // <= 16
+    constexpr int nw = kWaves;
     const int seg = (((n + nw - 1) / nw) + 63) & ~63;
     const int start = wave * seg;
     const int end = min(n, start + seg);
     const unsigned long long lt = (1ull << lane) - 1ull;
     constexpr int NB = 1 << kRadixBits;
     for (int shift = 0; shift < bits; shift += kRadixBits) {
-        for (int t = threadIdx.x; t < NB * 16; t += blockDim.x) histT[t] = 0;
+        for (int t = threadIdx.x; t < NB * nw; t += blockDim.x) histT[t] = 0;
         __syncthreads();
         for (int i = start + lane; i < end; i += 64) {
             const int d = (k0[i] >> shift) & (NB - 1);
-            atomicAdd((int *) &histT[d * 16 + wave], 1);
+            atomicAdd((int *) &histT[d * nw + wave], 1);
         }
         __syncthreads();
-        block_scan_array((int *) histT, NB * 16, tmp);   // exclusive, digit-major then wave: the scatter base of every (digit, wave)
+        block_scan_array((int *) histT, NB * nw, tmp);   // exclusive, digit-major then wave: the scatter base of every (digit, wave)
         for (int base = start; base < end; base += 64) {
             const int i = base + lane;
             const bool valid = i < end;
@@ -200,12 +202,12 @@ __device__ void block_radix_sort(unsigned *k0, unsigned *v0, unsigned *k1, unsig
             const int rank = __popcll(m & lt);
             const int cnt = __popcll(m);
             int pos = 0;
-            if (valid) pos = histT[d * 16 + wave] + rank;
+            if (valid) pos = histT[d * nw + wave] + rank;
             __builtin_amdgcn_wave_barrier();
             if (valid) {
                 k1[pos] = key;
                 v1[pos] = val;
-                if (rank == cnt - 1) histT[d * 16 + wave] = pos + 1;
+                if (rank == cnt - 1) histT[d * nw + wave] = pos + 1;
             }
             __builtin_amdgcn_wave_barrier();
         }
@@ -1335,7 +1337,7 @@ struct OctShared {  // carved out of dynamic LDS
     int *Epos, *Ecnt;         // expandable nodes in creation order (cap each)
     unsigned *sk[2], *sv[2];  // sort buffers for E (cap each)
     int *flag;                // processed flag per list position (cap)
-    unsigned *cand;           // LDS-resident candidate sort buffers (4 x ldsCand), optional
+    unsigned *cand;           // LDS-resident candidate sort buffer(s), optional: 2 x ldsCand (the second one over the node arrays), 4 x ldsCand with global node arrays
 };
 
 // kGlobalNodes: the 19 per-list-position arrays live in a global arena (nodeArena, 19 * cap ints per (frame, level)) instead of LDS --
@@ -1352,8 +1354,12 @@ constexpr unsigned kNoKeypoint = 0xFFFFFFFFu;   // procRec.y of a processing pos
 // in tree passes whose every boundary search was 11 dependent global reads; here the candidates are read twice, linearly, and the tree passes
 // stay in LDS.  A tree that wants to split a node BELOW depth dm (a few very crowded spots in an otherwise empty level) raises s_overflow and
 // the workgroup starts over on the sorting path -- same result, the old speed.
-template <bool kGlobalNodes, bool kHist>
-__global__ __launch_bounds__(kOctBlock) __attribute__((amdgpu_waves_per_eu(kHist ? 4 : 8, 8))) void k_octree(const LevelGeom *__restrict__ geom, int nlevels, int levelBase,
+//
+// kBlock: threads per workgroup (1024 / 512 / 256).  The host sizes it per launch with the levels it carries (ygzf_api.hip, plan_oct_sort): a 1024-thread
+// workgroup holds half a CU's wave slots whatever its LDS, so that two of them left no room for the other contexts' FAST and describe waves.  Every loop
+// strides by it; the results do not depend on it.
+template <bool kGlobalNodes, bool kHist, int kBlock>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kHist ? 4 : 8, 8))) void k_octree(const LevelGeom *__restrict__ geom, int nlevels, int levelBase,
                                                       const unsigned short *__restrict__ cellCnt,
                                                       const unsigned *__restrict__ slots, int totalCells,
                                                       long long totalSlots, unsigned *__restrict__ candKey0,
@@ -1366,7 +1372,7 @@ __global__ __launch_bounds__(kOctBlock) __attribute__((amdgpu_waves_per_eu(kHist
                                                       int regionInts, int histBins, int *gHist, int *gDone, int doneTarget, int spinBudget) {
     static_assert(!(kGlobalNodes && kHist), "the histogram plan keeps the node arrays in LDS");
     extern __shared__ __attribute__((aligned(16))) int dyn[];
-    __shared__ int histT[kRadixHist];
+    __shared__ int histT[radix_hist_ints(kBlock / 64)];
     __shared__ int s_tmp[20];
     __shared__ unsigned long long s_tmp64[17];
     __shared__ int s_n, s_nE, s_cut, s_flagA, s_overflow;
@@ -1400,11 +1406,13 @@ __global__ __launch_bounds__(kOctBlock) __attribute__((amdgpu_waves_per_eu(kHist
     if (nCells <= 0 || g.nCols <= 0) {
         if (part != 0) { helper_leaves(); return; }
         if (tid == 0) { *lvlCnt = 0; lvlCandCnt[f * nlevels + l] = 0; }
-        for (int i = tid; i < g.kpCap; i += kOctBlock) procRec[(long long) f * kpStride + g.kpBase + i] = make_uint2(0u, kNoKeypoint);
+        for (int i = tid; i < g.kpCap; i += kBlock) procRec[(long long) f * kpStride + g.kpBase + i] = make_uint2(0u, kNoKeypoint);
         return;
     }
     OctShared S;
     int *PS = nullptr;        // kHist: histBins + 1 ints behind the region the cell table, the key tables and (later) the node arrays share
+    unsigned *candB = nullptr;   // LDS node arrays, sort plan: the candidates' second sort buffer (2 * ldsCand words) lies over the cell table and the
+                                 // node arrays -- both idle while the candidates are sorted; the first one (2 * ldsCand words) behind that region
     {
         int *p = dyn;
         S.cellPref = p;
@@ -1418,7 +1426,11 @@ __global__ __launch_bounds__(kOctBlock) __attribute__((amdgpu_waves_per_eu(kHist
         S.Epos = p; p += cap; S.Ecnt = p; p += cap;
         for (int b = 0; b < 2; b++) { S.sk[b] = (unsigned *) p; p += cap; S.sv[b] = (unsigned *) p; p += cap; }
         S.flag = p; p += cap;
-        S.cand = (unsigned *) (kGlobalNodes ? candLds : p);   // 4 * ldsCand words: key/val double buffers when the level's candidates fit
+        if (kGlobalNodes) S.cand = (unsigned *) candLds;   // 4 * ldsCand words: key/val double buffers when the level's candidates fit
+        else if (!kHist) {
+            candB = (unsigned *) dyn;
+            S.cand = (unsigned *) dyn + max((int) (p - dyn), 2 * ldsCand);   // (p - dyn: a multiple of 4, as is ldsCand)
+        }
     }
     const unsigned short *cc = cellCnt + (long long) f * totalCells + g.cellBase;
     const unsigned *sl = slots + (long long) f * totalSlots + g.slotBase;
@@ -1443,7 +1455,7 @@ __global__ __launch_bounds__(kOctBlock) __attribute__((amdgpu_waves_per_eu(kHist
 restart:   // (kHist: a second time, on the sorting path, after the tree asked for a split below depth dm)
     if (kHist && tid == 0) s_overflow = 0;
     // ---- 1. candidate offsets per cell (cell-major order == the reference's vToDistributeKeys order) ----
-    for (int i = tid; i < nCells; i += kOctBlock) S.cellPref[i] = cc[i];
+    for (int i = tid; i < nCells; i += kBlock) S.cellPref[i] = cc[i];
     __syncthreads();
     const int M = block_scan_array(S.cellPref, nCells, s_tmp);
     if (tid == 0) { S.cellPref[nCells] = M; if (part == 0) lvlCandCnt[f * nlevels + l] = M; }
@@ -1451,13 +1463,17 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
     if (M == 0) {
         if (part != 0) { helper_leaves(); return; }
         if (tid == 0) *lvlCnt = 0;
-        for (int i = tid; i < g.kpCap; i += kOctBlock) procRec[(long long) f * kpStride + g.kpBase + i] = make_uint2(0u, kNoKeypoint);
+        for (int i = tid; i < g.kpCap; i += kBlock) procRec[(long long) f * kpStride + g.kpBase + i] = make_uint2(0u, kNoKeypoint);
         return;
     }
     OSTAMP(1);
     // ---- 2. path keys: one thread per candidate (its cell by binary search in the prefix table) ----
     const bool inLds = M <= ldsCand;
-    if (inLds) { key0 = S.cand; val0 = S.cand + ldsCand; key1 = S.cand + 2 * ldsCand; val1 = S.cand + 3 * ldsCand; }
+    if (inLds) {
+        key0 = S.cand; val0 = S.cand + ldsCand;
+        if (candB) { key1 = candB; val1 = candB + ldsCand; }
+        else { key1 = S.cand + 2 * ldsCand; val1 = S.cand + 3 * ldsCand; }
+    }
     // A workgroup has ONE CU: 2800 candidates x ~300 instructions of cell decode (a division), root (a float division) and ten
     // subdivision steps were 7 us of a 752x480 level 0.  x and y subdivide independently, so the key is the OR of a per-column word
     // (root, x bits spread to the even positions) and a per-row word (y bits on the odd positions): both tables and the cells' origins
@@ -1473,7 +1489,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
             v = (v | (v << 2)) & 0x33333333u;
             return (v | (v << 1)) & 0x55555555u;
         };
-        for (int t = tid; t < lenX + lenY + nCells; t += kOctBlock) {
+        for (int t = tid; t < lenX + lenY + nCells; t += kBlock) {
             if (t < lenX) {
                 const int x = t;
                 int root = (int) ((float) x / g.hX);
@@ -1507,7 +1523,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         __syncthreads();
     }
     if (kHist && useHist) {
-        for (int b = tid; b <= nBins; b += kOctBlock) PS[b] = 0;
+        for (int b = tid; b <= nBins; b += kBlock) PS[b] = 0;
         __syncthreads();
     }
     {
@@ -1517,10 +1533,10 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         while ((1 << steps) < nCells) steps++;
         constexpr int kKU = 4;
         const int shares = kHist && useHist && !alone ? parts : 1;   // (the sorting path after a restart, or no helpers in sight: workgroup 0 takes everything)
-        for (int i0 = tid + part * kKU * kOctBlock; i0 < M; i0 += shares * kKU * kOctBlock) {
+        for (int i0 = tid + part * kKU * kBlock; i0 < M; i0 += shares * kKU * kBlock) {
             int ia[kKU], a[kKU], b[kKU];
 #pragma unroll
-            for (int u = 0; u < kKU; u++) { ia[u] = min(i0 + u * kOctBlock, M - 1); a[u] = 0; b[u] = nCells; }
+            for (int u = 0; u < kKU; u++) { ia[u] = min(i0 + u * kBlock, M - 1); a[u] = 0; b[u] = nCells; }
             for (int st = 0; st < steps; st++) {             // a[u] = last cell c with cellPref[c] <= ia[u]
 #pragma unroll
                 for (int u = 0; u < kKU; u++) {
@@ -1549,7 +1565,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
             int binOf[kKU];
 #pragma unroll
             for (int u = 0; u < kKU; u++) {
-                const int i = i0 + u * kOctBlock;
+                const int i = i0 + u * kBlock;
                 binOf[u] = -2 - (tid & 63);
                 if (i < M) {
                     const int x = (int) (e[u] & 255u) + ox[u], y = (int) ((e[u] >> 8) & 255u) + oy[u];
@@ -1580,7 +1596,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         __syncthreads();
         if (part != 0) {
             int *mine = gh + (long long) (part - 1) * histBins;
-            for (int b = tid; b < nBins; b += kOctBlock) mine[b] = PS[b];
+            for (int b = tid; b < nBins; b += kBlock) mine[b] = PS[b];
         }
         // Release / acquire by ONE thread per workgroup, the barriers carrying the other threads' accesses along: an agent-scope release is a write-back
         // of the XCD's whole L2 -- executed by every wave of every workgroup (`__threadfence()` in all threads, the portable idiom) it made every level
@@ -1606,7 +1622,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
             __syncthreads();
             goto restart;
         }
-        for (int b = tid; b < nBins; b += kOctBlock) {
+        for (int b = tid; b < nBins; b += kBlock) {
             int v = PS[b];
             for (int q = 0; q < parts - 1; q++) v += gh[(long long) q * histBins + b];
             PS[b] = v;
@@ -1620,8 +1636,15 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         block_scan_array(PS, nBins, s_tmp);        // exclusive: PS[b] = candidates in front of bin b in path-key order
         if (tid == 0) PS[nBins] = M;
         __syncthreads();
-    } else
-        block_radix_sort(key0, val0, key1, val1, M, g.keyBits, histT, s_tmp, &skeys, &svals);
+    } else {
+        block_radix_sort<kBlock / 64>(key0, val0, key1, val1, M, g.keyBits, histT, s_tmp, &skeys, &svals);
+        if (inLds && candB && skeys == key1) {   // (uniform) an odd number of passes ended over the node arrays: back to the first buffer
+            for (int i = tid; i < M; i += kBlock) { key0[i] = key1[i]; val0[i] = val1[i]; }
+            __syncthreads();
+            skeys = key0;
+            svals = val0;
+        }
+    }
     OSTAMP(3);
     // child boundaries of the node (lo, cnt, dep): a_c = first position in [lo, lo + cnt] whose child digit is >= c
     auto bounds = [&](int lo, int cnt, int dep, int *a1, int *a2, int *a3) {
@@ -1755,7 +1778,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
             // -- full pass (:588-640): every node with more than one point is divided
             int totK, totE, totS;
             const int nxt = cur ^ 1;
-            for (int i = tid; i < n; i += kOctBlock) {
+            for (int i = tid; i < n; i += kBlock) {
                 const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[i];
                 int k = 0, e = 0;
                 if (cnt > 1) {
@@ -1771,7 +1794,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
             }
             __syncthreads();
             block_scan_array3(S.kArr, S.eArr, S.sArr, n, s_tmp64, &totK, &totE, &totS);
-            for (int i = tid; i < n; i += kOctBlock) {
+            for (int i = tid; i < n; i += kBlock) {
                 const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[i], lo = (cur ? S.nlo[1] : S.nlo[0])[i], dep = (cur ? S.ndep[1] : S.ndep[0])[i];
                 emit(nxt, lo, cnt, dep, cnt > 1 ? S.b1[i] : 0, cnt > 1 ? S.b2[i] : 0, cnt > 1 ? S.b3[i] : 0, S.kArr[i], S.eArr[i], S.sArr[i], totK);
             }
@@ -1793,22 +1816,22 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
                 while ((1 << seqBits) < max(nE, 2)) seqBits++;
                 int cntBits = 1;
                 while ((1 << cntBits) <= M) cntBits++;
-                for (int j = tid; j < nE; j += kOctBlock) {
+                for (int j = tid; j < nE; j += kBlock) {
                     S.sk[0][j] = ((unsigned) S.Ecnt[j] << seqBits) | (unsigned) j;
                     S.sv[0][j] = (unsigned) j;
                 }
-                for (int j = tid; j < n; j += kOctBlock) S.flag[j] = 0;
+                for (int j = tid; j < n; j += kBlock) S.flag[j] = 0;
                 if (tid == 0) s_cut = nE - 1;
                 __syncthreads();
                 unsigned *ek, *ev;
-                if (nE <= kOctBlock) {
+                if (nE <= kBlock) {
                     // a few hundred distinct keys (they carry the creation sequence): the position of a key is the number of smaller keys -- counted off
                     // LDS reads, no histogram, no scan, ONE barrier (the radix sort: three passes of four).  T = 1 .. 16 adjacent lanes share a key, each
                     // counting a quarter-aligned slice of the list with 16-byte reads: one thread per key reading word by word made a round of 512
                     // expandable nodes 8192 wave-wide LDS reads -- 14 of the 22 us of a 1920x1080 level's only expand round.
                     // (launches of many frames have other workgroups to fill the wait: there one thread per key issues the fewest instructions)
                     int tl = 0;
-                    while (gridDim.y <= 16 && tl < 4 && (nE << (tl + 1)) <= kOctBlock) tl++;
+                    while (gridDim.y <= 16 && tl < 4 && (nE << (tl + 1)) <= kBlock) tl++;
                     const int T = 1 << tl, j = tid >> tl, sub = tid & (T - 1);
                     const bool vec = (((unsigned) (uintptr_t) S.sk[0]) & 15u) == 0;   // (LDS offset; the host rounds the list capacity to a multiple of 4)
                     unsigned key = 0;
@@ -1836,9 +1859,9 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
                     ek = S.sk[1];
                     ev = S.sv[1];
                 } else
-                    block_radix_sort(S.sk[0], S.sv[0], S.sk[1], S.sv[1], nE, seqBits + cntBits, histT, s_tmp, &ek, &ev);
+                    block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], nE, seqBits + cntBits, histT, s_tmp, &ek, &ev);
                 // processing order j: descending (size, creation seq)
-                for (int j = tid; j < nE; j += kOctBlock) {
+                for (int j = tid; j < nE; j += kBlock) {
                     const int e = (int) ev[nE - 1 - j];
                     const int pos = S.Epos[e];
                     const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[pos], lo = (cur ? S.nlo[1] : S.nlo[0])[pos];
@@ -1851,7 +1874,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
                 }
                 __syncthreads();
                 block_scan_array(S.kArr, nE, s_tmp);  // exclusive growth before j
-                for (int j = tid; j < nE; j += kOctBlock) {
+                for (int j = tid; j < nE; j += kBlock) {
                     const int e = (int) ev[nE - 1 - j];
                     const int pos = S.Epos[e];
                     const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[pos], lo = (cur ? S.nlo[1] : S.nlo[0])[pos];
@@ -1864,7 +1887,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
                 __syncthreads();
                 const int nProc = s_cut + 1;
                 // nodes j >= nProc are not expanded: no children, no new expandable entries
-                for (int j = tid; j < nE; j += kOctBlock) {
+                for (int j = tid; j < nE; j += kBlock) {
                     if (j >= nProc) S.eArr[j] = 0;
                     else S.flag[S.Epos[(int) ev[nE - 1 - j]]] = 1;
                 }
@@ -1884,11 +1907,11 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
                     totC = S.kArr[jl] + jl + k;
                 }
                 // unprocessed old nodes keep their order behind the new children
-                for (int i = tid; i < n; i += kOctBlock) S.sArr[i] = 1 - S.flag[i];
+                for (int i = tid; i < n; i += kBlock) S.sArr[i] = 1 - S.flag[i];
                 __syncthreads();
                 block_scan_array(S.sArr, n, s_tmp);
                 const int nxt2 = cur ^ 1;
-                for (int i = tid; i < n; i += kOctBlock) {
+                for (int i = tid; i < n; i += kBlock) {
                     if (!S.flag[i]) {
                         const int p = totC + S.sArr[i];
                         (nxt2 ? S.nlo[1] : S.nlo[0])[p] = (cur ? S.nlo[1] : S.nlo[0])[i]; (nxt2 ? S.ncnt[1] : S.ncnt[0])[p] = (cur ? S.ncnt[1] : S.ncnt[0])[i]; (nxt2 ? S.ndep[1] : S.ndep[0])[p] = (cur ? S.ndep[1] : S.ndep[0])[i];
@@ -1897,7 +1920,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
                 // new expandable list goes to the sort buffers first (Epos/Ecnt are still being read)
                 unsigned *nEpos = (ek == S.sk[0]) ? S.sk[1] : S.sk[0];
                 unsigned *nEcnt = (ev == S.sv[0]) ? S.sv[1] : S.sv[0];
-                for (int j = tid; j < nProc; j += kOctBlock) {
+                for (int j = tid; j < nProc; j += kBlock) {
                     const int e = (int) ev[nE - 1 - j];
                     const int pos = S.Epos[e];
                     const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[pos], lo = (cur ? S.nlo[1] : S.nlo[0])[pos], dep = (cur ? S.ndep[1] : S.ndep[0])[pos];
@@ -1919,7 +1942,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
                     }
                 }
                 __syncthreads();
-                for (int j = tid; j < totE2; j += kOctBlock) { S.Epos[j] = (int) nEpos[j]; S.Ecnt[j] = (int) nEcnt[j]; }
+                for (int j = tid; j < totE2; j += kBlock) { S.Epos[j] = (int) nEpos[j]; S.Ecnt[j] = (int) nEcnt[j]; }
                 __syncthreads();
                 cur = nxt2;
                 n = totC + (n - nProc);
@@ -1944,7 +1967,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
     const int lane = lane_id(), wave = wave_id();
     if (kHist && useHist) {
         // first bin and log2 of the bin count of every final node (PS is still the prefix table)
-        for (int i = tid; i < n; i += kOctBlock) {
+        for (int i = tid; i < n; i += kBlock) {
             const int lo = (cur ? S.nlo[1] : S.nlo[0])[i], sh = 2 * (dm - (cur ? S.ndep[1] : S.ndep[0])[i]);
             int a = 0, b = nBins >> sh;
             while (b - a > 1) {
@@ -1957,7 +1980,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         }
         __syncthreads();
         // bin -> final node, written over the prefix table (sixteen lanes per node; bins outside every node hold no candidate)
-        for (int i0 = wave * 4; i0 < n; i0 += (kOctBlock / 64) * 4) {
+        for (int i0 = wave * 4; i0 < n; i0 += (kBlock / 64) * 4) {
             const int i = i0 + (lane >> 4), sl16 = lane & 15;
             if (i < n) {
                 const int f0 = S.b1[i], len = 1 << S.b2[i];
@@ -1967,20 +1990,20 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         __syncthreads();
         // the candidates once more, linearly: best (score, then smallest index) per node
         constexpr int kFU = 4;   // (every load of a round in flight before the first LDS operation: 60 dependent global round trips per thread were 40 us of a 3840x2160 level)
-        for (int i0 = tid; i0 < M; i0 += kFU * kOctBlock) {
+        for (int i0 = tid; i0 < M; i0 += kFU * kBlock) {
             unsigned w[kFU];
 #pragma unroll
-            for (int u = 0; u < kFU; u++) w[u] = key0[min(i0 + u * kOctBlock, M - 1)];
+            for (int u = 0; u < kFU; u++) w[u] = key0[min(i0 + u * kBlock, M - 1)];
 #pragma unroll
             for (int u = 0; u < kFU; u++) {
-                const int i = i0 + u * kOctBlock;
+                const int i = i0 + u * kBlock;
                 const int node = i < M ? PS[w[u] & 0xFFFFu] : -2 - lane;
                 const unsigned v = row_run_max(node, ((w[u] >> 16) << 24) | (0xFFFFFFu - (unsigned) i));
                 if (node >= 0 && row_run_last(node)) atomicMax((unsigned *) &S.kArr[node], v);
             }
         }
     } else
-    for (int i0 = wave * 4; i0 < n; i0 += (kOctBlock / 64) * 4) {   // sixteen lanes (a DPP row) per node: arg-max over its range (LDS / DPP only);
+    for (int i0 = wave * 4; i0 < n; i0 += (kBlock / 64) * 4) {   // sixteen lanes (a DPP row) per node: arg-max over its range (LDS / DPP only);
         const int i = i0 + (lane >> 4), sl16 = lane & 15;           // the final nodes hold ~10 candidates each
         const bool ok = i < n;
         const int lo = ok ? (cur ? S.nlo[1] : S.nlo[0])[i] : 0, cnt = ok ? (cur ? S.ncnt[1] : S.ncnt[0])[i] : 0;
@@ -1993,7 +2016,7 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         if (ok && sl16 == 0) S.kArr[i] = (int) best;
     }
     __syncthreads();
-    for (int i = tid; i < n; i += kOctBlock) {         // a thread per node: the dependent global read of the winner's position, all in flight at once
+    for (int i = tid; i < n; i += kBlock) {         // a thread per node: the dependent global read of the winner's position, all in flight at once
         const unsigned best = (unsigned) S.kArr[i];
         const unsigned idx = 0xFFFFFFu - (best & 0xFFFFFFu);
         const unsigned p = xy[idx];
@@ -2012,12 +2035,12 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         // (launches of a few frames -- one Tracking frame -- keep the list order: the sort buys cache locality across many frames' windows and
         // costs two block-wide passes of its own)
         unsigned *ok = S.sk[0], *ov = S.sv[0];
-        if (gridDim.y > 4) block_radix_sort(S.sk[0], S.sv[0], S.sk[1], S.sv[1], n, 12, histT, s_tmp, &ok, &ov);
+        if (gridDim.y > 4) block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], n, 12, histT, s_tmp, &ok, &ov);
         // k_describe's work list: processing position i -> (x | y << 16, score | list position << 8) in ONE record, so that a describe wave
         // knows its keypoint after a single memory round trip (it used to follow procOrder -> position / score: two dependent ones)
         // (score | list position << 8 | level << 24; positions past the level's count carry kNoKeypoint so that the wave there leaves at once)
         uint2 *pr = procRec + (long long) f * kpStride + g.kpBase;
-        for (int i = tid; i < g.kpCap; i += kOctBlock) {
+        for (int i = tid; i < g.kpCap; i += kBlock) {
             if (i < n) {
                 const unsigned li = ov[i];
                 pr[i] = make_uint2((unsigned) S.b1[li], (unsigned) S.b2[li] | (li << 8) | ((unsigned) l << 24));
@@ -2690,37 +2713,58 @@ void launch_fast_tab_persist(hipStream_t st, const FrameSet &fs, const FastCellR
 }
 
 size_t octree_lds_bytes(int maxCellsPerLevel, int cap, int ldsCand, bool globalNodes) {
-    return sizeof(int) * ((size_t) maxCellsPerLevel + 1 + 3 + (globalNodes ? 0 : 19 * (size_t) cap) + 4 * (size_t) ldsCand);
+    if (globalNodes) return sizeof(int) * ((size_t) maxCellsPerLevel + 1 + 3 + 4 * (size_t) ldsCand);
+    // (k_octree: the candidates' second sort buffer lies over the cell table and the node arrays, the first one behind them)
+    const size_t region = (((size_t) maxCellsPerLevel + 1 + 3) & ~(size_t) 3) + 19 * (size_t) cap;
+    return sizeof(int) * (std::max(region, 2 * (size_t) ldsCand) + 2 * (size_t) ldsCand);
+}
+
+int octree_lds_cand(int maxCellsPerLevel, int cap, size_t budget) {
+    const long long region = (((long long) maxCellsPerLevel + 1 + 3) & ~3ll) + 19ll * cap, ints = (long long) (budget / sizeof(int));
+    long long c = ints / 4;                              // the second buffer wider than the region it lies over
+    if (2 * c < region) c = (ints - region) / 2;         // ... or inside it
+    c &= ~3ll;
+    return c < 256 ? 0 : (int) std::min(c, 8192ll);
 }
 
 size_t octree_hist_lds_bytes(int regionInts, int histBins) { return sizeof(int) * ((size_t) regionInts + (size_t) histBins + 1); }
 
 hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist) {
-    constexpr int kOctMaxDyn = 160 * 1024 - 10 * 1024;   // the kernel's static LDS (radix histogram, scan scratch) is ~8.5 KB
-    if (hist) return hipFuncSetAttribute((const void *) k_octree<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
-    return globalNodes ? hipFuncSetAttribute((const void *) k_octree<true, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn)
-                       : hipFuncSetAttribute((const void *) k_octree<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
+    constexpr int kOctMaxDyn = 160 * 1024 - 10 * 1024;   // the kernel's static LDS (radix histogram, scan scratch) is ~8.5 KB at 1024 threads
+    if (hist) return hipFuncSetAttribute((const void *) k_octree<false, true, kOctBlock>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
+    if (globalNodes) return hipFuncSetAttribute((const void *) k_octree<true, false, kOctBlock>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
+    hipError_t e = hipFuncSetAttribute((const void *) k_octree<false, false, 1024>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *) k_octree<false, false, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
+    if (e == hipSuccess) e = hipFuncSetAttribute((const void *) k_octree<false, false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
+    return e;
 }
 
 // levels [level0, level0 + nLaunchLevels) of every frame; histBins > 0 selects the histogram plan (regionInts ints shared by the cell table, the
-// key tables and the node arrays, then histBins + 1 ints of prefix table)
+// key tables and the node arrays, then histBins + 1 ints of prefix table).  block: threads per workgroup of the sort plan with LDS node arrays
+// (1024, 512 or 256); the other two plans run 1024.
 void launch_octree(hipStream_t st, const LevelGeom *dGeom, int nlevels, int level0, int nLaunchLevels, const unsigned short *cellCnt, const unsigned *slots,
                    int totalCells, long long totalSlots, unsigned *k0, unsigned *v0, unsigned *k1, unsigned *v1, unsigned *xy,
                    long long candStride, unsigned *lvlKpXY, unsigned char *lvlKpScore, int *lvlKpCnt, int *lvlCandCnt,
                    uint2 *procRec, int kpStride, int cap, int ldsCand, size_t ldsBytes, int nFrames, long long *dbg, int *nodeArena,
-                   int regionInts, int histBins, int helpers, int *gHist, int *gDone, int doneTarget, int spinBudget) {
+                   int regionInts, int histBins, int helpers, int *gHist, int *gDone, int doneTarget, int spinBudget, int block) {
     if (histBins > 0)
-        hipLaunchKernelGGL((k_octree<false, true>), dim3(nLaunchLevels, nFrames, helpers > 1 && gHist ? helpers : 1), dim3(kOctBlock), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells,
+        hipLaunchKernelGGL((k_octree<false, true, kOctBlock>), dim3(nLaunchLevels, nFrames, helpers > 1 && gHist ? helpers : 1), dim3(kOctBlock), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells,
                            totalSlots, k0, v0, k1, v1, xy, candStride, lvlKpXY, lvlKpScore, lvlKpCnt, lvlCandCnt, procRec, kpStride, cap, 0,
                            dbg, nullptr, regionInts, histBins, helpers > 1 ? gHist : nullptr, gDone, doneTarget, spinBudget);
     else if (nodeArena)
-        hipLaunchKernelGGL((k_octree<true, false>), dim3(nLaunchLevels, nFrames), dim3(kOctBlock), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells,
+        hipLaunchKernelGGL((k_octree<true, false, kOctBlock>), dim3(nLaunchLevels, nFrames), dim3(kOctBlock), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells,
                            totalSlots, k0, v0, k1, v1, xy, candStride, lvlKpXY, lvlKpScore, lvlKpCnt, lvlCandCnt, procRec, kpStride, cap, ldsCand,
                            dbg, nodeArena, 0, 0, nullptr, nullptr, 0, 0);
-    else
-        hipLaunchKernelGGL((k_octree<false, false>), dim3(nLaunchLevels, nFrames), dim3(kOctBlock), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells,
-                           totalSlots, k0, v0, k1, v1, xy, candStride, lvlKpXY, lvlKpScore, lvlKpCnt, lvlCandCnt, procRec, kpStride, cap, ldsCand,
-                           dbg, nodeArena, 0, 0, nullptr, nullptr, 0, 0);
+    else {
+#define YGZF_OCT_SORT_LAUNCH(B)                                                                                                                      \
+        hipLaunchKernelGGL((k_octree<false, false, B>), dim3(nLaunchLevels, nFrames), dim3(B), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells, \
+                           totalSlots, k0, v0, k1, v1, xy, candStride, lvlKpXY, lvlKpScore, lvlKpCnt, lvlCandCnt, procRec, kpStride, cap, ldsCand,   \
+                           dbg, nodeArena, 0, 0, nullptr, nullptr, 0, 0)
+        if (block == 256) YGZF_OCT_SORT_LAUNCH(256);
+        else if (block == 512) YGZF_OCT_SORT_LAUNCH(512);
+        else YGZF_OCT_SORT_LAUNCH(1024);
+#undef YGZF_OCT_SORT_LAUNCH
+    }
 }
 
 void launch_describe(hipStream_t st, const FrameSet &fs, const LevelGeom *dGeom, int nlevels, const int *lvlKpCnt, int *lvlBase,

@@ -81,13 +81,15 @@ void launch_fast_tab_persist(hipStream_t st, const FrameSet &fs, const FastCellR
                              unsigned *stats, unsigned *counters, int nWorkgroups);
 constexpr int kFastStatWords = 8 * 64;   // `stats`: 64 x {cells sampled, cells whose keypoints are FAST(minTh)'s, score rounds beyond the first, plan: 1 one pass / 2 iniTh first, corner-bearing quads, quads, -, pass-1 runs}
 size_t octree_lds_bytes(int maxCellsPerLevel, int cap, int ldsCand, bool globalNodes);
+int octree_lds_cand(int maxCellsPerLevel, int cap, size_t budget);   // the sort plan's candidate budget within `budget` bytes of LDS node arrays + buffers (0: < 256)
 size_t octree_hist_lds_bytes(int regionInts, int histBins);
 hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist);
 void launch_octree(hipStream_t st, const LevelGeom *dGeom, int nlevels, int level0, int nLaunchLevels, const unsigned short *cellCnt, const unsigned *slots,
                    int totalCells, long long totalSlots, unsigned *k0, unsigned *v0, unsigned *k1, unsigned *v1, unsigned *xy,
                    long long candStride, unsigned *lvlKpXY, unsigned char *lvlKpScore, int *lvlKpCnt, int *lvlCandCnt,
                    uint2 *procRec, int kpStride, int cap, int ldsCand, size_t ldsBytes, int nFrames, long long *dbg, int *nodeArena,
-                   int regionInts, int histBins, int helpers = 1, int *gHist = nullptr, int *gDone = nullptr, int doneTarget = 0, int spinBudget = 0);
+                   int regionInts, int histBins, int helpers = 1, int *gHist = nullptr, int *gDone = nullptr, int doneTarget = 0, int spinBudget = 0,
+                   int block = kOctBlock);
 constexpr int kOctDbgAlone = 16 * 8 + 16 + 16 * 16;  // per level: six phase stamps, M, n; then per level the workgroups that left the histogram plan; then per level up to 8 (list size, time) pairs of the tree passes;
 constexpr int kOctDbgAloneFrames = kOctDbgAlone + 16; // then per level the workgroups 0 that gave up waiting for their helpers (computed the level alone); then a mask of the frames (< 64) where that happened
 constexpr int kOctDbgWords = kOctDbgAloneFrames + 1;

@@ -338,6 +338,58 @@ int build_geometry(ygzf_ctx *c, int w, int h, Geometry &G) {
     return YGZF_OK;
 }
 
+// Which octree plan a geometry takes -- NOT the budgets of the launches that run.  The per-list-position arrays (19 x cap ints) stay in LDS while one
+// workgroup fits the CU; very large per-level feature budgets move them to a global arena.  ldsCand = the candidates one 1024-thread launch of all levels
+// keeps in LDS at 16 bytes each ON TOP of the cell table and node arrays (the layout before the overlay, and still the layout of the global-arena
+// launch): no such budget (or the global arena) -> the histogram plan.  This formula is kept as the plan choice's yardstick so that which geometries
+// take the sort plan (and with it every hist-plan workload) stays where it was; it also sizes the one launch of the global-arena plan
+// (c->octLdsCand / c->octLds).  The launches of the sort plan with LDS node arrays take plan_oct_sort's budgets (octree_lds_cand: the second sort
+// buffer over the node arrays) -- a change to one formula does not move the other.
+static void oct_sort_budget(const Geometry &G, bool *globalNodes, int *ldsCand) {
+    *globalNodes = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, 0, false) > 142 * 1024;
+    const size_t fixed = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, 0, *globalNodes);
+    const size_t budget = (size_t) 71 * 1024;   // two workgroups per CU beside 9 KB of static LDS each (radix histogram)
+    *ldsCand = fixed + 16 * 256 < budget ? (int) ((budget - fixed) / 16) : 0;
+    if (*ldsCand > 8192) *ldsCand = 8192;
+}
+
+// The sort plan's launches.  Two 1024-thread workgroups of k_octree fill a CU's 32 wave slots whatever their LDS, so a level in such a workgroup
+// leaves nothing beside it for the other contexts' FAST and describe waves.  Consecutive levels are launched together while their list caps stay
+// within a factor of two of the group's first level; a group whose lists hold more than 256 nodes keeps 1024 threads and 71 KB, one of more than
+// 128 nodes takes 512 threads and 44 KB, the rest 256 threads and 36 KB.  The candidates fit those budgets at 16 bytes each because their second sort
+// buffer lies over the node arrays (k_octree): 2800 / 2300 of them -- what the levels of a 752x480 frame hold (up to ~2700 per level on the
+// synthetic clip); a level that holds more sorts through global memory, same result.
+std::vector<OctSortGroup> ygzf::plan_oct_sort(const Geometry &G, int L, bool oneGroup, int block, size_t ldsBytes) {
+    std::vector<OctSortGroup> out;
+    auto finish = [&](OctSortGroup grp, int cells) {
+        if (grp.cap < 4) grp.cap = 4;
+        const int b = block == 256 || block == 512 || block == 1024 ? block : grp.block;
+        grp.block = b;
+        const size_t budget = ldsBytes ? ldsBytes : (size_t) (b == 1024 ? 71 : b == 512 ? 44 : 36) * 1024;
+        grp.ldsCand = octree_lds_cand(cells, grp.cap, budget);
+        grp.lds = octree_lds_bytes(cells, grp.cap, grp.ldsCand, false);
+        out.push_back(grp);
+    };
+    if (oneGroup) {
+        OctSortGroup grp;
+        grp.l0 = 0; grp.n = L; grp.cap = G.kpCapMax; grp.block = kOctBlock;
+        finish(grp, G.maxCellsPerLevel);
+        return out;
+    }
+    for (int l = 0; l < L;) {
+        OctSortGroup grp;
+        grp.l0 = l;
+        int cells = 0;
+        for (; l < L && (grp.n == 0 || 2 * G.lv[l].kpCap > G.lv[grp.l0].kpCap); l++, grp.n++) {
+            grp.cap = std::max(grp.cap, (G.lv[l].kpCap + 3) & ~3);
+            cells = std::max(cells, G.lv[l].nCols * G.lv[l].nRows);
+        }
+        grp.block = grp.cap > 256 ? 1024 : grp.cap > 128 ? 512 : 256;
+        finish(grp, cells);
+    }
+    return out;
+}
+
 int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
     if (w < 1 || h < 1) return fail(c, YGZF_ERR_INVALID, "image size %dx%d", w, h);
     if (w > c->maxW || h > c->maxH) return fail(c, YGZF_ERR_INVALID, "image %dx%d exceeds the context maximum %dx%d", w, h, c->maxW, c->maxH);
@@ -400,17 +452,13 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
         rc = ensure(c, c->dFastCells, std::max<size_t>(G.fastCells.size() * sizeof(FastCellRec), 32));
         if (rc) return rc;
         if (!G.fastCells.empty()) HIPCHECK(c, hipMemcpy(c->dFastCells.p, G.fastCells.data(), G.fastCells.size() * sizeof(FastCellRec), hipMemcpyHostToDevice));
-        // LDS-resident candidate sort buffers: as many as keep two workgroups per CU (<= ~78 KB each)
-        {
-            // per-list-position arrays (19 x cap ints) stay in LDS while one workgroup fits the CU; very large per-level feature budgets
-            // move them to a global arena
-            c->octGlobalNodes = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, 0, false) > 142 * 1024;
-            const size_t fixed = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, 0, c->octGlobalNodes);
-            const size_t budget = (size_t) 71 * 1024;   // two workgroups per CU beside 9 KB of static LDS each (radix histogram); 48 / 36 / 24 KB measured slower (profiles/r05_f_octree_lds_and_streams.txt)
-            c->octLdsCand = fixed + 16 * 256 < budget ? (int) ((budget - fixed) / 16) : 0;
-            if (c->octLdsCand > 8192) c->octLdsCand = 8192;
-        }
+        oct_sort_budget(G, &c->octGlobalNodes, &c->octLdsCand);
         c->octLds = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, c->octLdsCand, c->octGlobalNodes);
+        // the sort plan's launches with LDS node arrays: level groups of their own workgroup size and LDS (YGZF_FORCE=oct_groups=1: one launch of all
+        // levels; oct_block / oct_lds_kb pin the size / the LDS of every launch)
+        c->octSortGroups.clear();
+        if (!c->octGlobalNodes && c->octLdsCand > 0)
+            c->octSortGroups = plan_oct_sort(G, L, forced("oct_groups", 0) == 1, (int) forced("oct_block", 0), (size_t) forced("oct_lds_kb", 0) * 1024);
         // Levels too large for LDS-resident candidate buffers (1920x1080 / 4000 and up) take the histogram plan: no sort, tree passes in LDS
         // (extract_kernels.hip, k_octree<.., kHist>).  Consecutive levels are launched together while their list caps stay within a factor of two of
         // the group's first level, so that the small levels do not reserve the LDS of the large ones.
@@ -676,6 +724,7 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
             HIPCHECK(c, hipMemsetAsync(odbg, 0, kOctDbgWords * sizeof(long long), c->stream));
         }
         int smallHelpers = 0;   // workgroups per (level, frame) of the small plan's launch (0: another plan)
+        bool sortGroups = false;   // the sort plan's level groups ran (c->octSortGroups)
         {
             hipStream_t so = c->stream;
             ProfScope ps(c, KK_OCTREE, so);
@@ -715,6 +764,15 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
                               (unsigned char *) c->dLvlScore.p, (int *) c->dLvlCnt.p, (int *) c->dLvlCand.p,
                               (uint2 *) c->dProcOrder.p, G.kpStride, grp.cap, 0, grp.lds, nFrames, odbg, nullptr, grp.regionInts, grp.histBins,
                               helpers, gHist, gDone, c->octDoneTarget, c->octHelperSpin);
+            } else if (c->octGroups.empty() && !c->octSortGroups.empty()) {
+                sortGroups = true;
+                for (const auto &grp : c->octSortGroups)
+                    launch_octree(so, dGeom, L, grp.l0, grp.n, (const unsigned short *) c->dCellCnt.p, (const unsigned *) c->dSlots.p,
+                                  G.totalCells, G.totalSlots, (unsigned *) c->dK0.p, (unsigned *) c->dV0.p, (unsigned *) c->dK1.p,
+                                  (unsigned *) c->dV1.p, (unsigned *) c->dXY.p, G.candStride, (unsigned *) c->dLvlXY.p,
+                                  (unsigned char *) c->dLvlScore.p, (int *) c->dLvlCnt.p, (int *) c->dLvlCand.p,
+                                  (uint2 *) c->dProcOrder.p, G.kpStride, grp.cap, grp.ldsCand, grp.lds, nFrames, odbg, nullptr, 0, 0,
+                                  1, nullptr, nullptr, 0, 0, grp.block);
             } else if (c->octGroups.empty())
                 launch_octree(so, dGeom, L, 0, L, (const unsigned short *) c->dCellCnt.p, (const unsigned *) c->dSlots.p,
                               G.totalCells, G.totalSlots, (unsigned *) c->dK0.p, (unsigned *) c->dV0.p, (unsigned *) c->dK1.p,
@@ -749,6 +807,12 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
                 for (const auto &grp : c->octGroups) fprintf(stderr, " levels %d-%d cap %d bins %d lds %zu;", grp.l0, grp.l0 + grp.n - 1, grp.cap, grp.histBins, grp.lds);
                 fprintf(stderr, " workgroups of %d frames that fell back to the sort, per level:", nFrames);
                 for (int l = 0; l < L; l++) fprintf(stderr, " %lld", st[16 * 8 + l]);
+                fprintf(stderr, "]\n");
+            }
+            if (sortGroups) {   // (a level of frame 0 whose M above exceeds its launch's candidate budget sorted through global memory)
+                fprintf(stderr, "[ygzf octree sort plan: %zu launches;", c->octSortGroups.size());
+                for (const auto &grp : c->octSortGroups)
+                    fprintf(stderr, " levels %d-%d threads %d cap %d candidates %d lds %zu;", grp.l0, grp.l0 + grp.n - 1, grp.block, grp.cap, grp.ldsCand, grp.lds);
                 fprintf(stderr, "]\n");
             }
             if (smallHelpers) {
@@ -1073,6 +1137,28 @@ int ygzf_pyramid_plan_host(const ygzf_extractor_cfg *cfg, int w, int h, int *n_s
             }
     }
     return YGZF_OK;
+}
+
+int ygzf_octree_sort_plan_host(const ygzf_extractor_cfg *cfg, int w, int h, int *groups, int groups_cap) {
+    if (!cfg || cfg->nlevels < 1 || cfg->nlevels > kMaxLevels || cfg->nfeatures < 0 || !(cfg->scale_factor > 1.0f) || w < 1 || h < 1) return YGZF_ERR_INVALID;
+    ygzf_ctx tmp;
+    tmp.tab.init(*cfg);
+    Geometry G;
+    const int rc = build_geometry(&tmp, w, h, G);
+    if (rc) return rc;
+    bool globalNodes = false;
+    int ldsCand = 0;
+    oct_sort_budget(G, &globalNodes, &ldsCand);
+    if (globalNodes || ldsCand == 0) return 0;
+    const std::vector<OctSortGroup> grp = plan_oct_sort(G, cfg->nlevels, false, 0, 0);
+    if (groups) {
+        if (groups_cap < (int) grp.size() * 6) return YGZF_ERR_INVALID;
+        for (size_t i = 0; i < grp.size(); i++) {
+            int *o = groups + 6 * i;
+            o[0] = grp[i].l0; o[1] = grp[i].n; o[2] = grp[i].block; o[3] = grp[i].cap; o[4] = grp[i].ldsCand; o[5] = (int) grp[i].lds;
+        }
+    }
+    return (int) grp.size();
 }
 
 int ygzf_pyramid_plan_base_host(const ygzf_extractor_cfg *cfg, int w, int h) {

@@ -49,6 +49,12 @@ struct Geometry {
     int kpStride = 0, kpCapMax = 0;
 };
 
+// One launch of k_octree's sort plan (node arrays in LDS): levels [l0, l0 + n), `block` threads per workgroup, list capacity `cap`, candidate
+// budget `ldsCand` (more candidates sort through global memory), `lds` bytes of dynamic LDS.
+struct OctSortGroup { int l0 = 0, n = 0, block = kOctBlock, cap = 0, ldsCand = 0; size_t lds = 0; };
+// oneGroup: all levels in one launch of kOctBlock threads (YGZF_FORCE=oct_groups=1); block > 0 / ldsBytes > 0 pin every launch's workgroup / LDS
+YGZF_HIDDEN std::vector<OctSortGroup> plan_oct_sort(const Geometry &G, int L, bool oneGroup, int block, size_t ldsBytes);
+
 }  // namespace ygzf
 
 using namespace ygzf;
@@ -98,13 +104,14 @@ struct ygzf_ctx {
     std::vector<unsigned char> alKey;   // cache key of the uploaded SiaLevel tables
     int identityPoses = 0;
     void *identityPosesPtr = nullptr;
-    size_t octLds = 0;
+    size_t octLds = 0;         // one launch of all levels (the global-arena sort plan); the plan choice (oct_sort_budget) -- not the budgets of octSortGroups
     int octLdsCand = 0;
     bool octGlobalNodes = false;
     // histogram plan of the octree (levels with tens of thousands of candidates): launches of consecutive levels, each with its own LDS allotment
     struct OctGroup { int l0 = 0, n = 0, cap = 0, regionInts = 0, histBins = 0; size_t lds = 0; };
     std::vector<OctGroup> octGroups;
     OctGroup octSmall;                     // all levels in ONE histogram-plan launch: launches of a few frames (see run_extract)
+    std::vector<OctSortGroup> octSortGroups;   // sort plan with LDS node arrays: its launches (plan_oct_sort)
     bool haveOctSmall = false;
     bool carryOff = false;     // ygzf_set_carry_previous(0): extractions do not carry the previous batch's last frame into slot 0
     struct OctHistLayout {     // what dOctHist's hand-over counters were last cleared for (k_octree's helper workgroups)

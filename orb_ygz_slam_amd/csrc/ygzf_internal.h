@@ -20,7 +20,7 @@ constexpr int kBorder = kEdgeThreshold - 3;  // minBorderX of ComputeKeyPointsOc
 constexpr int kMaxLevels = 16;
 constexpr int kMaxCellWin = 66;       // window side of one FAST cell: wCell(<60)+6
 constexpr int kFastBlock = 256;   // 4 waves (cell positions) per workgroup; single-wave workgroups measured slower: 739 vs 625 us per 256 frames
-constexpr int kOctBlock = 1024;   // threads per (level, frame) workgroup of k_octree (512 / 256 measured: no schedule effect, profiles/r05_f_octree_block_sweep.txt)
+constexpr int kOctBlock = 1024;   // threads per (level, frame) workgroup of k_octree's histogram plan and of its sort plan's largest levels (the sort plan's smaller levels: 512 / 256, plan_oct_sort)
 // The dynamic-LDS ceiling of a kernel is a per-process attribute of the function: it is always set to the same value (the CU's 160 KB
 // minus room for static LDS), never to a per-call size, so that contexts used from different threads cannot lower it under each other.
 constexpr int kMaxDynLds = 160 * 1024 - 2048;
