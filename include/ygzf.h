@@ -381,6 +381,14 @@ int ygzf_match_counts(ygzf_ctx *ctx, int *nmatches /* n_frames ints */);
  * extensions -- identical matches, but a crowded frame (th = 5 after relocalisation, thousands of features) silently loses the speed-up;
  * bench.py prints it.  Synchronises the context. */
 int ygzf_match_fallbacks(ygzf_ctx *ctx, unsigned *pairs);
+/* The same counter split by cause, and the rare paths that do not end in a hand-over, summed over every matcher launch of this context so
+ * far (SearchByProjection in its three forms, SearchForInitialization, ygzf_match_batch_prev):
+ *   stats[0] pairs handed to the one-wave pass (= ygzf_match_fallbacks)     stats[1] ... because the fixpoint reached its round cap
+ *   stats[2] ... because a query needed a third list extension or the launch's extension slots were used up
+ *   stats[3] list extensions (blocks of eight candidates) the fixpoint handed out
+ *   stats[4] full window rescans of the one-wave pass (a query whose speculative list was taken or outbid entirely)
+ * Synchronises the context. */
+int ygzf_match_path_stats(ygzf_ctx *ctx, unsigned stats[5]);
 int ygzf_match_fetch(ygzf_ctx *ctx, int frame, int *cur_match, uint8_t *cur_owner, int cap);
 /* All pairs of the last ygzf_match_batch_prev at once: row p of `match` (stride >= ygzf_max_keypoints ints per row) receives the match
  * array of pair p in full row length (entries past the frame's keypoint count are -1 or stale: read n_kp of them). */

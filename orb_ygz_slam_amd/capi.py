@@ -458,6 +458,13 @@ class Extractor:
         self._ck(self.L.ygzf_match_fallbacks(self.h, C.byref(n)))
         return n.value
 
+    def match_path_stats(self):
+        """the matcher's rare paths since the context was created (include/ygzf.h: ygzf_match_path_stats) -> dict"""
+        s = (C.c_uint * 5)()
+        self.L.ygzf_match_path_stats.argtypes = [C.c_void_p, C.c_void_p]
+        self._ck(self.L.ygzf_match_path_stats(self.h, s))
+        return dict(zip(("fallbacks", "round_cap", "ext_room", "ext_blocks", "rescans"), (int(v) for v in s)))
+
     def match_fetch(self, frame):
         w, h, _ = self._wh
         cap = self.max_keypoints(w, h)

@@ -156,8 +156,15 @@ struct MatchArgs {
     int split;
     int *splitCnt;                 // one counter per pair, zero between launches (the last workgroup resets it)
     unsigned char *splitX;         // kMatchSplitRec * capLast bytes per pair
-    unsigned *serialFallbacks;     // nullable: counts the pairs whose in-order resolution fell back from the block-wide fixpoint to the one-wave pass
+    unsigned *matchStat;     // nullable: the context's matcher counters (kMatchStat*); [0] counts the pairs whose in-order resolution fell back
+                                   // from the block-wide fixpoint to the one-wave pass
 };
+// The words of MatchArgs::matchStat (ygzf_match_fallbacks reads the first, ygzf_match_path_stats the five): pairs handed to the one-wave
+// pass, of which: out of rounds / out of extension room (a third block for one query, or the 65th slot); extension blocks handed out by the
+// fixpoint; full rescans of the one-wave pass (all modes, SearchForInitialization included).  Each is written by one thread per pair and only
+// when non-zero.
+constexpr int kMatchStatFallbacks = 0, kMatchStatRoundCap = 1, kMatchStatExtRoom = 2, kMatchStatExtended = 3, kMatchStatRescans = 4, kMatchStatWords = 5;
+constexpr int kMatchCauseRounds = 1, kMatchCauseExtRoom = 2;   // why a pair left the fixpoint (k_match_last: s_tmp[15])
 constexpr int kSpillSpec = 1, kSpillMisc = 2;
 constexpr int kMatchSplitRec = 56;   // uint4 + uint4 (lists of eight) + ushort4 + ushort4 + float angle + hasObs word
 size_t match_lds_bytes(int capCur, int capLast, bool descInLds, int spill, size_t *spillBytes, bool specDeep);

@@ -794,7 +794,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
             L.extOf[2 * i] = 0xFF; L.extOf[2 * i + 1] = 0xFF;
         }
         if (tid < 4) s_tmp[16 + tid] = 0;            // [16], [17]: "a pick moved" of even / odd rounds; [18]: queries to extend; [19]: slots in use
-        if (tid == 0) s_tmp[15] = 0;                 // hand the pair to the one-wave pass
+        if (tid == 0) s_tmp[15] = 0;                 // hand the pair to the one-wave pass: kMatchCauseRounds | kMatchCauseExtRoom
         __syncthreads();
         int rounds = 0, nExtended = 0;
         for (;; rounds++) {
@@ -878,7 +878,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
             __syncthreads();
             const int nWork = min(s_tmp[18], kExtSlots);
             if (nWork == 0 && !s_tmp[16 + (rounds & 1)]) break;   // fixpoint, nobody waits for an extension (tested BEFORE the round cap: a converged state is never thrown away)
-            if (rounds >= 95) { if (tid == 0) s_tmp[15] = 1; break; }
+            if (rounds >= 95) { if (tid == 0) s_tmp[15] = kMatchCauseRounds; break; }
             if (nWork == 0) continue;                    // some pick moved: another round, on the other claim buffer
             // extensions: one wave per query; the claims play no part, so all of them at once
             for (int w = wave; w < nWork; w += kMatchBlock / 64) {
@@ -887,7 +887,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 int slot = 0;
                 if (lane == 0) slot = (blk < 2 && A.serialOrder != 2) ? atomicAdd(&s_tmp[19], 1) : kExtSlots;
                 slot = __builtin_amdgcn_readfirstlane(slot);
-                if (slot >= kExtSlots) { if (lane == 0) s_tmp[15] = 1; continue; }
+                if (slot >= kExtSlots) { if (lane == 0) s_tmp[15] = kMatchCauseExtRoom; continue; }   // a third block, or slot 65
                 unsigned afterKey;
                 if (blk == 0) afterKey = two ? L.specKeyB[qx].w : L.specKey[qx].w;
                 else afterKey = L.extKey[8 * (int) L.extOf[2 * qx] + 7];
@@ -910,7 +910,15 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
         __syncthreads();
         const bool serial = s_tmp[15] != 0;
         if (dbg && tid == 0) dbg[6] = serial ? -1 : nExtended * 1000 + rounds + 1;
-        if (serial && tid == 0 && A.serialFallbacks) atomicAdd(A.serialFallbacks, 1u);   // always on: a crowded frame that loses the fixpoint's speed shows up in the profile
+        if (tid == 0 && A.matchStat) {   // always on: a crowded frame that loses the fixpoint's speed shows up in the profile.  One thread per pair, and only
+            // what is non-zero: an ordinary frame (no extension, no hand-over) executes no atomic here
+            if (serial) {
+                atomicAdd(A.matchStat + kMatchStatFallbacks, 1u);
+                atomicAdd(A.matchStat + (s_tmp[15] == kMatchCauseRounds ? kMatchStatRoundCap : kMatchStatExtRoom), 1u);
+            }
+            const int granted = min(s_tmp[19], kExtSlots);   // extension slots handed out (the requests beyond them were refused)
+            if (granted) atomicAdd(A.matchStat + kMatchStatExtended, (unsigned) granted);
+        }
         if (serial) {
             for (int i = tid; i < nt; i += kMatchBlock) { L.claim[i] = 64; L.match[i] = -1; }
             __syncthreads();
@@ -1076,6 +1084,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
         removed = wave_sum(removed);
         nmatches -= removed;
         if (lane == 0) A.nmatches[pair] = nmatches;
+        if (lane == 0 && nRescan && A.matchStat) atomicAdd(A.matchStat + kMatchStatRescans, (unsigned) nRescan);
         return;
     }
     if (A.mode == 1) {
@@ -1330,6 +1339,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     for (int i = lane; i < nt; i += 64) { ownerOut[i] = L.owner[i]; matchOut[i] = L.match[i]; }
     if (lane == 0) A.nmatches[pair] = nmatches;
+    if (lane == 0 && nRescan && A.matchStat) atomicAdd(A.matchStat + kMatchStatRescans, (unsigned) nRescan);
     STAMP(5);
     if (dbg && tid == 0) { dbg[6] = nRescan; dbg[7] = nq; }
 #undef STAMP

@@ -39,7 +39,7 @@ static int plan_match_lds(ygzf_ctx *c, MatchArgs &A, int nPairs, size_t *ldsByte
         if ((rc = ensure(c, c->dMatchStat, 64))) return rc;
         HIPCHECK(c, hipMemsetAsync(c->dMatchStat.p, 0, 64, c->stream));
     }
-    A.serialFallbacks = (unsigned *) c->dMatchStat.p;
+    A.matchStat = (unsigned *) c->dMatchStat.p;
     A.serialOrder = c->matchSerial;
     A.handoverFence = c->matchFence;
     A.fixedLanes = c->matchFixedLanes;
@@ -152,6 +152,16 @@ int ygzf_match_fallbacks(ygzf_ctx *c, unsigned *pairs) {
     if (!c->dMatchStat.p) return YGZF_OK;   // no matcher launch yet
     HIPCHECK(c, hipSetDevice(c->device));
     HIPCHECK(c, hipMemcpyAsync(pairs, c->dMatchStat.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return YGZF_OK;
+}
+
+int ygzf_match_path_stats(ygzf_ctx *c, unsigned stats[5]) {
+    if (!c || !stats) return fail(c, YGZF_ERR_INVALID, "null argument");
+    for (int i = 0; i < kMatchStatWords; i++) stats[i] = 0;
+    if (!c->dMatchStat.p) return YGZF_OK;   // no matcher launch yet
+    HIPCHECK(c, hipSetDevice(c->device));
+    HIPCHECK(c, hipMemcpyAsync(stats, c->dMatchStat.p, kMatchStatWords * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }

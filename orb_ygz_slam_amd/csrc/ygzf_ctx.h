@@ -131,7 +131,7 @@ struct ygzf_ctx {
     double fastCornerQuadsPerRun = 0.0, fastRunsPerCell = 0.0;   // last sampled: corner-bearing quads per pass-1 run, pass-1 runs per cell (ygzf_get_fast_stats)
     Buf dFastStats;
     Buf dFastCells;                        // FastCellRec table of the current geometry (k_fast_tab)
-    Buf dMatchStat;                        // one counter: pairs that fell back to the matcher's one-wave pass (ygzf_match_fallbacks)
+    Buf dMatchStat;                        // the matcher's counters (kernels.h: kMatchStat*; ygzf_match_fallbacks, ygzf_match_path_stats)
     Buf dPack;                             // inputs + outputs of a one-frame entry point, one copy each way (PackedTransfer)
     int fastKernel = 0;                    // ygzf_fast_kernel: 0 chosen per geometry, 1 k_fast_quads (register staging), 2 k_fast_tab (cell table + LDS-DMA)
     unsigned *hFastStats = nullptr;        // page-locked mirror, refreshed by an asynchronous copy after every FAST launch
