@@ -345,6 +345,52 @@ typedef struct ygzf_fuse_points {
 int ygzf_fuse_candidates(ygzf_ctx *ctx, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
                          int *best_idx, int *best_dist);
 
+/* ---- The projection searches of LoopClosing: ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)   src/ORBmatcher.cc:888-1004
+ *      (LoopClosing::SearchAndFuse, src/LoopClosing.cc:546-569, th 4), ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)
+ *      :265-373 (LoopClosing.cc:346, th 10) and ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th)   :1006-1216
+ *      (LoopClosing.cc:299, th 7.5) ----------------------------------------------------------------------------------------------------------
+ * The keyframes and points are passed as for ygzf_fuse_candidates; inv_level_sigma2 and cam.mbf are not read here (NULL / 0 allowed) and
+ * view.u_right is ignored: these members have no 5.99 / 7.8 gates and no mvuRight term.  The device takes DECOMPOSED poses, never Scw: Rcw /
+ * tcw / Ow of a ygzf_fuse_kf are the Rcw = sRcw / scw, tcw = Scw(0:3, 3) / scw and Ow = -Rcw' tcw of :274-278 / :897-901, evaluated by the
+ * caller (host/ORBmatcherLoop.h: with the user's OpenCV in a reference build).  These three members do their algebra with cv::Mat where the
+ * first Fuse uses Eigen; the arithmetic below is OpenCV 2.4 / 3.2's, the project's default (parity unpinned):
+ *   Pc = ((R0 P0 + R1 P1) + R2 P2) + t per row in float; Pc.z < 0 rejects; invz = 1 / z, x = PcX invz, u = fx x + cx; IsInImage half-open;
+ *   cv::norm(v) = (float) sqrt(sum of (double) v[i] (double) v[i] in index order), the double square root correctly rounded;
+ *   PO.dot(Pn) = sum of (double) PO[i] (double) Pn[i] in index order; the viewing test is dot < 0.5 (double) dist;
+ *   PredictScale(dist, pKF) from mf_max_distance / dist; radius = th mvScaleFactors[level]; candidate levels [level - 1, level].
+ * The reference starts bestDist at INT_MAX in Fuse(.., Scw, ..) and SearchBySim3, which would also pick a key at Hamming distance 256; here
+ * every search reports -1 / 256 where no candidate is closer than 256.  No threshold of a caller reaches 256 (TH_LOW 50, TH_HIGH 100), so no
+ * result a caller sees differs.  All three use scratch buffers only (a context in the middle of a batch keeps its state) and have
+ * ygzf_fuse_candidates' argument checks and key-count limit.
+ *
+ * ygzf_fuse_sim3_candidates: n_kf keyframes (each with its own decomposed pose) x n_points points, distance norm(P - Ow), viewing test.
+ * skip (n_kf x n_points, NULL = none): the isBad / spAlreadyFound tests of :915.  best_idx / best_dist as ygzf_fuse_candidates, BEFORE the
+ * updates of :989-1000 (host/LoopApply.h applies them in the reference's order).
+ *
+ * ygzf_search_by_projection_sim3: one keyframe; skip (n_points, NULL = none) = the tests of :291; key_matched (kf->view.n bytes, NULL = none):
+ * nonzero = vpMatched[idx] is set, the key is passed over (:348).  Per point the n_best (1..8) least (distance, position in
+ * GetFeaturesInArea's list) candidates with distance <= max_dist (0..255) come back in cand_idx / cand_dist (n_points x n_best), ascending,
+ * padded with -1 / 256: the first is the reference's bestIdx under the given mask, the others let the caller resolve the dependence of
+ * :348 on earlier iterations without a call per point (host/LoopApply.h).
+ *
+ * ygzf_search_by_sim3: both directions in one launch.  pts1 / pts2 hold one entry per key of kf1 / kf2 (GetMapPointMatches; normal may be
+ * NULL); skip1 / skip2 (NULL = none): nonzero = no MapPoint in the slot, already matched (:1052, :1128) or bad.  Rcw / tcw / Ow of kf1 and kf2
+ * are not read: T carries R1w t1w, R2w t2w (GetRotation / GetTranslation) and sR12, t12, sR21 = (1 / s12) R12', t21 = -sR21 t12 (:1022-1024),
+ * row-major.  KF1's points go through R1w, t1w then sR21, t21 into kf2 (whose cam the caller fills as the reference does: pKF1's fx fy cx cy
+ * with pKF2's bounds), KF2's through R2w, t2w then sR12, t12 into kf1; the distance is norm(Pc) in the target camera's frame, no viewing test.
+ * match1[i1] (kf1->view.n) = vnMatch1 (best key of KF2 with distance <= th_dist, else -1), match2 (kf2->view.n) = vnMatch2; the agreement
+ * loop of :1200-1213 runs on the host inside the call: match12[i1] = idx2 where match2[match1[i1]] == i1, else -1; *nfound their number. */
+typedef struct ygzf_sim3_transforms {
+    float R1w[9], t1w[3], R2w[9], t2w[3], sR12[9], t12[3], sR21[9], t21[3];
+} ygzf_sim3_transforms;
+int ygzf_fuse_sim3_candidates(ygzf_ctx *ctx, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip,
+                              float th, int *best_idx, int *best_dist);
+int ygzf_search_by_projection_sim3(ygzf_ctx *ctx, const ygzf_fuse_kf *kf, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip,
+                                   const uint8_t *key_matched, float th, int n_best, int max_dist, int *cand_idx, int *cand_dist);
+int ygzf_search_by_sim3(ygzf_ctx *ctx, const ygzf_fuse_kf *kf1, const ygzf_fuse_kf *kf2, const ygzf_fuse_points *pts1,
+                        const ygzf_fuse_points *pts2, const uint8_t *skip1, const uint8_t *skip2, const ygzf_sim3_transforms *T, float th,
+                        int th_dist, int *match1, int *match2, int *match12, int *nfound);
+
 /* ---- Frame::ComputeBoW()   src/Frame.cc:495-500 -> ORBVocabulary::transform(features, BowVector, FeatureVector, levelsup = 4), i.e.
  *      DBoW2::TemplatedVocabulary<FORB::TDescriptor, FORB>::transform   Thirdparty/DBoW2/DBoW2/TemplatedVocabulary.h:1151-1283 ---
  * The vocabulary tree lives on the device.  ygzf_vocabulary_set uploads it as the reference's loaders build it (loadFromTextFile

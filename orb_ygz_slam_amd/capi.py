@@ -49,6 +49,11 @@ class FusePoints(C.Structure):
                 ("mf_max_distance", C.c_void_p), ("desc", C.c_void_p)]
 
 
+class Sim3Transforms(C.Structure):
+    _fields_ = [("R1w", C.c_float * 9), ("t1w", C.c_float * 3), ("R2w", C.c_float * 9), ("t2w", C.c_float * 3), ("sR12", C.c_float * 9),
+                ("t12", C.c_float * 3), ("sR21", C.c_float * 9), ("t21", C.c_float * 3)]
+
+
 class SiaFrame(C.Structure):
     _fields_ = [("n", C.c_int), ("keys", C.c_void_p), ("mp_valid", C.c_void_p), ("outlier", C.c_void_p), ("mp_world", C.c_void_p),
                 ("Tcw", C.c_float * 7), ("nlevels", C.c_int), ("levels", C.POINTER(C.c_void_p)), ("level_w", C.c_void_p),
@@ -150,6 +155,10 @@ def load_library(build_if_missing=True):
     L.ygzf_search_for_triangulation.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(FrameView), vp, C.POINTER(FrameView), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(Camera), C.c_int, C.c_int, vp, ip]
     L.ygzf_fuse_candidates.argtypes = [vp, C.c_int, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
+    L.ygzf_fuse_sim3_candidates.argtypes = [vp, C.c_int, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
+    L.ygzf_search_by_projection_sim3.argtypes = [vp, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, vp, C.c_float, C.c_int, C.c_int, vp, vp]
+    L.ygzf_search_by_sim3.argtypes = [vp, C.POINTER(FuseKf), C.POINTER(FuseKf), C.POINTER(FusePoints), C.POINTER(FusePoints), vp, vp,
+                                      C.POINTER(Sim3Transforms), C.c_float, C.c_int, vp, vp, vp, ip]
     L.ygzf_compute_stereo_matches.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, vp, vp, C.c_float, C.c_float, vp, vp]
     L.ygzf_stereo_batch.argtypes = [vp, C.c_float, C.c_float]
     L.ygzf_stereo_fetch.argtypes = [vp, C.c_int, vp, vp, C.c_int]
@@ -623,38 +632,95 @@ class Extractor:
                                                       int(check_ori), _p(match), C.byref(n)))
         return n.value, match[:f1.n]
 
-    def fuse_candidates(self, kfs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=3.0, skip=None):
-        """ORBmatcher::Fuse(KeyFrame*, MapPoints, th) candidate search over K keyframes x P points -> (best_idx, best_dist), K x P int32
-        (-1 / 256: none).  kfs: dicts with keys (KP_DTYPE), desc, u_right (None: monocular), scale_factors (None: the context's tables),
-        inv_level_sigma2, cam (Camera: fx fy cx cy mbf, bounds), Rcw (3x3), tcw, Ow, log_scale_factor.  skip: K x P bytes or None."""
-        keep = []
+    def _fuse_kfs(self, kfs, keep):
         arr = (FuseKf * max(len(kfs), 1))()
         for k, kf in enumerate(kfs):
             ck, cd = np.ascontiguousarray(kf["keys"], KP_DTYPE), np.ascontiguousarray(kf["desc"], np.uint8)
             u = None if kf.get("u_right") is None else np.ascontiguousarray(kf["u_right"], np.float32)
             sf = None if kf.get("scale_factors") is None else np.ascontiguousarray(kf["scale_factors"], np.float32)
-            ig = np.ascontiguousarray(kf["inv_level_sigma2"], np.float32)
+            ig = None if kf.get("inv_level_sigma2") is None else np.ascontiguousarray(kf["inv_level_sigma2"], np.float32)
             keep.extend([ck, cd, u, sf, ig])
             f = arr[k]
             f.view = FrameView(len(ck), ck.ctypes.data, cd.ctypes.data, None if u is None else u.ctypes.data,
                                None if sf is None else sf.ctypes.data, self.nlevels if sf is None else len(sf))
             f.cam = kf["cam"]
-            f.inv_level_sigma2 = ig.ctypes.data
+            f.inv_level_sigma2 = None if ig is None else ig.ctypes.data
             f.Rcw[:] = [float(x) for x in np.asarray(kf["Rcw"], np.float32).reshape(9)]
             f.tcw[:] = [float(x) for x in np.asarray(kf["tcw"], np.float32).reshape(3)]
             f.Ow[:] = [float(x) for x in np.asarray(kf["Ow"], np.float32).reshape(3)]
             f.log_scale_factor = float(kf["log_scale_factor"])
-        w, nr = np.ascontiguousarray(world, np.float32).reshape(-1, 3), np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
+        return arr
+
+    @staticmethod
+    def _fuse_points(world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, keep):
+        w = np.ascontiguousarray(world, np.float32).reshape(-1, 3)
+        nr = None if normal is None else np.ascontiguousarray(normal, np.float32).reshape(-1, 3)
         mx, mn, mf = (np.ascontiguousarray(a, np.float32).reshape(-1) for a in (max_dist_inv, min_dist_inv, mf_max_distance))
         d = np.ascontiguousarray(desc, np.uint8).reshape(-1, 32)
         keep.extend([w, nr, mx, mn, mf, d])
-        K, P = len(kfs), len(w)
-        pts = FusePoints(w.ctypes.data, nr.ctypes.data, mx.ctypes.data, mn.ctypes.data, mf.ctypes.data, d.ctypes.data)
+        return FusePoints(w.ctypes.data, None if nr is None else nr.ctypes.data, mx.ctypes.data, mn.ctypes.data, mf.ctypes.data, d.ctypes.data), len(w)
+
+    def fuse_candidates(self, kfs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=3.0, skip=None):
+        """ORBmatcher::Fuse(KeyFrame*, MapPoints, th) candidate search over K keyframes x P points -> (best_idx, best_dist), K x P int32
+        (-1 / 256: none).  kfs: dicts with keys (KP_DTYPE), desc, u_right (None: monocular), scale_factors (None: the context's tables),
+        inv_level_sigma2, cam (Camera: fx fy cx cy mbf, bounds), Rcw (3x3), tcw, Ow, log_scale_factor.  skip: K x P bytes or None."""
+        keep = []
+        arr = self._fuse_kfs(kfs, keep)
+        pts, P = self._fuse_points(world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, keep)
+        K = len(kfs)
         sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, P)
         bi = np.full((max(K, 1), max(P, 1)), -1, np.int32)
         bd = np.full((max(K, 1), max(P, 1)), 256, np.int32)
         self._ck(self.L.ygzf_fuse_candidates(self.h, K, arr, P, C.byref(pts), None if sk is None else _p(sk), th, _p(bi), _p(bd)))
         return bi[:K, :P].copy(), bd[:K, :P].copy()
+
+    def fuse_sim3_candidates(self, kfs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=4.0, skip=None):
+        """ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint) candidate search over K keyframes x P points -> (best_idx, best_dist) as
+        fuse_candidates.  kfs: as there, Rcw / tcw / Ow the decomposed Scw; inv_level_sigma2 / u_right are not read."""
+        keep = []
+        arr = self._fuse_kfs(kfs, keep)
+        pts, P = self._fuse_points(world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, keep)
+        K = len(kfs)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, P)
+        bi = np.full((max(K, 1), max(P, 1)), -1, np.int32)
+        bd = np.full((max(K, 1), max(P, 1)), 256, np.int32)
+        self._ck(self.L.ygzf_fuse_sim3_candidates(self.h, K, arr, P, C.byref(pts), None if sk is None else _p(sk), th, _p(bi), _p(bd)))
+        return bi[:K, :P].copy(), bd[:K, :P].copy()
+
+    def search_by_projection_sim3(self, kf, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=10.0, skip=None, key_matched=None,
+                                  n_best=1, max_dist=255):
+        """ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th) candidate search: per point the n_best least (distance, list
+        position) keys with distance <= max_dist that key_matched does not mask -> (cand_idx, cand_dist), P x n_best int32, -1 / 256 padded."""
+        keep = []
+        arr = self._fuse_kfs([kf], keep)
+        pts, P = self._fuse_points(world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, keep)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(P)
+        km = None if key_matched is None else np.ascontiguousarray(key_matched, np.uint8).reshape(len(kf["keys"]))
+        nb = max(int(n_best), 1)
+        ci = np.full((max(P, 1), nb), -1, np.int32)
+        cd = np.full((max(P, 1), nb), 256, np.int32)
+        self._ck(self.L.ygzf_search_by_projection_sim3(self.h, arr, P, C.byref(pts), None if sk is None else _p(sk), None if km is None else _p(km),
+                                                       th, int(n_best), int(max_dist), _p(ci), _p(cd)))
+        return ci[:P].copy(), cd[:P].copy()
+
+    def search_by_sim3(self, kf1, kf2, pts1, pts2, transforms, th=7.5, th_dist=100, skip1=None, skip2=None):
+        """ORBmatcher::SearchBySim3, both directions and the agreement loop -> (nfound, match12, match1, match2).  pts1 / pts2: tuples (world,
+        max_dist_inv, min_dist_inv, mf_max_distance, desc), one entry per key of kf1 / kf2; transforms: dict R1w t1w R2w t2w sR12 t12 sR21 t21."""
+        keep = []
+        a1, a2 = self._fuse_kfs([kf1], keep), self._fuse_kfs([kf2], keep)
+        p1, n1 = self._fuse_points(pts1[0], None, *pts1[1:], keep)
+        p2, n2 = self._fuse_points(pts2[0], None, *pts2[1:], keep)
+        assert n1 == len(kf1["keys"]) and n2 == len(kf2["keys"])
+        T = Sim3Transforms()
+        for name in ("R1w", "t1w", "R2w", "t2w", "sR12", "t12", "sR21", "t21"):
+            getattr(T, name)[:] = [float(x) for x in np.asarray(transforms[name], np.float32).reshape(-1)]
+        s1 = None if skip1 is None else np.ascontiguousarray(skip1, np.uint8).reshape(n1)
+        s2 = None if skip2 is None else np.ascontiguousarray(skip2, np.uint8).reshape(n2)
+        m1, m12, m2 = np.full(max(n1, 1), -1, np.int32), np.full(max(n1, 1), -1, np.int32), np.full(max(n2, 1), -1, np.int32)
+        nf = C.c_int()
+        self._ck(self.L.ygzf_search_by_sim3(self.h, a1, a2, C.byref(p1), C.byref(p2), None if s1 is None else _p(s1), None if s2 is None else _p(s2),
+                                            C.byref(T), th, int(th_dist), _p(m1), _p(m2), _p(m12), C.byref(nf)))
+        return nf.value, m12[:n1].copy(), m1[:n1].copy(), m2[:n2].copy()
 
     @staticmethod
     def _frustum_in(world, normal, max_dist_inv, min_dist_inv, mf_max_distance, Rcw, tcw, Ow, log_scale_factor, viewing_cos_limit, candidate, keep):

@@ -13,25 +13,13 @@
 
 #include "../../../include/ygzf.h"
 #include "FuseApply.h"
+#include "MatcherPack.h"
 #include "ORBmatcherFuse.h"
 #include "ygzf_pool.h"
 
 namespace ygz {
 
 namespace {
-// MapPoint::mfMaxDistance (PredictScale's numerator) is private in the reference's MapPoint.h: read through an explicit instantiation, whose
-// arguments access checking does not apply to (as host/TrackingBatched.cc does)
-template <typename Tag, typename Tag::type M>
-struct FuseMemberOf {
-    friend typename Tag::type member_ptr(Tag) { return M; }
-};
-struct FuseMaxDistanceTag {
-    typedef float MapPoint::*type;
-    friend type member_ptr(FuseMaxDistanceTag);
-};
-template struct FuseMemberOf<FuseMaxDistanceTag, &MapPoint::mfMaxDistance>;
-inline float max_distance(MapPoint *mp) { return mp->*member_ptr(FuseMaxDistanceTag()); }
-
 // the device query of FuseApply.h: one ygzf_fuse_candidates call for kfs x pts
 struct DeviceQuery {
     ygzf_ctx *c;
@@ -46,28 +34,7 @@ struct DeviceQuery {
         for (size_t k = 0; k < K; k++) {
             KeyFrame *pKF = kfs[k];
             ygzf_fuse_kf &f = kv[k];
-            std::memset(&f, 0, sizeof f);
-            const int n = pKF->N;
-            f.view.n = n;
-            f.view.keys = (const ygzf_kp *) pKF->mvKeys.data();
-            const cv::Mat &D = pKF->mDescriptors;
-            if (n > 0 && !(D.isContinuous() && D.cols == 32)) {
-                hold[k].resize((size_t) n * 32);
-                for (int i = 0; i < n; i++) std::memcpy(&hold[k][(size_t) i * 32], D.ptr<uint8_t>(i), 32);
-                f.view.desc = hold[k].data();
-            } else {
-                f.view.desc = n > 0 ? D.ptr<uint8_t>(0) : nullptr;
-            }
-            f.view.u_right = (int) pKF->mvuRight.size() == n ? pKF->mvuRight.data() : nullptr;
-            f.view.scale_factors = pKF->mvScaleFactors.data();
-            f.view.nlevels = pKF->mnScaleLevels;
-            if ((int) pKF->mvScaleFactors.size() < pKF->mnScaleLevels || (int) pKF->mvInvLevelSigma2.size() < pKF->mnScaleLevels) {
-                ygzf_host::report_failure(who, "keyframe scale tables shorter than mnScaleLevels");
-                return false;
-            }
-            f.cam.fx = pKF->fx; f.cam.fy = pKF->fy; f.cam.cx = pKF->cx; f.cam.cy = pKF->cy; f.cam.mbf = pKF->mbf;
-            f.cam.min_x = (float) pKF->mnMinX; f.cam.min_y = (float) pKF->mnMinY; f.cam.max_x = (float) pKF->mnMaxX; f.cam.max_y = (float) pKF->mnMaxY;
-            f.inv_level_sigma2 = pKF->mvInvLevelSigma2.data();
+            if (!pack_keyframe(pKF, pKF, f, hold[k], who)) return false;
             const Matrix3f R = pKF->GetRotation();
             const Vector3f t = pKF->GetTranslation(), O = pKF->GetCameraCenter();
             for (int r = 0; r < 3; r++) {
@@ -75,23 +42,9 @@ struct DeviceQuery {
                 f.tcw[r] = t[r];
                 f.Ow[r] = O[r];
             }
-            f.log_scale_factor = pKF->mfLogScaleFactor;
         }
-        std::vector<float> world(3 * P, 0.f), normal(3 * P, 0.f), maxInv(P, 0.f), minInv(P, 0.f), maxDist(P, 1.f);
-        std::vector<uint8_t> desc(32 * P, 0);
-        for (size_t i = 0; i < P; i++) {
-            MapPoint *mp = pts[i];
-            if (!mp) continue;   // (every row skips it)
-            ygz_compat::world_pos(mp, &world[3 * i]);
-            const Vector3f nrm = mp->GetNormal();
-            for (int r = 0; r < 3; r++) normal[3 * i + r] = nrm[r];
-            maxInv[i] = mp->GetMaxDistanceInvariance();
-            minInv[i] = mp->GetMinDistanceInvariance();
-            maxDist[i] = max_distance(mp);
-            const cv::Mat d = mp->GetDescriptor();
-            if (!d.empty()) std::memcpy(&desc[32 * i], d.ptr<uint8_t>(0), 32);
-        }
-        ygzf_fuse_points fp = {world.data(), normal.data(), maxInv.data(), minInv.data(), maxDist.data(), desc.data()};
+        const PointArrays pa(pts, 0, nullptr);   // (a null entry stays zero: every row skips it)
+        const ygzf_fuse_points &fp = pa.view;
         const int rc = ygzf_fuse_candidates(c, (int) K, kv.data(), (int) P, &fp, skip.data(), th, bi.data(), bd.data());
         if (rc != YGZF_OK) {
             ygzf_host::report_failure(who, ygzf_last_error(c));

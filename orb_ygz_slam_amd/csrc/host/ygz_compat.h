@@ -161,6 +161,10 @@ public:
     Vector3f GetNormal() const { return mNormalVector; }                                        // src/MapPoint.cc:74-77
     MapPoint *GetReplaced() const { return mpReplaced; }
     bool IsInKeyFrame(KeyFrame *pKF) const { return mObservations.count(pKF) != 0; }           // :286-289
+    int GetIndexInKeyFrame(KeyFrame *pKF) const {                                              // :278-284 (SearchBySim3)
+        const std::map<KeyFrame *, size_t>::const_iterator it = mObservations.find(pKF);
+        return it == mObservations.end() ? -1 : (int) it->second;
+    }
     void IncreaseVisible(int n) { mnVisible += n; }                                             // :196-199
     void IncreaseFound(int n) { mnFound += n; }                                                 // :201-204
     inline void AddObservation(KeyFrame *pKF, size_t idx);
@@ -225,6 +229,12 @@ public:
     int mnMinX = 0, mnMinY = 0, mnMaxX = 0, mnMaxY = 0;
     bool mbBad = false;
     bool isBad() const { return mbBad; }
+    std::set<MapPoint *> GetMapPoints() const {                                                 // src/KeyFrame.cc:449-460 (Fuse(pKF, Scw, ..))
+        std::set<MapPoint *> s;
+        for (MapPoint *pMP : mvpMapPoints)
+            if (pMP && !pMP->isBad()) s.insert(pMP);
+        return s;
+    }
     bool IsInImage(const float &x, const float &y) const { return (x >= mnMinX && x < mnMaxX && y >= mnMinY && y < mnMaxY); }   // src/KeyFrame.cc:811-813
     void AddMapPoint(MapPoint *pMP, const size_t &idx) { mvpMapPoints[idx] = pMP; }             // :428-431
     void EraseMapPointMatch(const size_t &idx) { mvpMapPoints[idx] = static_cast<MapPoint *>(nullptr); }   // :433-436

@@ -340,6 +340,28 @@ struct FuseArgs {
 size_t fuse_lds_bytes(int maxKeys);
 hipError_t launch_fuse(hipStream_t st, const FuseArgs &A, int maxKeys);
 
+// The loop-closing projection searches (match_kernels.hip: k_proj_search<mode>, the body k_fuse runs as PM_FUSE): Fuse(pKF, Scw, ...),
+// SearchByProjection(pKF, Scw, ...) and the two directions of SearchBySim3.  A row is one target keyframe with its own point list.
+enum ProjMode { PM_FUSE = 0, PM_FUSE_SCW = 1, PM_PROJ_SCW = 2, PM_SIM3 = 3 };
+struct ProjRow {
+    FuseKf kf;                      // the target keyframe; Rcw / tcw = the (first) transform, Ow = its camera centre (unused by PM_SIM3)
+    float R2[9], t2[3];             // PM_SIM3: the second transform, Pc = R2 * (Rcw * P + tcw) + t2
+    long long world, normal, maxDistInv, minDistInv, mfMaxDistance, mpDesc;   // byte offsets from ProjArgs::base (normal -1: PM_SIM3)
+    long long skip, keyMatched;     // byte offsets, -1: none.  skip: nPoints bytes; keyMatched: kf.n bytes (PM_PROJ_SCW)
+    int nPoints;
+    long long out;                  // first point of this row in bestIdx / bestDist (in points; times nBest entries)
+};
+struct ProjArgs {
+    int mode;                       // ProjMode, not PM_FUSE
+    int nRows, maxPoints, slice;    // grid = (ceil(maxPoints / slice), nRows)
+    const uint8_t *base;
+    const ProjRow *rows;
+    float th;
+    int nBest, maxHamming;          // candidates kept per point (1 unless PM_PROJ_SCW) and the largest distance kept (<= 255)
+    int *bestIdx, *bestDist;        // nBest entries per point, ascending (dist, list position), padded with -1 / 256
+};
+hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys);
+
 struct SiaArgs {
     int ldsFeat;                    // feature slots of the dynamic LDS carve-up (float4 s_feat[ldsFeat] | float2 s_uv[ldsFeat] | float4 s_jac[2*ldsFeat])
     int stageOff, stageBytes;       // byte offset (from the start of dynamic LDS) and size of the staged current-image region

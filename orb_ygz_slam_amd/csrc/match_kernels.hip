@@ -1850,7 +1850,148 @@ hipError_t launch_features_in_area(hipStream_t st, const FiaArgs &A) {
 // Arithmetic in the reference's order (-ffp-contract=off); Rcw*P + t and the squared norm as k_frustum.  Where Fuse differs from isInFrustum:
 // x = PcX*invz then fx*x + cx; KeyFrame::IsInImage is half-open (:811-813); the viewing test is PO.Pn < 0.5*dist3D in double; the error
 // gates compare the float product with the double literals 7.8 / 5.99.
+//
+// The same body (proj_search_point<MODE>) serves the three projection searches of LoopClosing, which write their algebra with cv::Mat where
+// Fuse above uses Eigen (OpenCV 2.4 / 3.2 behaviour, the project's default; DESIGN section 2 "parity unpinned"):
+//   PM_FUSE_SCW  Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)           src/ORBmatcher.cc:888-1004
+//   PM_PROJ_SCW  SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)  :265-373  (keys with keyMatched[idx] != 0 are passed over, :348;
+//                the nBest least (dist, list position) candidates with dist <= maxDist come back, ascending)
+//   PM_SIM3      one direction of SearchBySim3                          :1049-1122 / :1125-1198  (two transforms chained; the distance is
+//                norm(Pc) in the target camera's frame; no viewing test)
+// What these share and Fuse does not: cv::norm on three floats accumulates (double) v[i] * (double) v[i] in index order, takes the double
+// square root and casts to float (sqrt_to_float below: the correctly rounded double root, then the cast); PO.dot(Pn) accumulates
+// (double) PO[i] * (double) Pn[i]; the viewing test is dot < 0.5 * (double) dist.  No 5.99 / 7.8 gates, no mvuRight term.  Rcw * P + t is the
+// float form above for both (OpenCV's small-matrix gemm: float dot left to right, then one float add).
+// Two of the three reference bodies start bestDist at INT_MAX, which would also accept a key at Hamming distance 256; here every mode starts
+// at 256 (-1 / 256: none).  No caller's threshold (TH_LOW 50, TH_HIGH 100) reaches 256, so nothing a caller sees differs.
 // ------------------------------------------------------------------------------------------------------------------
+// (float) sqrt(s) as the host computes it: the correctly rounded DOUBLE root, then the cast (two roundings, as cv::norm's `(float) std::sqrt`).
+// The device's double sqrt is taken to be within one ulp and brought to the correctly rounded double exactly: the residual s - q*q of such a q
+// is exact in one fma, and q is the nearest double iff -q*u < s - q*q <= q*u (u = the spacing of doubles at q; equality with a midpoint's
+// square cannot occur, it has more than 53 bits).  s >= 0 a double sum of squares of floats.
+__device__ __forceinline__ float sqrt_to_float(double s) {
+    double q = sqrt(s);
+    if (q > 1.0e-150 && q < 1.0e150) {
+        const double u = __longlong_as_double(__double_as_longlong(q) & 0x7FF0000000000000ll) * 0x1p-52;
+        const double r = fma(-q, q, s), qu = q * u;
+        if (r > qu) q += u;
+        else if (r <= -qu) q -= u;
+    }
+    return (float) q;
+}
+
+// One point against one keyframe (a whole wave; `lane` 0 writes).  R2 / t2: PM_SIM3's second transform.  outIdx / outDist: nBest entries
+// (nBest = 1 unless PM_PROJ_SCW), preset here to -1 / 256.
+template <int MODE>
+__device__ __forceinline__ void proj_search_point(const FuseKf &K, const float *R2, const float *t2, const ygzf_kp *__restrict__ keys,
+                                                  const uint8_t *__restrict__ kdesc, const float *__restrict__ uRight,
+                                                  const uint8_t *__restrict__ keyMatched, const int *cellStart, const int *list, const float *P,
+                                                  const float *Pn, float minDist, float maxDist, float mfMaxDistance, const uint64_t *md, float th,
+                                                  int nBestArg, int maxHamming, int lane, int *outIdx, int *outDist) {
+    const int nBest = MODE == PM_PROJ_SCW ? nBestArg : 1;
+    int found = 0;
+    do {
+        float PcX = (K.Rcw[0] * P[0] + K.Rcw[1] * P[1] + K.Rcw[2] * P[2]) + K.tcw[0];
+        float PcY = (K.Rcw[3] * P[0] + K.Rcw[4] * P[1] + K.Rcw[5] * P[2]) + K.tcw[1];
+        float PcZ = (K.Rcw[6] * P[0] + K.Rcw[7] * P[1] + K.Rcw[8] * P[2]) + K.tcw[2];
+        if (MODE == PM_SIM3) {
+            const float qx = (R2[0] * PcX + R2[1] * PcY + R2[2] * PcZ) + t2[0];
+            const float qy = (R2[3] * PcX + R2[4] * PcY + R2[5] * PcZ) + t2[1];
+            const float qz = (R2[6] * PcX + R2[7] * PcY + R2[8] * PcZ) + t2[2];
+            PcX = qx; PcY = qy; PcZ = qz;
+        }
+        if (PcZ < 0.0f) break;
+        const float invz = 1 / PcZ;
+        const float x = PcX * invz, y = PcY * invz;
+        const float u = K.fx * x + K.cx, v = K.fy * y + K.cy;
+        if (!(u >= K.minX && u < K.maxX && v >= K.minY && v < K.maxY)) break;
+        const float ur = u - K.mbf * invz;
+        const float PO[3] = {P[0] - K.Ow[0], P[1] - K.Ow[1], P[2] - K.Ow[2]};
+        float dist3D;
+        if (MODE == PM_FUSE) {
+            dist3D = sqrtf(PO[0] * PO[0] + PO[1] * PO[1] + PO[2] * PO[2]);
+        } else {
+            const float a0 = MODE == PM_SIM3 ? PcX : PO[0], a1 = MODE == PM_SIM3 ? PcY : PO[1], a2 = MODE == PM_SIM3 ? PcZ : PO[2];
+            double s = (double) a0 * (double) a0;
+            s += (double) a1 * (double) a1;
+            s += (double) a2 * (double) a2;
+            dist3D = sqrt_to_float(s);
+        }
+        if (dist3D < minDist || dist3D > maxDist) break;
+        if (MODE == PM_FUSE) {
+            const float dot = PO[0] * Pn[0] + PO[1] * Pn[1] + PO[2] * Pn[2];
+            if ((double) dot < 0.5 * (double) dist3D) break;
+        } else if (MODE != PM_SIM3) {
+            double dot = (double) PO[0] * (double) Pn[0];
+            dot += (double) PO[1] * (double) Pn[1];
+            dot += (double) PO[2] * (double) Pn[2];
+            if (dot < 0.5 * (double) dist3D) break;
+        }
+        const float ratio = mfMaxDistance / dist3D;
+        int pred = 0;
+        for (int k = 1; k < K.nLevels; k++) pred += (ratio >= K.levelStep[k]) ? 1 : 0;
+        const float r = th * K.scale[pred];
+        const int nMinCellX = max(0, (int) floorf((u - K.minX - r) * K.gridInvW));
+        if (nMinCellX >= GRID_COLS) break;
+        const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((u - K.minX + r) * K.gridInvW));
+        if (nMaxCellX < 0) break;
+        const int nMinCellY = max(0, (int) floorf((v - K.minY - r) * K.gridInvH));
+        if (nMinCellY >= GRID_ROWS) break;
+        const int nMaxCellY = min(GRID_ROWS - 1, (int) ceilf((v - K.minY + r) * K.gridInvH));
+        if (nMaxCellY < 0 || nMinCellY > nMaxCellY) break;
+        const uint64_t m0 = md[0], m1 = md[1], m2 = md[2], m3 = md[3];
+        unsigned prev = 0;   // the key of the previous pass (PM_PROJ_SCW, pass > 0): this pass finds the least key above it
+        for (int pass = 0; pass < nBest; pass++) {
+            unsigned best = 0xFFFFFFFFu;
+            int bestLane = -1;
+            int ord = 0;   // position in GetFeaturesInArea's concatenated cell lists
+            for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
+                const int s = cellStart[ix * GRID_ROWS + nMinCellY], e = cellStart[ix * GRID_ROWS + nMaxCellY + 1];
+                for (int base = s; base < e; base += 64, ord += 64) {
+                    const int j = base + lane;
+                    if (j >= e) continue;
+                    const int idx = list[j];
+                    const ygzf_kp kp = keys[idx];
+                    if (!(fabsf(kp.x - u) < r && fabsf(kp.y - v) < r)) continue;   // GetFeaturesInArea
+                    if (MODE == PM_PROJ_SCW && keyMatched && keyMatched[idx]) continue;   // vpMatched[idx], :348
+                    const int kpLevel = kp.octave;
+                    if (kpLevel < pred - 1 || kpLevel > pred) continue;
+                    if (MODE == PM_FUSE) {
+                        const float ex = u - kp.x, ey = v - kp.y;
+                        const float kpr = uRight ? uRight[idx] : -1.0f;
+                        if (kpr >= 0) {
+                            const float er = ur - kpr;
+                            const float e2 = ex * ex + ey * ey + er * er;
+                            if ((double) (e2 * K.invSigma2[kpLevel]) > 7.8) continue;
+                        } else {
+                            const float e2 = ex * ex + ey * ey;
+                            if ((double) (e2 * K.invSigma2[kpLevel]) > 5.99) continue;
+                        }
+                    }
+                    const uint64_t *d = (const uint64_t *) (kdesc + 32 * (size_t) idx);
+                    const unsigned dist = __popcll(d[0] ^ m0) + __popcll(d[1] ^ m1) + __popcll(d[2] ^ m2) + __popcll(d[3] ^ m3);
+                    if ((int) dist > maxHamming) continue;   // maxHamming <= 255: never below the initial bestDist = 256
+                    const unsigned key = (dist << 16) | (unsigned) (ord + lane);
+                    if (MODE == PM_PROJ_SCW && pass > 0 && key <= prev) continue;
+                    if (key < best) { best = key; bestLane = idx; }
+                }
+            }
+            const unsigned wbest = wave_min_dpp(best);
+            if (wbest == 0xFFFFFFFFu) break;
+            const unsigned long long owner = __ballot(best == wbest);
+            const int bestIdx = __shfl(bestLane, (int) __ffsll((long long) owner) - 1);
+            if (lane == 0) {
+                outIdx[pass] = bestIdx;
+                outDist[pass] = (int) (wbest >> 16);
+            }
+            prev = wbest;
+            found = pass + 1;
+        }
+    } while (false);
+    if (lane == 0)
+        for (int k = found; k < nBest; k++) { outIdx[k] = -1; outDist[k] = 256; }
+}
+
 __global__ __launch_bounds__(kMatchBlock) void k_fuse(FuseArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ int s_tmp[kMatchBlock / 64];
@@ -1867,79 +2008,13 @@ __global__ __launch_bounds__(kMatchBlock) void k_fuse(FuseArgs A) {
     const int p0 = blockIdx.x * A.slice, p1 = min(A.nPoints, p0 + A.slice);
     for (int i = p0 + wave; i < p1; i += kMatchBlock / 64) {
         const size_t o = (size_t) kf * A.nPoints + i;
-        int bestIdx = -1, bestDist = 256;
-        do {
-            if (A.skip && A.skip[o]) break;
-            const float *P = A.world + 3 * (size_t) i;
-            const float PcX = (K.Rcw[0] * P[0] + K.Rcw[1] * P[1] + K.Rcw[2] * P[2]) + K.tcw[0];
-            const float PcY = (K.Rcw[3] * P[0] + K.Rcw[4] * P[1] + K.Rcw[5] * P[2]) + K.tcw[1];
-            const float PcZ = (K.Rcw[6] * P[0] + K.Rcw[7] * P[1] + K.Rcw[8] * P[2]) + K.tcw[2];
-            if (PcZ < 0.0f) break;
-            const float invz = 1 / PcZ;
-            const float x = PcX * invz, y = PcY * invz;
-            const float u = K.fx * x + K.cx, v = K.fy * y + K.cy;
-            if (!(u >= K.minX && u < K.maxX && v >= K.minY && v < K.maxY)) break;
-            const float ur = u - K.mbf * invz;
-            const float PO[3] = {P[0] - K.Ow[0], P[1] - K.Ow[1], P[2] - K.Ow[2]};
-            const float dist3D = sqrtf(PO[0] * PO[0] + PO[1] * PO[1] + PO[2] * PO[2]);
-            if (dist3D < A.minDistInv[i] || dist3D > A.maxDistInv[i]) break;
-            const float *Pn = A.normal + 3 * (size_t) i;
-            const float dot = PO[0] * Pn[0] + PO[1] * Pn[1] + PO[2] * Pn[2];
-            if ((double) dot < 0.5 * (double) dist3D) break;
-            const float ratio = A.mfMaxDistance[i] / dist3D;
-            int pred = 0;
-            for (int k = 1; k < K.nLevels; k++) pred += (ratio >= K.levelStep[k]) ? 1 : 0;
-            const float r = A.th * K.scale[pred];
-            const int nMinCellX = max(0, (int) floorf((u - K.minX - r) * K.gridInvW));
-            if (nMinCellX >= GRID_COLS) break;
-            const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((u - K.minX + r) * K.gridInvW));
-            if (nMaxCellX < 0) break;
-            const int nMinCellY = max(0, (int) floorf((v - K.minY - r) * K.gridInvH));
-            if (nMinCellY >= GRID_ROWS) break;
-            const int nMaxCellY = min(GRID_ROWS - 1, (int) ceilf((v - K.minY + r) * K.gridInvH));
-            if (nMaxCellY < 0 || nMinCellY > nMaxCellY) break;
-            const uint64_t *md = (const uint64_t *) (A.mpDesc + 32 * (size_t) i);
-            const uint64_t m0 = md[0], m1 = md[1], m2 = md[2], m3 = md[3];
-            unsigned best = 0xFFFFFFFFu;
-            int bestLane = -1;
-            int ord = 0;   // position in GetFeaturesInArea's concatenated cell lists
-            for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-                const int s = cellStart[ix * GRID_ROWS + nMinCellY], e = cellStart[ix * GRID_ROWS + nMaxCellY + 1];
-                for (int base = s; base < e; base += 64, ord += 64) {
-                    const int j = base + lane;
-                    if (j >= e) continue;
-                    const int idx = list[j];
-                    const ygzf_kp kp = keys[idx];
-                    if (!(fabsf(kp.x - u) < r && fabsf(kp.y - v) < r)) continue;   // GetFeaturesInArea
-                    const int kpLevel = kp.octave;
-                    if (kpLevel < pred - 1 || kpLevel > pred) continue;
-                    const float ex = u - kp.x, ey = v - kp.y;
-                    const float kpr = uRight ? uRight[idx] : -1.0f;
-                    if (kpr >= 0) {
-                        const float er = ur - kpr;
-                        const float e2 = ex * ex + ey * ey + er * er;
-                        if ((double) (e2 * K.invSigma2[kpLevel]) > 7.8) continue;
-                    } else {
-                        const float e2 = ex * ex + ey * ey;
-                        if ((double) (e2 * K.invSigma2[kpLevel]) > 5.99) continue;
-                    }
-                    const uint64_t *d = (const uint64_t *) (kdesc + 32 * (size_t) idx);
-                    const unsigned dist = __popcll(d[0] ^ m0) + __popcll(d[1] ^ m1) + __popcll(d[2] ^ m2) + __popcll(d[3] ^ m3);
-                    if (dist >= 256) continue;   // never below the initial bestDist = 256
-                    const unsigned key = (dist << 16) | (unsigned) (ord + lane);
-                    if (key < best) { best = key; bestLane = idx; }
-                }
-            }
-            const unsigned wbest = wave_min_dpp(best);
-            if (wbest == 0xFFFFFFFFu) break;
-            const unsigned long long owner = __ballot(best == wbest);
-            bestIdx = __shfl(bestLane, (int) __ffsll((long long) owner) - 1);
-            bestDist = (int) (wbest >> 16);
-        } while (false);
-        if (lane == 0) {
-            A.bestIdx[o] = bestIdx;
-            A.bestDist[o] = bestDist;
+        if (A.skip && A.skip[o]) {
+            if (lane == 0) { A.bestIdx[o] = -1; A.bestDist[o] = 256; }
+            continue;
         }
+        proj_search_point<PM_FUSE>(K, nullptr, nullptr, keys, kdesc, uRight, nullptr, cellStart, list, A.world + 3 * (size_t) i,
+                                   A.normal + 3 * (size_t) i, A.minDistInv[i], A.maxDistInv[i], A.mfMaxDistance[i],
+                                   (const uint64_t *) (A.mpDesc + 32 * (size_t) i), A.th, 1, 255, lane, A.bestIdx + o, A.bestDist + o);
     }
 }
 
@@ -1950,6 +2025,58 @@ hipError_t launch_fuse(hipStream_t st, const FuseArgs &A, int maxKeys) {
     hipError_t e = hipFuncSetAttribute((const void *) k_fuse, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_fuse, dim3((A.nPoints + A.slice - 1) / A.slice, A.nKf), dim3(kMatchBlock), fuse_lds_bytes(maxKeys), st, A);
+    return hipSuccess;
+}
+
+// The loop-closing searches: workgroup = one row (blockIdx.y: a target keyframe with its own point list) x a slice of that row's points.
+// Rows shorter than the longest leave their surplus workgroups idle (SearchBySim3's two directions have N1 and N2 points).
+template <int MODE>
+__global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
+    __shared__ int s_tmp[kMatchBlock / 64];
+    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
+    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
+    int *list = cellFill + GRID_CELLS;               // n
+    const ProjRow &R = A.rows[blockIdx.y];
+    const int p0 = blockIdx.x * A.slice, p1 = min(R.nPoints, p0 + A.slice);
+    if (p0 >= p1) return;                            // the whole workgroup, before any barrier
+    const FuseKf &K = R.kf;
+    const ygzf_kp *keys = (const ygzf_kp *) (A.base + K.keys);
+    const uint8_t *kdesc = A.base + K.desc;
+    const float *world = (const float *) (A.base + R.world);
+    const float *normal = R.normal >= 0 ? (const float *) (A.base + R.normal) : nullptr;
+    const float *maxInv = (const float *) (A.base + R.maxDistInv), *minInv = (const float *) (A.base + R.minDistInv);
+    const float *mfMax = (const float *) (A.base + R.mfMaxDistance);
+    const uint8_t *mpDesc = A.base + R.mpDesc;
+    const uint8_t *skip = R.skip >= 0 ? A.base + R.skip : nullptr;
+    const uint8_t *keyMatched = R.keyMatched >= 0 ? A.base + R.keyMatched : nullptr;
+    const int nBest = MODE == PM_PROJ_SCW ? A.nBest : 1;
+    build_grid_lds(keys, K.n, K.minX, K.minY, K.gridInvW, K.gridInvH, cellStart, cellFill, list, s_tmp);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int i = p0 + wave; i < p1; i += kMatchBlock / 64) {
+        const size_t o = ((size_t) R.out + (size_t) i) * (size_t) nBest;
+        if (skip && skip[i]) {
+            if (lane == 0)
+                for (int k = 0; k < nBest; k++) { A.bestIdx[o + k] = -1; A.bestDist[o + k] = 256; }
+            continue;
+        }
+        proj_search_point<MODE>(K, R.R2, R.t2, keys, kdesc, nullptr, keyMatched, cellStart, list, world + 3 * (size_t) i,
+                                normal ? normal + 3 * (size_t) i : nullptr, minInv[i], maxInv[i], mfMax[i],
+                                (const uint64_t *) (mpDesc + 32 * (size_t) i), A.th, nBest, A.maxHamming, lane, A.bestIdx + o, A.bestDist + o);
+    }
+}
+
+hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys) {
+    if (A.nRows <= 0 || A.maxPoints <= 0) return hipSuccess;
+    const void *fn = A.mode == PM_FUSE_SCW ? (const void *) k_proj_search<PM_FUSE_SCW>
+                     : A.mode == PM_PROJ_SCW ? (const void *) k_proj_search<PM_PROJ_SCW> : (const void *) k_proj_search<PM_SIM3>;
+    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    if (e != hipSuccess) return e;
+    const dim3 grid((A.maxPoints + A.slice - 1) / A.slice, A.nRows), block(kMatchBlock);
+    const size_t lds = fuse_lds_bytes(maxKeys);
+    if (A.mode == PM_FUSE_SCW) hipLaunchKernelGGL(k_proj_search<PM_FUSE_SCW>, grid, block, lds, st, A);
+    else if (A.mode == PM_PROJ_SCW) hipLaunchKernelGGL(k_proj_search<PM_PROJ_SCW>, grid, block, lds, st, A);
+    else hipLaunchKernelGGL(k_proj_search<PM_SIM3>, grid, block, lds, st, A);
     return hipSuccess;
 }
 

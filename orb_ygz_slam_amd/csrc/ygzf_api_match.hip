@@ -625,6 +625,45 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
     return YGZF_OK;
 }
 
+// One keyframe of the Fuse / loop-closing searches: the argument checks (needSigma: mvInvLevelSigma2 is read, i.e. the first Fuse) ...
+static int fuse_kf_check(ygzf_ctx *c, const ygzf_fuse_kf &K, int k, bool needSigma) {
+    const int n = K.view.n;
+    if (n < 0) return fail(c, YGZF_ERR_INVALID, "keyframe %d: negative key count", k);
+    if (n > 0 && (!K.view.keys || !K.view.desc)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null key array", k);
+    if (needSigma && !K.inv_level_sigma2) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null mvInvLevelSigma2", k);
+    const int L = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
+    if (L < 1 || L > kMaxLevels) return fail(c, YGZF_ERR_INVALID, "keyframe %d: nlevels out of range", k);
+    if (!(K.cam.max_x > K.cam.min_x) || !(K.cam.max_y > K.cam.min_y)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: empty image bounds", k);
+    for (int i = 0; i < n; i++)
+        if (K.view.keys[i].octave < 0 || K.view.keys[i].octave >= L)
+            return fail(c, YGZF_ERR_INVALID, "keyframe %d: keypoint octave outside the scale tables", k);
+    if (fuse_lds_bytes(n) > (size_t) kMaxDynLds)
+        return fail(c, YGZF_ERR_UNSUPPORTED, "keyframe %d: more than %d keypoints in one grid", k, (int) ((kMaxDynLds - 25000) / 4));
+    return YGZF_OK;
+}
+// ... and its device record; the key arrays join the packed upload
+static void fuse_kf_fill(ygzf_ctx *c, PackedTransfer &P, const ygzf_fuse_kf &K, FuseKf &F) {
+    memset(&F, 0, sizeof F);
+    const size_t n = (size_t) K.view.n;
+    F.keys = (long long) P.add_in(K.view.keys, sizeof(ygzf_kp) * n);
+    F.desc = (long long) P.add_in(K.view.desc, 32 * n);
+    F.uRight = K.view.u_right ? (long long) P.add_in(K.view.u_right, 4 * n) : -1;
+    F.n = (int) n;
+    F.nLevels = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
+    memcpy(F.Rcw, K.Rcw, 36);
+    memcpy(F.tcw, K.tcw, 12);
+    memcpy(F.Ow, K.Ow, 12);
+    F.fx = K.cam.fx; F.fy = K.cam.fy; F.cx = K.cam.cx; F.cy = K.cam.cy; F.mbf = K.cam.mbf;
+    F.minX = K.cam.min_x; F.minY = K.cam.min_y; F.maxX = K.cam.max_x; F.maxY = K.cam.max_y;
+    F.gridInvW = (float) 64 / (K.cam.max_x - K.cam.min_x);   // mfGridElementWidthInv / HeightInv, src/Frame.cc:302-303
+    F.gridInvH = (float) 48 / (K.cam.max_y - K.cam.min_y);
+    predict_scale_steps(K.log_scale_factor, F.nLevels, F.levelStep);
+    for (int l = 0; l < kMaxLevels; l++) {
+        F.scale[l] = l < F.nLevels ? (K.view.scale_factors ? K.view.scale_factors[l] : c->tab.scale[l]) : 1.f;
+        F.invSigma2[l] = l < F.nLevels && K.inv_level_sigma2 ? K.inv_level_sigma2[l] : 1.f;
+    }
+}
+
 // ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) candidate search, src/ORBmatcher.cc:764-868 (include/ygzf.h).  Validation
 // first; one packed copy in (every keyframe's keys / descriptors / mvuRight, the point arrays, the skip mask, the per-keyframe tables), one out.
 // Touches nothing in c->held: only the packed staging area is written.
@@ -636,50 +675,15 @@ int ygzf_fuse_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_p
     if (!kfs || !pts || !best_idx || !best_dist) return fail(c, YGZF_ERR_INVALID, "null argument");
     if (!pts->world || !pts->normal || !pts->max_dist_inv || !pts->min_dist_inv || !pts->mf_max_distance || !pts->desc)
         return fail(c, YGZF_ERR_INVALID, "null point array");
-    int maxKeys = 0;
+    int maxKeys = 0, rc;
     for (int k = 0; k < n_kf; k++) {
-        const ygzf_fuse_kf &K = kfs[k];
-        const int n = K.view.n;
-        if (n < 0) return fail(c, YGZF_ERR_INVALID, "keyframe %d: negative key count", k);
-        if (n > 0 && (!K.view.keys || !K.view.desc)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null key array", k);
-        if (!K.inv_level_sigma2) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null mvInvLevelSigma2", k);
-        const int L = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
-        if (L < 1 || L > kMaxLevels) return fail(c, YGZF_ERR_INVALID, "keyframe %d: nlevels out of range", k);
-        if (!(K.cam.max_x > K.cam.min_x) || !(K.cam.max_y > K.cam.min_y)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: empty image bounds", k);
-        for (int i = 0; i < n; i++)
-            if (K.view.keys[i].octave < 0 || K.view.keys[i].octave >= L)
-                return fail(c, YGZF_ERR_INVALID, "keyframe %d: keypoint octave outside the scale tables", k);
-        if (fuse_lds_bytes(n) > (size_t) kMaxDynLds)
-            return fail(c, YGZF_ERR_UNSUPPORTED, "keyframe %d: more than %d keypoints in one grid", k, (int) ((kMaxDynLds - 25000) / 4));
-        maxKeys = std::max(maxKeys, n);
+        if ((rc = fuse_kf_check(c, kfs[k], k, true))) return rc;
+        maxKeys = std::max(maxKeys, kfs[k].view.n);
     }
     HIPCHECK(c, hipSetDevice(c->device));
-    int rc;
     PackedTransfer P(c);
     std::vector<FuseKf> fk((size_t) n_kf);
-    for (int k = 0; k < n_kf; k++) {
-        const ygzf_fuse_kf &K = kfs[k];
-        FuseKf &F = fk[k];
-        memset(&F, 0, sizeof F);
-        const size_t n = (size_t) K.view.n;
-        F.keys = (long long) P.add_in(K.view.keys, sizeof(ygzf_kp) * n);
-        F.desc = (long long) P.add_in(K.view.desc, 32 * n);
-        F.uRight = K.view.u_right ? (long long) P.add_in(K.view.u_right, 4 * n) : -1;
-        F.n = (int) n;
-        F.nLevels = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
-        memcpy(F.Rcw, K.Rcw, 36);
-        memcpy(F.tcw, K.tcw, 12);
-        memcpy(F.Ow, K.Ow, 12);
-        F.fx = K.cam.fx; F.fy = K.cam.fy; F.cx = K.cam.cx; F.cy = K.cam.cy; F.mbf = K.cam.mbf;
-        F.minX = K.cam.min_x; F.minY = K.cam.min_y; F.maxX = K.cam.max_x; F.maxY = K.cam.max_y;
-        F.gridInvW = (float) 64 / (K.cam.max_x - K.cam.min_x);   // mfGridElementWidthInv / HeightInv, src/Frame.cc:302-303
-        F.gridInvH = (float) 48 / (K.cam.max_y - K.cam.min_y);
-        predict_scale_steps(K.log_scale_factor, F.nLevels, F.levelStep);
-        for (int l = 0; l < kMaxLevels; l++) {
-            F.scale[l] = l < F.nLevels ? (K.view.scale_factors ? K.view.scale_factors[l] : c->tab.scale[l]) : 1.f;
-            F.invSigma2[l] = l < F.nLevels ? K.inv_level_sigma2[l] : 1.f;
-        }
-    }
+    for (int k = 0; k < n_kf; k++) fuse_kf_fill(c, P, kfs[k], fk[k]);
     const size_t N = (size_t) n_points, KP = (size_t) n_kf * N;
     const size_t iKf = P.add_in(fk.data(), sizeof(FuseKf) * fk.size()), iW = P.add_in(pts->world, 12 * N), iN = P.add_in(pts->normal, 12 * N),
                  iMax = P.add_in(pts->max_dist_inv, 4 * N), iMin = P.add_in(pts->min_dist_inv, 4 * N), iMf = P.add_in(pts->mf_max_distance, 4 * N),
@@ -705,6 +709,142 @@ int ygzf_fuse_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_p
     }
     HIPCHECK(c, hipGetLastError());
     return P.download();
+}
+
+// ---- the loop-closing projection searches (include/ygzf.h; match_kernels.hip: k_proj_search) -------------------------------------------
+// As ygzf_fuse_candidates: validation first, one packed copy each way, nothing in c->held touched.
+static int proj_points_check(ygzf_ctx *c, const ygzf_fuse_points *pts, bool needNormal) {
+    if (!pts->world || (needNormal && !pts->normal) || !pts->max_dist_inv || !pts->min_dist_inv || !pts->mf_max_distance || !pts->desc)
+        return fail(c, YGZF_ERR_INVALID, "null point array");
+    return YGZF_OK;
+}
+static void proj_row_points(PackedTransfer &P, ProjRow &R, const ygzf_fuse_points *pts, int n, bool withNormal, const uint8_t *skip) {
+    const size_t N = (size_t) n;
+    R.world = (long long) P.add_in(pts->world, 12 * N);
+    R.normal = withNormal ? (long long) P.add_in(pts->normal, 12 * N) : -1;
+    R.maxDistInv = (long long) P.add_in(pts->max_dist_inv, 4 * N);
+    R.minDistInv = (long long) P.add_in(pts->min_dist_inv, 4 * N);
+    R.mfMaxDistance = (long long) P.add_in(pts->mf_max_distance, 4 * N);
+    R.mpDesc = (long long) P.add_in(pts->desc, 32 * N);
+    R.skip = skip ? (long long) P.add_in(skip, N) : -1;
+    R.keyMatched = -1;
+    R.nPoints = n;
+}
+static int proj_run(ygzf_ctx *c, PackedTransfer &P, std::vector<ProjRow> &rows, int mode, int maxPoints, int maxKeys, float th, int nBest,
+                    int maxHamming, size_t oI, size_t oD) {
+    int rc;
+    const size_t iR = P.add_in(rows.data(), sizeof(ProjRow) * rows.size());
+    uint8_t *d;
+    if ((rc = P.upload(&d))) return rc;
+    ProjArgs A;
+    A.mode = mode;
+    A.nRows = (int) rows.size(); A.maxPoints = maxPoints;
+    A.slice = 64;   // as k_fuse: SearchAndFuse's tens of keyframes x thousands of points give hundreds of workgroups
+    A.base = d;
+    A.rows = (const ProjRow *) (d + iR);
+    A.th = th;
+    A.nBest = nBest; A.maxHamming = maxHamming;
+    A.bestIdx = (int *) P.d_out(oI);
+    A.bestDist = (int *) P.d_out(oD);
+    {
+        ProfScope ps(c, KK_PROJ);
+        HIPCHECK(c, launch_proj_search(c->stream, A, maxKeys));
+    }
+    HIPCHECK(c, hipGetLastError());
+    return P.download();
+}
+
+int ygzf_fuse_sim3_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
+                              int *best_idx, int *best_dist) {
+    if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
+    if (n_kf < 0 || n_points < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
+    if (n_kf == 0 || n_points == 0) return YGZF_OK;
+    if (!kfs || !pts || !best_idx || !best_dist) return fail(c, YGZF_ERR_INVALID, "null argument");
+    int rc, maxKeys = 0;
+    if ((rc = proj_points_check(c, pts, true))) return rc;
+    for (int k = 0; k < n_kf; k++) {
+        if ((rc = fuse_kf_check(c, kfs[k], k, false))) return rc;
+        maxKeys = std::max(maxKeys, kfs[k].view.n);
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    PackedTransfer P(c);
+    std::vector<ProjRow> rows((size_t) n_kf);
+    memset(rows.data(), 0, sizeof(ProjRow) * rows.size());
+    const size_t N = (size_t) n_points;
+    proj_row_points(P, rows[0], pts, n_points, true, nullptr);   // one copy of the point arrays, shared by every row
+    const long long iS = skip ? (long long) P.add_in(skip, (size_t) n_kf * N) : -1;
+    for (int k = 0; k < n_kf; k++) {
+        if (k) rows[k] = rows[0];
+        fuse_kf_fill(c, P, kfs[k], rows[k].kf);
+        rows[k].skip = skip ? iS + (long long) ((size_t) k * N) : -1;
+        rows[k].out = (long long) ((size_t) k * N);
+    }
+    const size_t oI = P.add_out(best_idx, 4 * N * n_kf), oD = P.add_out(best_dist, 4 * N * n_kf);
+    return proj_run(c, P, rows, PM_FUSE_SCW, n_points, maxKeys, th, 1, 255, oI, oD);
+}
+
+int ygzf_search_by_projection_sim3(ygzf_ctx *c, const ygzf_fuse_kf *kf, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip,
+                                   const uint8_t *key_matched, float th, int n_best, int max_dist, int *cand_idx, int *cand_dist) {
+    if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
+    if (n_points < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
+    if (n_best < 1 || n_best > 8) return fail(c, YGZF_ERR_INVALID, "n_best %d outside 1..8", n_best);
+    if (max_dist < 0 || max_dist > 255) return fail(c, YGZF_ERR_INVALID, "max_dist %d outside 0..255", max_dist);
+    if (n_points == 0) return YGZF_OK;
+    if (!kf || !pts || !cand_idx || !cand_dist) return fail(c, YGZF_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = proj_points_check(c, pts, true)) || (rc = fuse_kf_check(c, *kf, 0, false))) return rc;
+    HIPCHECK(c, hipSetDevice(c->device));
+    PackedTransfer P(c);
+    std::vector<ProjRow> rows(1);
+    memset(rows.data(), 0, sizeof(ProjRow));
+    proj_row_points(P, rows[0], pts, n_points, true, skip);
+    fuse_kf_fill(c, P, *kf, rows[0].kf);
+    if (key_matched && kf->view.n > 0) rows[0].keyMatched = (long long) P.add_in(key_matched, (size_t) kf->view.n);
+    const size_t E = (size_t) n_points * (size_t) n_best;
+    const size_t oI = P.add_out(cand_idx, 4 * E), oD = P.add_out(cand_dist, 4 * E);
+    return proj_run(c, P, rows, PM_PROJ_SCW, n_points, kf->view.n, th, n_best, max_dist, oI, oD);
+}
+
+int ygzf_search_by_sim3(ygzf_ctx *c, const ygzf_fuse_kf *kf1, const ygzf_fuse_kf *kf2, const ygzf_fuse_points *pts1, const ygzf_fuse_points *pts2,
+                        const uint8_t *skip1, const uint8_t *skip2, const ygzf_sim3_transforms *T, float th, int th_dist, int *match1, int *match2,
+                        int *match12, int *nfound) {
+    if (!c || !kf1 || !kf2 || !T || !nfound) return fail(c, YGZF_ERR_INVALID, "null argument");
+    *nfound = 0;
+    const int n1 = kf1->view.n, n2 = kf2->view.n;
+    int rc;
+    if ((rc = fuse_kf_check(c, *kf1, 1, false)) || (rc = fuse_kf_check(c, *kf2, 2, false))) return rc;
+    if ((n1 > 0 && (!pts1 || !match1 || !match12)) || (n2 > 0 && (!pts2 || !match2))) return fail(c, YGZF_ERR_INVALID, "null argument");
+    if ((n1 > 0 && (rc = proj_points_check(c, pts1, false))) || (n2 > 0 && (rc = proj_points_check(c, pts2, false)))) return rc;
+    for (int i = 0; i < n1; i++) match1[i] = match12[i] = -1;
+    for (int i = 0; i < n2; i++) match2[i] = -1;
+    if (n1 == 0 || n2 == 0) return YGZF_OK;   // either direction finds no key, or has no point, and nothing can agree
+    HIPCHECK(c, hipSetDevice(c->device));
+    PackedTransfer P(c);
+    std::vector<ProjRow> rows(2);
+    memset(rows.data(), 0, sizeof(ProjRow) * 2);
+    // row 0: KF1's points into KF2 (R1w, t1w then sR21, t21); row 1: KF2's points into KF1 (R2w, t2w then sR12, t12)
+    proj_row_points(P, rows[0], pts1, n1, false, skip1);
+    fuse_kf_fill(c, P, *kf2, rows[0].kf);
+    memcpy(rows[0].kf.Rcw, T->R1w, 36); memcpy(rows[0].kf.tcw, T->t1w, 12);
+    memcpy(rows[0].R2, T->sR21, 36); memcpy(rows[0].t2, T->t21, 12);
+    rows[0].out = 0;
+    proj_row_points(P, rows[1], pts2, n2, false, skip2);
+    fuse_kf_fill(c, P, *kf1, rows[1].kf);
+    memcpy(rows[1].kf.Rcw, T->R2w, 36); memcpy(rows[1].kf.tcw, T->t2w, 12);
+    memcpy(rows[1].R2, T->sR12, 36); memcpy(rows[1].t2, T->t12, 12);
+    rows[1].out = n1;
+    std::vector<int> bi((size_t) n1 + n2), bd((size_t) n1 + n2);
+    const size_t oI = P.add_out(bi.data(), 4 * bi.size()), oD = P.add_out(bd.data(), 4 * bd.size());
+    if ((rc = proj_run(c, P, rows, PM_SIM3, std::max(n1, n2), std::max(n1, n2), th, 1, 255, oI, oD))) return rc;
+    for (int i = 0; i < n1; i++) match1[i] = bd[i] <= th_dist ? bi[i] : -1;                 // :1119-1121
+    for (int i = 0; i < n2; i++) match2[i] = bd[n1 + i] <= th_dist ? bi[n1 + i] : -1;       // :1195-1197
+    int found = 0;
+    for (int i1 = 0; i1 < n1; i1++) {                                                       // :1200-1213
+        const int idx2 = match1[i1];
+        if (idx2 >= 0 && match2[idx2] == i1) { match12[i1] = idx2; found++; }
+    }
+    *nfound = found;
+    return YGZF_OK;
 }
 
 int ygzf_search_for_initialization(ygzf_ctx *c, const ygzf_frame_view *F1, const ygzf_frame_view *F2, const ygzf_camera *cam, float *prev_matched_xy,
