@@ -316,44 +316,32 @@ struct FiaArgs {                    // Frame::GetFeaturesInArea queries against 
 size_t fia_lds_bytes(int n);
 hipError_t launch_features_in_area(hipStream_t st, const FiaArgs &A);
 
-// ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) candidate search, K keyframes x P points (match_kernels.hip): per pair the
-// bestIdx / bestDist of src/ORBmatcher.cc:764-868 before any map update (-1 / 256: none)
-struct FuseKf {                     // one keyframe; keys / desc / uRight are byte offsets from FuseArgs::base (uRight -1: monocular)
+// The projection searches of one snapshot (match_kernels.hip: k_proj_search<mode>): ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th),
+// K keyframes x P points, per pair the bestIdx / bestDist of src/ORBmatcher.cc:764-868 before any map update (-1 / 256: none); and
+// LoopClosing's Fuse(pKF, Scw, ...), SearchByProjection(pKF, Scw, ...) and the two directions of SearchBySim3.  A row is one target keyframe
+// with its own point list.
+struct FuseKf {                     // one keyframe; keys / desc / uRight are byte offsets from ProjArgs::base (uRight -1: monocular)
     long long keys, desc, uRight;
     int n, nLevels;
     float Rcw[9], tcw[3], Ow[3];
     float fx, fy, cx, cy, mbf, minX, minY, maxX, maxY, gridInvW, gridInvH;
     float levelStep[kMaxLevels];    // PredictScale steps of this keyframe's mfLogScaleFactor / mnScaleLevels (as FrustumArgs::levelStep)
     float scale[kMaxLevels];        // mvScaleFactors
-    float invSigma2[kMaxLevels];    // mvInvLevelSigma2
-};
-struct FuseArgs {
-    int nKf, nPoints, slice;        // slice = points per workgroup; grid = (ceil(nPoints / slice), nKf)
-    const uint8_t *base;
-    const FuseKf *kfs;
-    const float *world, *normal, *maxDistInv, *minDistInv, *mfMaxDistance;   // n x 3, n x 3, n, n, n
-    const uint8_t *mpDesc;          // n x 32
-    const uint8_t *skip;            // nullable: nKf x nPoints, nonzero = no search
-    float th;
-    int *bestIdx, *bestDist;        // nKf x nPoints
+    float invSigma2[kMaxLevels];    // mvInvLevelSigma2 (read by PM_FUSE only)
 };
 size_t fuse_lds_bytes(int maxKeys);
-hipError_t launch_fuse(hipStream_t st, const FuseArgs &A, int maxKeys);
-
-// The loop-closing projection searches (match_kernels.hip: k_proj_search<mode>, the body k_fuse runs as PM_FUSE): Fuse(pKF, Scw, ...),
-// SearchByProjection(pKF, Scw, ...) and the two directions of SearchBySim3.  A row is one target keyframe with its own point list.
 enum ProjMode { PM_FUSE = 0, PM_FUSE_SCW = 1, PM_PROJ_SCW = 2, PM_SIM3 = 3 };
 struct ProjRow {
     FuseKf kf;                      // the target keyframe; Rcw / tcw = the (first) transform, Ow = its camera centre (unused by PM_SIM3)
     float R2[9], t2[3];             // PM_SIM3: the second transform, Pc = R2 * (Rcw * P + tcw) + t2
-    long long world, normal, maxDistInv, minDistInv, mfMaxDistance, mpDesc;   // byte offsets from ProjArgs::base (normal -1: PM_SIM3)
-    long long skip, keyMatched;     // byte offsets, -1: none.  skip: nPoints bytes; keyMatched: kf.n bytes (PM_PROJ_SCW)
+    long long world, normal, maxDistInv, minDistInv, mfMaxDistance, mpDesc;   // byte offsets from ProjArgs::base (normal -1 for PM_SIM3 only)
+    long long skip, keyMatched;     // byte offsets from ProjArgs::base, -1: none.  skip: nPoints bytes; keyMatched: kf.n bytes (PM_PROJ_SCW)
     int nPoints;
     long long out;                  // first point of this row in bestIdx / bestDist (in points; times nBest entries)
 };
 struct ProjArgs {
-    int mode;                       // ProjMode, not PM_FUSE
-    int nRows, maxPoints, slice;    // grid = (ceil(maxPoints / slice), nRows)
+    int mode;                       // any ProjMode
+    int nRows, maxPoints, slice;    // slice = points per workgroup; grid = (ceil(maxPoints / slice), nRows)
     const uint8_t *base;
     const ProjRow *rows;
     float th;

@@ -1992,44 +1992,11 @@ __device__ __forceinline__ void proj_search_point(const FuseKf &K, const float *
         for (int k = found; k < nBest; k++) { outIdx[k] = -1; outDist[k] = 256; }
 }
 
-__global__ __launch_bounds__(kMatchBlock) void k_fuse(FuseArgs A) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
-    __shared__ int s_tmp[kMatchBlock / 64];
-    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
-    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
-    int *list = cellFill + GRID_CELLS;               // n
-    const int kf = blockIdx.y;
-    const FuseKf &K = A.kfs[kf];
-    const ygzf_kp *keys = (const ygzf_kp *) (A.base + K.keys);
-    const uint8_t *kdesc = A.base + K.desc;
-    const float *uRight = K.uRight >= 0 ? (const float *) (A.base + K.uRight) : nullptr;
-    build_grid_lds(keys, K.n, K.minX, K.minY, K.gridInvW, K.gridInvH, cellStart, cellFill, list, s_tmp);
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int p0 = blockIdx.x * A.slice, p1 = min(A.nPoints, p0 + A.slice);
-    for (int i = p0 + wave; i < p1; i += kMatchBlock / 64) {
-        const size_t o = (size_t) kf * A.nPoints + i;
-        if (A.skip && A.skip[o]) {
-            if (lane == 0) { A.bestIdx[o] = -1; A.bestDist[o] = 256; }
-            continue;
-        }
-        proj_search_point<PM_FUSE>(K, nullptr, nullptr, keys, kdesc, uRight, nullptr, cellStart, list, A.world + 3 * (size_t) i,
-                                   A.normal + 3 * (size_t) i, A.minDistInv[i], A.maxDistInv[i], A.mfMaxDistance[i],
-                                   (const uint64_t *) (A.mpDesc + 32 * (size_t) i), A.th, 1, 255, lane, A.bestIdx + o, A.bestDist + o);
-    }
-}
-
 size_t fuse_lds_bytes(int maxKeys) { return fia_lds_bytes(maxKeys); }
 
-hipError_t launch_fuse(hipStream_t st, const FuseArgs &A, int maxKeys) {
-    if (A.nKf <= 0 || A.nPoints <= 0) return hipSuccess;
-    hipError_t e = hipFuncSetAttribute((const void *) k_fuse, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_fuse, dim3((A.nPoints + A.slice - 1) / A.slice, A.nKf), dim3(kMatchBlock), fuse_lds_bytes(maxKeys), st, A);
-    return hipSuccess;
-}
-
-// The loop-closing searches: workgroup = one row (blockIdx.y: a target keyframe with its own point list) x a slice of that row's points.
-// Rows shorter than the longest leave their surplus workgroups idle (SearchBySim3's two directions have N1 and N2 points).
+// Every projection search: workgroup = one row (blockIdx.y: a target keyframe with its own point list) x a slice of that row's points.
+// Rows shorter than the longest leave their surplus workgroups idle (SearchBySim3's two directions have N1 and N2 points).  Fuse's K keyframes
+// x P points are K rows over one copy of the point arrays, row k's skip mask and results at k * P.
 template <int MODE>
 __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
@@ -2043,6 +2010,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
     const FuseKf &K = R.kf;
     const ygzf_kp *keys = (const ygzf_kp *) (A.base + K.keys);
     const uint8_t *kdesc = A.base + K.desc;
+    const float *uRight = MODE == PM_FUSE && K.uRight >= 0 ? (const float *) (A.base + K.uRight) : nullptr;   // the other bodies have no mvuRight term
     const float *world = (const float *) (A.base + R.world);
     const float *normal = R.normal >= 0 ? (const float *) (A.base + R.normal) : nullptr;
     const float *maxInv = (const float *) (A.base + R.maxDistInv), *minInv = (const float *) (A.base + R.minDistInv);
@@ -2060,24 +2028,29 @@ __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
                 for (int k = 0; k < nBest; k++) { A.bestIdx[o + k] = -1; A.bestDist[o + k] = 256; }
             continue;
         }
-        proj_search_point<MODE>(K, R.R2, R.t2, keys, kdesc, nullptr, keyMatched, cellStart, list, world + 3 * (size_t) i,
+        proj_search_point<MODE>(K, R.R2, R.t2, keys, kdesc, uRight, keyMatched, cellStart, list, world + 3 * (size_t) i,
                                 normal ? normal + 3 * (size_t) i : nullptr, minInv[i], maxInv[i], mfMax[i],
                                 (const uint64_t *) (mpDesc + 32 * (size_t) i), A.th, nBest, A.maxHamming, lane, A.bestIdx + o, A.bestDist + o);
     }
 }
 
+template <int MODE>
+static hipError_t launch_proj_mode(hipStream_t st, const ProjArgs &A, int maxKeys) {
+    hipError_t e = hipFuncSetAttribute((const void *) k_proj_search<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k_proj_search<MODE>, dim3((A.maxPoints + A.slice - 1) / A.slice, A.nRows), dim3(kMatchBlock), fuse_lds_bytes(maxKeys), st, A);
+    return hipSuccess;
+}
+
 hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys) {
     if (A.nRows <= 0 || A.maxPoints <= 0) return hipSuccess;
-    const void *fn = A.mode == PM_FUSE_SCW ? (const void *) k_proj_search<PM_FUSE_SCW>
-                     : A.mode == PM_PROJ_SCW ? (const void *) k_proj_search<PM_PROJ_SCW> : (const void *) k_proj_search<PM_SIM3>;
-    hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
-    if (e != hipSuccess) return e;
-    const dim3 grid((A.maxPoints + A.slice - 1) / A.slice, A.nRows), block(kMatchBlock);
-    const size_t lds = fuse_lds_bytes(maxKeys);
-    if (A.mode == PM_FUSE_SCW) hipLaunchKernelGGL(k_proj_search<PM_FUSE_SCW>, grid, block, lds, st, A);
-    else if (A.mode == PM_PROJ_SCW) hipLaunchKernelGGL(k_proj_search<PM_PROJ_SCW>, grid, block, lds, st, A);
-    else hipLaunchKernelGGL(k_proj_search<PM_SIM3>, grid, block, lds, st, A);
-    return hipSuccess;
+    switch (A.mode) {
+    case PM_FUSE: return launch_proj_mode<PM_FUSE>(st, A, maxKeys);
+    case PM_FUSE_SCW: return launch_proj_mode<PM_FUSE_SCW>(st, A, maxKeys);
+    case PM_PROJ_SCW: return launch_proj_mode<PM_PROJ_SCW>(st, A, maxKeys);
+    case PM_SIM3: return launch_proj_mode<PM_SIM3>(st, A, maxKeys);
+    }
+    return hipErrorInvalidValue;
 }
 
 // LDS bytes / per-pair global spill bytes of the carve-up in k_match_last for a given plan

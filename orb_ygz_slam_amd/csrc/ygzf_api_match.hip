@@ -4,12 +4,20 @@
 extern "C" {
 
 // ---- matcher ----------------------------------------------------------------------------------------------------------
+static void grid_inverses(const ygzf_camera &cam, float &invW, float &invH) {   // mfGridElementWidthInv / HeightInv, src/Frame.cc:302-303
+    invW = (float) 64 / (cam.max_x - cam.min_x);
+    invH = (float) 48 / (cam.max_y - cam.min_y);
+}
+
 static void fill_camera(MatchArgs &A, const ygzf_camera *cam, const ygzf_ctx *c) {
     A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy; A.mb = cam->mb; A.mbf = cam->mbf;
     A.minX = cam->min_x; A.minY = cam->min_y; A.maxX = cam->max_x; A.maxY = cam->max_y;
-    A.gridInvW = (float) 64 / (cam->max_x - cam->min_x);  // mfGridElementWidthInv, src/Frame.cc:302-303
-    A.gridInvH = (float) 48 / (cam->max_y - cam->min_y);
+    grid_inverses(*cam, A.gridInvW, A.gridInvH);
     for (int l = 0; l < kMaxLevels; l++) A.scaleFactors[l] = l < c->tab.cfg.nlevels ? c->tab.scale[l] : 1.f;
+}
+// ... and the caller's own scale factors, where a frame view brings them, over the context's
+static void fill_view_scales(MatchArgs &A, const ygzf_frame_view *F) {
+    if (F->scale_factors) for (int l = 0; l < kMaxLevels && l < F->nlevels; l++) A.scaleFactors[l] = F->scale_factors[l];
 }
 
 static int plan_match_lds(ygzf_ctx *c, MatchArgs &A, int nPairs, size_t *ldsBytes) {
@@ -65,6 +73,66 @@ static int plan_match_lds(ygzf_ctx *c, MatchArgs &A, int nPairs, size_t *ldsByte
     *ldsBytes = b;
     return YGZF_OK;
 }
+
+// The k_match_last launch of every entry point below, from a filled MatchArgs.  Under YGZF_DEBUG=match the phase stamps of pair `dbgPair` go to
+// stderr (a blocking copy of their own, so the caller's download may come after).
+static int run_match(ygzf_ctx *c, MatchArgs &A, int nPairs, int dbgPair, const char *label) {
+    int rc;
+    if (c->matchDebug) {
+        if ((rc = ensure(c, c->dTmpC, (size_t) nPairs * 8 * sizeof(long long)))) return rc;
+        A.dbg = (long long *) c->dTmpC.p;
+    }
+    size_t lds;
+    if ((rc = plan_match_lds(c, A, nPairs, &lds))) return rc;
+    {
+        ProfScope ps(c, KK_MATCH);
+        launch_match_last(c->stream, A, nPairs, lds);
+    }
+    HIPCHECK(c, hipGetLastError());
+    if (A.dbg) {
+        long long st[8];
+        HIPCHECK(c, hipMemcpy(st, A.dbg + 8 * dbgPair, sizeof st, hipMemcpyDeviceToHost));
+        fprintf(stderr, "[ygzf match %s, 100MHz ticks] grid %lld  proj %lld  spec %lld  seq %lld  tail %lld  rescans %lld of %lld queries\n", label,
+                st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6], st[7]);
+    }
+    return YGZF_OK;
+}
+
+// One (Cur, Last) pair whose arrays ride the caller's PackedTransfer: Cur's keys / descriptors / mvuRight / owners, the two counts and the three
+// outputs.  add() before P.upload(), fill() after it.  A null ownerOut / matchOut keeps that output on the device (kernel scratch).
+struct PackedPair {
+    const ygzf_frame_view *F;
+    int counts[2];
+    size_t keys, desc, uRight, ownerIn, cnt, owner, match, nmatches;
+    void add(PackedTransfer &P, const ygzf_frame_view *F_, int nLast, const uint8_t *ownerIn_, uint8_t *ownerOut, int *matchOut, int *nmatchesOut) {
+        F = F_;
+        counts[0] = F->n; counts[1] = nLast;
+        const size_t nt = (size_t) F->n;
+        keys = P.add_in(F->keys, nt * sizeof(ygzf_kp));
+        desc = P.add_in(F->desc, nt * 32);
+        uRight = P.add_in(F->u_right, F->u_right ? nt * 4 : 0);
+        ownerIn = P.add_in(ownerIn_, nt);
+        cnt = P.add_in(counts, sizeof counts);
+        owner = P.add_out(ownerOut, nt);
+        match = P.add_out(matchOut, nt * sizeof(int));
+        nmatches = P.add_out(nmatchesOut, sizeof(int));
+    }
+    void fill(MatchArgs &A, const PackedTransfer &P, const uint8_t *dIn) const {
+        A.curKeys = (const ygzf_kp *) (dIn + keys);
+        A.curDesc = dIn + desc;
+        A.curURight = F->u_right ? (const float *) (dIn + uRight) : nullptr;
+        A.ownerIn = dIn + ownerIn;
+        A.curCnt = A.lastCnt = (const int *) (dIn + cnt);   // one pair: count strides 0, Cur's count first
+        A.cntStrideCur = A.cntStrideLast = 0;
+        A.cntOffCur = 0;
+        A.cntOffLast = 1;
+        A.kpStrideCur = A.capCur = counts[0];
+        A.kpStrideLast = A.capLast = counts[1];
+        A.owner = P.d_out(owner);
+        A.match = (int *) P.d_out(match);
+        A.nmatches = (int *) P.d_out(nmatches);
+    }
+};
 
 int ygzf_match_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, float th, int b_mono, int check_level, int check_orientation) {
     if (!c || !cam) return fail(c, YGZF_ERR_INVALID, "null argument");
@@ -124,47 +192,22 @@ int ygzf_match_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, float th, int b_m
     A.nmatches = (int *) c->dNMatch.p;
     A.capCur = G.kpStride;
     A.capLast = G.kpStride;
-    if (c->matchDebug) {
-        if ((rc = ensure(c, c->dTmpC, (size_t) B * 8 * sizeof(long long)))) return rc;
-        A.dbg = (long long *) c->dTmpC.p;
-    }
-    size_t lds;
-    if ((rc = plan_match_lds(c, A, B, &lds))) return rc;
-    {
-        ProfScope ps(c, KK_MATCH);
-        launch_match_last(c->stream, A, B, lds);
-    }
-    HIPCHECK(c, hipGetLastError());
-    if (A.dbg) {
-        long long st[8];
-        const int pp = B > 1 ? 1 : 0;
-        HIPCHECK(c, hipMemcpy(st, A.dbg + 8 * pp, sizeof st, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ygzf match pair %d, 100MHz ticks] grid %lld  proj %lld  spec %lld  seq %lld  tail %lld  rescans %lld of %lld queries\n", pp,
-                st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6], st[7]);
-    }
+    if ((rc = run_match(c, A, B, B > 1 ? 1 : 0, B > 1 ? "pair 1" : "pair 0"))) return rc;
     set_match_pairs(c, B);
     return YGZF_OK;
 }
 
-int ygzf_match_fallbacks(ygzf_ctx *c, unsigned *pairs) {
-    if (!c || !pairs) return fail(c, YGZF_ERR_INVALID, "null argument");
-    *pairs = 0;
+static int read_match_stats(ygzf_ctx *c, unsigned *dst, int words) {
+    if (!c || !dst) return fail(c, YGZF_ERR_INVALID, "null argument");
+    for (int i = 0; i < words; i++) dst[i] = 0;
     if (!c->dMatchStat.p) return YGZF_OK;   // no matcher launch yet
     HIPCHECK(c, hipSetDevice(c->device));
-    HIPCHECK(c, hipMemcpyAsync(pairs, c->dMatchStat.p, sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(dst, c->dMatchStat.p, words * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
-
-int ygzf_match_path_stats(ygzf_ctx *c, unsigned stats[5]) {
-    if (!c || !stats) return fail(c, YGZF_ERR_INVALID, "null argument");
-    for (int i = 0; i < kMatchStatWords; i++) stats[i] = 0;
-    if (!c->dMatchStat.p) return YGZF_OK;   // no matcher launch yet
-    HIPCHECK(c, hipSetDevice(c->device));
-    HIPCHECK(c, hipMemcpyAsync(stats, c->dMatchStat.p, kMatchStatWords * sizeof(unsigned), hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return YGZF_OK;
-}
+int ygzf_match_fallbacks(ygzf_ctx *c, unsigned *pairs) { return read_match_stats(c, pairs, 1); }
+int ygzf_match_path_stats(ygzf_ctx *c, unsigned stats[5]) { return read_match_stats(c, stats, kMatchStatWords); }
 
 int ygzf_match_counts(ygzf_ctx *c, int *nmatches) {
     if (!c || !nmatches) return fail(c, YGZF_ERR_INVALID, "null argument");
@@ -221,70 +264,36 @@ int ygzf_search_by_projection_last(ygzf_ctx *c, const ygzf_frame_view *cur, cons
             if (cur->keys[i].octave < 0 || cur->keys[i].octave >= nl) return fail(c, YGZF_ERR_INVALID, "cur keys[%d].octave %d outside 0..%d", i, cur->keys[i].octave, nl - 1);
     }
     HIPCHECK(c, hipSetDevice(c->device));
-    const size_t nt = cur->n, nq = last_n;
-    int counts[2] = {cur->n, last_n};
+    const size_t nq = last_n;
     float pose[24];
     memcpy(pose, Rcw, 36); memcpy(pose + 9, tcw, 12); memcpy(pose + 12, Rlw, 36); memcpy(pose + 21, tlw, 12);
     PackedTransfer P(c);
-    const size_t oCurK = P.add_in(cur->keys, nt * sizeof(ygzf_kp)), oCurD = P.add_in(cur->desc, nt * 32), oUR = P.add_in(cur->u_right, cur->u_right ? nt * 4 : 0),
-                 oOwn = P.add_in(cur_owner, nt), oLastK = P.add_in(last_keys, nq * sizeof(ygzf_kp)), oMpD = P.add_in(mp_desc, nq * 32),
-                 oWorld = P.add_in(mp_world, nq * 12), oValid = P.add_in(mp_valid, mp_valid ? nq : 0), oOutl = P.add_in(outlier, outlier ? nq : 0),
-                 oObs = P.add_in(mp_has_obs, mp_has_obs ? nq : 0), oCnt = P.add_in(counts, sizeof counts), oPose = P.add_in(pose, sizeof pose);
-    const size_t rOwner = P.add_out(cur_owner, nt), rMatch = P.add_out(cur_match, nt * sizeof(int)), rN = P.add_out(nmatches, sizeof(int));
+    PackedPair pair;
+    pair.add(P, cur, last_n, cur_owner, cur_owner, cur_match, nmatches);
+    const size_t oLastK = P.add_in(last_keys, nq * sizeof(ygzf_kp)), oMpD = P.add_in(mp_desc, nq * 32), oWorld = P.add_in(mp_world, nq * 12),
+                 oValid = P.add_in(mp_valid, mp_valid ? nq : 0), oOutl = P.add_in(outlier, outlier ? nq : 0),
+                 oObs = P.add_in(mp_has_obs, mp_has_obs ? nq : 0), oPose = P.add_in(pose, sizeof pose);
     int rc;
     uint8_t *dIn;
     if ((rc = P.upload(&dIn))) return rc;
     MatchArgs A;
     memset(&A, 0, sizeof A);
     A.maxDist = 100;   // TH_HIGH
-    A.curKeys = (const ygzf_kp *) (dIn + oCurK);
-    A.curDesc = dIn + oCurD;
-    A.curURight = cur->u_right ? (const float *) (dIn + oUR) : nullptr;
-    A.ownerIn = dIn + oOwn;
-    A.curCnt = (const int *) (dIn + oCnt);
-    A.kpStrideCur = (long long) nt;
-    A.cntStrideCur = 0;
-    A.cntOffCur = 0;
+    pair.fill(A, P, dIn);
     A.lastKeys = (const ygzf_kp *) (dIn + oLastK);
     A.mpDesc = dIn + oMpD;
     A.world = (const float *) (dIn + oWorld);
     A.mpValid = mp_valid ? dIn + oValid : nullptr;
     A.outlier = outlier ? dIn + oOutl : nullptr;
     A.hasObs = mp_has_obs ? dIn + oObs : nullptr;
-    A.lastCnt = (const int *) (dIn + oCnt);
-    A.kpStrideLast = (long long) nq;
-    A.cntStrideLast = 0;
-    A.cntOffLast = 1;
     A.poses = (const float *) (dIn + oPose);
     fill_camera(A, cam, c);
-    if (cur->scale_factors) for (int l = 0; l < kMaxLevels && l < cur->nlevels; l++) A.scaleFactors[l] = cur->scale_factors[l];
+    fill_view_scales(A, cur);
     A.th = th;
     A.bMono = b_mono != 0;
     A.checkLevel = check_level != 0;
     A.checkOri = check_orientation != 0;
-    A.owner = P.d_out(rOwner);
-    A.match = (int *) P.d_out(rMatch);
-    A.nmatches = (int *) P.d_out(rN);
-    A.capCur = (int) nt;
-    A.capLast = (int) nq;
-    size_t lds;
-    if ((rc = plan_match_lds(c, A, 1, &lds))) return rc;
-    if (c->matchDebug) {
-        if ((rc = ensure(c, c->dTmpC, 8 * sizeof(long long)))) return rc;
-        A.dbg = (long long *) c->dTmpC.p;
-    }
-    {
-        ProfScope ps(c, KK_MATCH);
-        launch_match_last(c->stream, A, 1, lds);
-    }
-    HIPCHECK(c, hipGetLastError());
-    if ((rc = P.download())) return rc;
-    if (A.dbg) {
-        long long st[8];
-        HIPCHECK(c, hipMemcpy(st, A.dbg, sizeof st, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ygzf match (cur, last), 100MHz ticks] grid %lld  proj %lld  spec %lld  seq %lld  tail %lld  rescans %lld of %lld queries\n",
-                st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6], st[7]);
-    }
+    if ((rc = run_match(c, A, 1, 0, "(cur, last)")) || (rc = P.download())) return rc;
     set_match_pairs(c, 0);
     return YGZF_OK;
 }
@@ -317,6 +326,23 @@ struct FrustumHost {   // host-side inputs of the fused isInFrustum stage (ygzf_
     uint8_t *in_view;
     float *proj_x, *proj_y, *proj_xr, *view_cos;
     int *level;
+};
+
+struct ProjectedQuery {   // projected_match's queries, thresholds and outputs; zero / null: absent
+    int mode;             // 1: F x local MapPoints, 2: Cur x KeyFrame points, 3: SearchForInitialization's window search
+    int n_mp;
+    const uint8_t *track_in_view, *is_bad, *mp_has_obs;
+    const float *proj_x, *proj_y, *proj_xr;
+    const float *view_cos, *mp_angle;   // mode 1 / mode 2
+    const int *scale_level;
+    const uint8_t *mp_desc;
+    float th, nnratio;
+    int check_level, max_dist, check_ori;
+    uint8_t *owner;
+    int *match, *nmatches;
+    const ygzf_kp *last_keys;   // mode 3
+    int *match12;               // mode 3
+    const FrustumHost *fr;      // mode 1: Frame::isInFrustum runs on the device first and supplies the projections
 };
 
 // The frustum inputs join the caller's packed upload (frustum_add_inputs before PackedTransfer::upload, frustum_fill_args after it).
@@ -353,41 +379,38 @@ static void frustum_fill_args(FrustumArgs &A, const uint8_t *dIn, const FrustumO
     A.nLevels = nlevels;
 }
 
-// shared body of the two searches whose queries arrive already projected (mode 1: F x local MapPoints, mode 2: Cur x KeyFrame points)
-static int projected_match(ygzf_ctx *c, int mode, const ygzf_frame_view *F, const ygzf_camera *cam, int n_mp, const uint8_t *track_in_view,
-                           const uint8_t *is_bad, const uint8_t *mp_has_obs, const float *proj_x, const float *proj_y, const float *proj_xr,
-                           const float *view_cos, const int *scale_level, const float *mp_angle, const uint8_t *mp_desc, float th,
-                           int check_level, float nnratio, int max_dist, int check_ori, uint8_t *owner, int *match, int *nmatches,
-                           const ygzf_kp *last_keys = nullptr, int *match12 = nullptr, const FrustumHost *fr = nullptr) {
-    if (!c || !F || !cam || !nmatches) return fail(c, YGZF_ERR_INVALID, "null argument");
-    *nmatches = 0;
+// shared body of the searches whose queries arrive already projected
+static int projected_match(ygzf_ctx *c, const ygzf_frame_view *F, const ygzf_camera *cam, const ProjectedQuery &Q) {
+    const int mode = Q.mode, n_mp = Q.n_mp;
+    const FrustumHost *fr = Q.fr;
+    if (!c || !F || !cam || !Q.nmatches) return fail(c, YGZF_ERR_INVALID, "null argument");
+    *Q.nmatches = 0;
     if (F->n < 0 || n_mp < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
     if (F->n == 0 || n_mp == 0) {
-        for (int i = 0; i < F->n; i++) if (match) match[i] = -1;
+        for (int i = 0; i < F->n; i++) if (Q.match) Q.match[i] = -1;
         return YGZF_OK;
     }
-    if (!F->keys || !F->desc || ((!proj_x || !proj_y) && !fr) || !mp_desc || !owner || !match) return fail(c, YGZF_ERR_INVALID, "null array");
+    if (!F->keys || !F->desc || ((!Q.proj_x || !Q.proj_y) && !fr) || !Q.mp_desc || !Q.owner || !Q.match) return fail(c, YGZF_ERR_INVALID, "null array");
     if (fr) {
         if (mode != 1) return fail(c, YGZF_ERR_INVALID, "fused frustum stage only feeds SearchByProjection(F, MapPoints)");
     } else if (mode != 3) {
-        if (!track_in_view || (mode == 1 && !view_cos) || (mode == 2 && !mp_angle) || !scale_level) return fail(c, YGZF_ERR_INVALID, "null array");
+        if (!Q.track_in_view || (mode == 1 && !Q.view_cos) || (mode == 2 && !Q.mp_angle) || !Q.scale_level) return fail(c, YGZF_ERR_INVALID, "null array");
         for (int i = 0; i < n_mp; i++)
-            if (track_in_view[i] && (scale_level[i] < 0 || scale_level[i] >= kMaxLevels)) return fail(c, YGZF_ERR_INVALID, "scale level out of range");
-    } else if (!last_keys || !match12) return fail(c, YGZF_ERR_INVALID, "null array");
+            if (Q.track_in_view[i] && (Q.scale_level[i] < 0 || Q.scale_level[i] >= kMaxLevels)) return fail(c, YGZF_ERR_INVALID, "scale level out of range");
+    } else if (!Q.last_keys || !Q.match12) return fail(c, YGZF_ERR_INVALID, "null array");
     HIPCHECK(c, hipSetDevice(c->device));
-    const size_t nt = F->n, nq = n_mp;
-    int counts[2] = {F->n, n_mp};
+    const size_t nq = n_mp;
     float pose[24] = {0};
     const int frLevels = F->nlevels > 0 ? F->nlevels : c->tab.cfg.nlevels;
     // one packed copy in, one out (PackedTransfer).  The per-MapPoint arrays the fused isInFrustum stage WRITES (projections, viewing cosine,
     // predicted level, in-view flag) live in the output half so that the caller's optional copies of them ride the same copy back.
     PackedTransfer P(c);
-    const size_t oCurK = P.add_in(F->keys, nt * sizeof(ygzf_kp)), oCurD = P.add_in(F->desc, nt * 32), oUR = P.add_in(F->u_right, F->u_right ? nt * 4 : 0),
-                 oOwn = P.add_in(owner, nt), oLastK = P.add_in(last_keys, last_keys ? nq * sizeof(ygzf_kp) : 0), oMpD = P.add_in(mp_desc, nq * 32),
-                 oBad = P.add_in(is_bad, is_bad ? nq : 0), oObs = P.add_in(mp_has_obs, mp_has_obs ? nq : 0), oCnt = P.add_in(counts, sizeof counts),
-                 oPose = P.add_in(pose, sizeof pose);
+    PackedPair pair;   // mode 3 keeps owner / match as kernel scratch (the caller derives them from match12)
+    pair.add(P, F, n_mp, Q.owner, mode == 3 ? nullptr : Q.owner, mode == 3 ? nullptr : Q.match, Q.nmatches);
+    const size_t oLastK = P.add_in(Q.last_keys, Q.last_keys ? nq * sizeof(ygzf_kp) : 0), oMpD = P.add_in(Q.mp_desc, nq * 32),
+                 oBad = P.add_in(Q.is_bad, Q.is_bad ? nq : 0), oObs = P.add_in(Q.mp_has_obs, Q.mp_has_obs ? nq : 0), oPose = P.add_in(pose, sizeof pose);
     size_t oPX = 0, oPY = 0, oPXR = 0, oVC = 0, oLv = 0, oTV = 0;
-    size_t rPX = 0, rPY = 0, rPXR = 0, rVC = 0, rLv = 0, rTV = 0, rM12 = 0, rOwner = 0, rMatch = 0;
+    size_t rPX = 0, rPY = 0, rPXR = 0, rVC = 0, rLv = 0, rTV = 0, rM12 = 0;
     FrustumOffsets FO;
     int rc;
     if (fr) {
@@ -399,19 +422,16 @@ static int projected_match(ygzf_ctx *c, int mode, const ygzf_frame_view *F, cons
         rPXR = P.add_out(fr->proj_xr, nq * 4);
         rVC = P.add_out(fr->view_cos, nq * 4);
     } else {
-        oPX = P.add_in(proj_x, nq * 4);
-        oPY = P.add_in(proj_y, nq * 4);
-        oPXR = P.add_in(proj_xr, proj_xr ? nq * 4 : 0);
+        oPX = P.add_in(Q.proj_x, nq * 4);
+        oPY = P.add_in(Q.proj_y, nq * 4);
+        oPXR = P.add_in(Q.proj_xr, Q.proj_xr ? nq * 4 : 0);
         if (mode != 3) {
-            oTV = P.add_in(track_in_view, nq);
-            oVC = P.add_in(mode == 2 ? mp_angle : view_cos, nq * 4);
-            oLv = P.add_in(scale_level, nq * 4);
+            oTV = P.add_in(Q.track_in_view, nq);
+            oVC = P.add_in(mode == 2 ? Q.mp_angle : Q.view_cos, nq * 4);
+            oLv = P.add_in(Q.scale_level, nq * 4);
         }
     }
-    if (mode == 3) rM12 = P.add_out(match12, nq * sizeof(int));
-    rOwner = P.add_out(mode == 3 ? nullptr : owner, nt);            // mode 3 keeps them as kernel scratch (the caller derives them from match12)
-    rMatch = P.add_out(mode == 3 ? nullptr : (void *) match, nt * sizeof(int));
-    const size_t rN = P.add_out(nmatches, sizeof(int));
+    if (mode == 3) rM12 = P.add_out(Q.match12, nq * sizeof(int));
     uint8_t *dIn;
     if ((rc = P.upload(&dIn))) return rc;
     const float *dPX, *dY, *dXR, *dVC;
@@ -434,7 +454,7 @@ static int projected_match(ygzf_ctx *c, int mode, const ygzf_frame_view *F, cons
     } else {
         dPX = (const float *) (dIn + oPX);
         dY = (const float *) (dIn + oPY);
-        dXR = proj_xr ? (const float *) (dIn + oPXR) : nullptr;
+        dXR = Q.proj_xr ? (const float *) (dIn + oPXR) : nullptr;
         dVC = (const float *) (dIn + oVC);     // unused in mode 3
         dLv = (const int *) (dIn + oLv);
         dTV = mode != 3 ? dIn + oTV : nullptr;
@@ -448,23 +468,15 @@ static int projected_match(ygzf_ctx *c, int mode, const ygzf_frame_view *F, cons
     // MapPoint without any free candidate and writes mvpMapPoints[-1] (:1431-1432, undefined; its callers pass 100 and 64).  Defined here, as in the
     // oracle, as: no candidate, no match.  (Found by the fuzzer once its KeyFrame leg compared with the oracle: 256 reached the kernel, whose keys
     // reserve dist > 255 for "nothing" -- wrong counts and an out-of-bounds store.)
-    A.maxDist = max_dist > 255 ? 255 : max_dist < 0 ? 0 : max_dist;
-    A.curKeys = (const ygzf_kp *) (dIn + oCurK);
-    A.curDesc = dIn + oCurD;
-    A.curURight = F->u_right ? (const float *) (dIn + oUR) : nullptr;
-    A.ownerIn = dIn + oOwn;
-    A.curCnt = (const int *) (dIn + oCnt);
-    A.kpStrideCur = (long long) nt;
-    A.lastKeys = (const ygzf_kp *) (dIn + (last_keys ? oLastK : 0));   // not read in modes 1, 2: any valid address
+    A.maxDist = Q.max_dist > 255 ? 255 : Q.max_dist < 0 ? 0 : Q.max_dist;
+    pair.fill(A, P, dIn);
+    A.lastKeys = (const ygzf_kp *) (dIn + (Q.last_keys ? oLastK : 0));   // not read in modes 1, 2: any valid address
     A.mpDesc = dIn + oMpD;
     A.world = dPX;     // unused in these modes
     A.mpValid = dTV;
     A.match12 = mode == 3 ? (int *) P.d_out(rM12) : nullptr;
-    A.outlier = is_bad ? dIn + oBad : nullptr;
-    A.hasObs = mp_has_obs ? dIn + oObs : nullptr;
-    A.lastCnt = (const int *) (dIn + oCnt);
-    A.kpStrideLast = (long long) nq;
-    A.cntOffLast = 1;
+    A.outlier = Q.is_bad ? dIn + oBad : nullptr;
+    A.hasObs = Q.mp_has_obs ? dIn + oObs : nullptr;
     A.poses = (const float *) (dIn + oPose);
     A.mpProjX = dPX;
     A.mpProjY = dY;
@@ -472,39 +484,40 @@ static int projected_match(ygzf_ctx *c, int mode, const ygzf_frame_view *F, cons
     A.mpViewCos = dVC;
     A.mpAngle = dVC;
     A.mpLevel = dLv;
-    A.nnratio = nnratio;
+    A.nnratio = Q.nnratio;
     fill_camera(A, cam, c);
-    if (F->scale_factors) for (int l = 0; l < kMaxLevels && l < F->nlevels; l++) A.scaleFactors[l] = F->scale_factors[l];
-    A.th = th;
+    fill_view_scales(A, F);
+    A.th = Q.th;
     A.bMono = 1;
-    A.checkLevel = check_level != 0;
-    A.checkOri = check_ori != 0;
-    A.owner = P.d_out(rOwner);
-    A.match = (int *) P.d_out(rMatch);
-    A.nmatches = (int *) P.d_out(rN);
-    A.capCur = (int) nt;
-    A.capLast = (int) nq;
-    size_t lds;
-    if ((rc = plan_match_lds(c, A, 1, &lds))) return rc;
-    if (c->matchDebug) {
-        if ((rc = ensure(c, c->dTmpC, 8 * sizeof(long long)))) return rc;
-        A.dbg = (long long *) c->dTmpC.p;
-    }
-    {
-        ProfScope ps(c, KK_MATCH);
-        launch_match_last(c->stream, A, 1, lds);
-    }
-    HIPCHECK(c, hipGetLastError());
-    if (A.dbg) {
-        long long st[8];
-        HIPCHECK(c, hipMemcpy(st, A.dbg, sizeof st, hipMemcpyDeviceToHost));
-        fprintf(stderr, "[ygzf match mode %d, 100MHz ticks] grid %lld  proj %lld  spec %lld  seq %lld  tail %lld  rescans %lld of %lld queries\n", mode,
-                st[1] - st[0], st[2] - st[1], st[3] - st[2], st[4] - st[3], st[5] - st[4], st[6], st[7]);
-    }
-    if ((rc = P.download())) return rc;
+    A.checkLevel = Q.check_level != 0;
+    A.checkOri = Q.check_ori != 0;
+    char label[16];
+    snprintf(label, sizeof label, "mode %d", mode);
+    if ((rc = run_match(c, A, 1, 0, label)) || (rc = P.download())) return rc;
     set_match_pairs(c, 0);
     return YGZF_OK;
 }
+
+// The node-wise searches' outputs (SearchByBoW, SearchForTriangulation): the match array, preset to -1 on the device, and a block of counters
+// ([0] nmatches, [4 .. 34) the rotation histogram), zeroed.  add() before P.upload(), clear() after it, count() after P.download().
+struct NodeSearchOut {
+    int tail[64];
+    size_t oMatch, oTail, matchBytes;
+    void add(PackedTransfer &P, int *match, size_t n) {
+        matchBytes = 4 * n;
+        oMatch = P.add_out(match, matchBytes);
+        oTail = P.add_out(tail, sizeof tail);
+    }
+    int *match(const PackedTransfer &P) const { return (int *) P.d_out(oMatch); }
+    int *nmatches(const PackedTransfer &P) const { return (int *) P.d_out(oTail); }
+    int *hist(const PackedTransfer &P) const { return nmatches(P) + 4; }
+    int clear(ygzf_ctx *c, const PackedTransfer &P) const {
+        HIPCHECK(c, hipMemsetAsync(match(P), 0xFF, matchBytes, c->stream));
+        HIPCHECK(c, hipMemsetAsync(nmatches(P), 0, sizeof tail, c->stream));
+        return YGZF_OK;
+    }
+    int count() const { return tail[0]; }
+};
 
 int ygzf_search_by_bow(ygzf_ctx *c, int n_nodes, const int *kf_off, const int *kf_idx, const int *f_off, const int *f_idx, int n_kf,
                        const uint8_t *kf_valid, const ygzf_kp *kf_keys, const uint8_t *kf_desc, int n_f, const ygzf_kp *f_keys, const uint8_t *f_desc,
@@ -528,22 +541,19 @@ int ygzf_search_by_bow(ygzf_ctx *c, int n_nodes, const int *kf_off, const int *k
     const size_t iKO = P.add_in(kf_off, 4 * (size_t) (n_nodes + 1)), iKI = P.add_in(kf_idx, 4 * (size_t) nk), iFO = P.add_in(f_off, 4 * (size_t) (n_nodes + 1)),
                  iFI = P.add_in(f_idx, 4 * (size_t) nfi), iKV = P.add_in(kf_valid, (size_t) n_kf), iKK = P.add_in(kf_keys, sizeof(ygzf_kp) * (size_t) n_kf),
                  iKD = P.add_in(kf_desc, 32 * (size_t) n_kf), iFK = P.add_in(f_keys, sizeof(ygzf_kp) * (size_t) n_f), iFD = P.add_in(f_desc, 32 * (size_t) n_f);
-    int tail[64];   // [0] nmatches, [4 .. 34) rotation histogram
-    const size_t oM = P.add_out(match, 4 * (size_t) n_f), oT = P.add_out(tail, sizeof tail);
+    NodeSearchOut out;
+    out.add(P, match, (size_t) n_f);
     uint8_t *d;
-    if ((rc = P.upload(&d)) || (rc = ensure(c, c->dOwner, (size_t) n_f))) return rc;
-    int *dMatch = (int *) P.d_out(oM), *dTail = (int *) P.d_out(oT);
-    HIPCHECK(c, hipMemsetAsync(dMatch, 0xFF, 4 * (size_t) n_f, c->stream));
-    HIPCHECK(c, hipMemsetAsync(dTail, 0, sizeof tail, c->stream));
+    if ((rc = P.upload(&d)) || (rc = ensure(c, c->dOwner, (size_t) n_f)) || (rc = out.clear(c, P))) return rc;
     {
         ProfScope ps(c, KK_BOWNODES);
         launch_bow(c->stream, n_nodes, (const int *) (d + iKO), (const int *) (d + iKI), (const int *) (d + iFO), (const int *) (d + iFI), d + iKV,
-                   (const ygzf_kp *) (d + iKK), d + iKD, n_f, (const ygzf_kp *) (d + iFK), d + iFD, nnratio, check_orientation != 0, dMatch,
-                   (unsigned char *) c->dOwner.p, dTail + 4, dTail);
+                   (const ygzf_kp *) (d + iKK), d + iKD, n_f, (const ygzf_kp *) (d + iFK), d + iFD, nnratio, check_orientation != 0, out.match(P),
+                   (unsigned char *) c->dOwner.p, out.hist(P), out.nmatches(P));
     }
     HIPCHECK(c, hipGetLastError());
     if ((rc = P.download())) return rc;
-    *nmatches = tail[0];
+    *nmatches = out.count();
     set_match_pairs(c, 0);
     return YGZF_OK;
 }
@@ -596,10 +606,10 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
                  iD1 = P.add_in(kf1->desc, 32 * N1), iD2 = P.add_in(kf2->desc, 32 * N2), iM1 = P.add_in(has_mp1, N1), iM2 = P.add_in(has_mp2, N2),
                  iU1 = P.add_in(kf1->u_right, kf1->u_right ? 4 * N1 : 0), iU2 = P.add_in(kf2->u_right, kf2->u_right ? 4 * N2 : 0),
                  iSf = P.add_in(sf.data(), 4 * (size_t) L), iSg = P.add_in(sg.data(), 4 * (size_t) L);
-    int tail[64];   // [0] nmatches, [4 .. 34) rotation histogram
-    const size_t oM = P.add_out(match12, 4 * N1), oT = P.add_out(tail, sizeof(tail));
+    NodeSearchOut out;
+    out.add(P, match12, N1);
     uint8_t *d;
-    if ((rc = P.upload(&d)) || (rc = ensure(c, c->dGen[9], N1 + 16))) return rc;
+    if ((rc = P.upload(&d)) || (rc = ensure(c, c->dGen[9], N1 + 16)) || (rc = out.clear(c, P))) return rc;
     A.nEntries = ne1; A.nNodes = n_nodes; A.n1 = n1;
     A.off1 = (const int *) (d + iO1); A.idx1 = (const int *) (d + iI1); A.off2 = (const int *) (d + iO2); A.idx2 = (const int *) (d + iI2);
     A.keys1 = (const ygzf_kp *) (d + iK1); A.keys2 = (const ygzf_kp *) (d + iK2);
@@ -608,19 +618,17 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
     A.uR2 = kf2->u_right ? (const float *) (d + iU2) : nullptr;
     A.sf2 = (const float *) (d + iSf); A.sigma2 = (const float *) (d + iSg);
     A.onlyStereo = only_stereo != 0; A.checkOri = check_orientation != 0;
-    A.match12 = (int *) P.d_out(oM);
+    A.match12 = out.match(P);
     A.binOf = (unsigned char *) c->dGen[9].p;
-    A.nmatches = (int *) P.d_out(oT);
-    A.hist = A.nmatches + 4;
-    HIPCHECK(c, hipMemsetAsync(P.d_out(oM), 0xFF, 4 * N1, c->stream));
-    HIPCHECK(c, hipMemsetAsync(P.d_out(oT), 0, sizeof(tail), c->stream));
+    A.nmatches = out.nmatches(P);
+    A.hist = out.hist(P);
     {
         ProfScope ps(c, KK_TRI);
         launch_triangulation(c->stream, A);
     }
     HIPCHECK(c, hipGetLastError());
     if ((rc = P.download())) return rc;
-    *nmatches = tail[0];
+    *nmatches = out.count();
     set_match_pairs(c, 0);
     return YGZF_OK;
 }
@@ -655,8 +663,7 @@ static void fuse_kf_fill(ygzf_ctx *c, PackedTransfer &P, const ygzf_fuse_kf &K, 
     memcpy(F.Ow, K.Ow, 12);
     F.fx = K.cam.fx; F.fy = K.cam.fy; F.cx = K.cam.cx; F.cy = K.cam.cy; F.mbf = K.cam.mbf;
     F.minX = K.cam.min_x; F.minY = K.cam.min_y; F.maxX = K.cam.max_x; F.maxY = K.cam.max_y;
-    F.gridInvW = (float) 64 / (K.cam.max_x - K.cam.min_x);   // mfGridElementWidthInv / HeightInv, src/Frame.cc:302-303
-    F.gridInvH = (float) 48 / (K.cam.max_y - K.cam.min_y);
+    grid_inverses(K.cam, F.gridInvW, F.gridInvH);
     predict_scale_steps(K.log_scale_factor, F.nLevels, F.levelStep);
     for (int l = 0; l < kMaxLevels; l++) {
         F.scale[l] = l < F.nLevels ? (K.view.scale_factors ? K.view.scale_factors[l] : c->tab.scale[l]) : 1.f;
@@ -664,55 +671,9 @@ static void fuse_kf_fill(ygzf_ctx *c, PackedTransfer &P, const ygzf_fuse_kf &K, 
     }
 }
 
-// ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) candidate search, src/ORBmatcher.cc:764-868 (include/ygzf.h).  Validation
-// first; one packed copy in (every keyframe's keys / descriptors / mvuRight, the point arrays, the skip mask, the per-keyframe tables), one out.
-// Touches nothing in c->held: only the packed staging area is written.
-int ygzf_fuse_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
-                         int *best_idx, int *best_dist) {
-    if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (n_kf < 0 || n_points < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
-    if (n_kf == 0 || n_points == 0) return YGZF_OK;
-    if (!kfs || !pts || !best_idx || !best_dist) return fail(c, YGZF_ERR_INVALID, "null argument");
-    if (!pts->world || !pts->normal || !pts->max_dist_inv || !pts->min_dist_inv || !pts->mf_max_distance || !pts->desc)
-        return fail(c, YGZF_ERR_INVALID, "null point array");
-    int maxKeys = 0, rc;
-    for (int k = 0; k < n_kf; k++) {
-        if ((rc = fuse_kf_check(c, kfs[k], k, true))) return rc;
-        maxKeys = std::max(maxKeys, kfs[k].view.n);
-    }
-    HIPCHECK(c, hipSetDevice(c->device));
-    PackedTransfer P(c);
-    std::vector<FuseKf> fk((size_t) n_kf);
-    for (int k = 0; k < n_kf; k++) fuse_kf_fill(c, P, kfs[k], fk[k]);
-    const size_t N = (size_t) n_points, KP = (size_t) n_kf * N;
-    const size_t iKf = P.add_in(fk.data(), sizeof(FuseKf) * fk.size()), iW = P.add_in(pts->world, 12 * N), iN = P.add_in(pts->normal, 12 * N),
-                 iMax = P.add_in(pts->max_dist_inv, 4 * N), iMin = P.add_in(pts->min_dist_inv, 4 * N), iMf = P.add_in(pts->mf_max_distance, 4 * N),
-                 iD = P.add_in(pts->desc, 32 * N), iS = P.add_in(skip, skip ? KP : 0);
-    const size_t oI = P.add_out(best_idx, 4 * KP), oD = P.add_out(best_dist, 4 * KP);
-    uint8_t *d;
-    if ((rc = P.upload(&d))) return rc;
-    FuseArgs A;
-    A.nKf = n_kf; A.nPoints = n_points;
-    A.slice = 64;   // points per workgroup (four per wave): a forward pass of 20 keyframes x 1 500 points and a reverse pass of 1 x 30 000 both give ~500 workgroups
-    A.base = d;
-    A.kfs = (const FuseKf *) (d + iKf);
-    A.world = (const float *) (d + iW); A.normal = (const float *) (d + iN);
-    A.maxDistInv = (const float *) (d + iMax); A.minDistInv = (const float *) (d + iMin); A.mfMaxDistance = (const float *) (d + iMf);
-    A.mpDesc = d + iD;
-    A.skip = skip ? d + iS : nullptr;
-    A.th = th;
-    A.bestIdx = (int *) P.d_out(oI);
-    A.bestDist = (int *) P.d_out(oD);
-    {
-        ProfScope ps(c, KK_FUSE);
-        HIPCHECK(c, launch_fuse(c->stream, A, maxKeys));
-    }
-    HIPCHECK(c, hipGetLastError());
-    return P.download();
-}
-
-// ---- the loop-closing projection searches (include/ygzf.h; match_kernels.hip: k_proj_search) -------------------------------------------
-// As ygzf_fuse_candidates: validation first, one packed copy each way, nothing in c->held touched.
+// ---- the projection searches of one snapshot (include/ygzf.h; match_kernels.hip: k_proj_search) -------------------------------------------
+// Validation first; one packed copy in (every keyframe's keys / descriptors / mvuRight, the point arrays, the skip masks, the row table), one
+// out.  Nothing in c->held is touched: only the packed staging area is written.
 static int proj_points_check(ygzf_ctx *c, const ygzf_fuse_points *pts, bool needNormal) {
     if (!pts->world || (needNormal && !pts->normal) || !pts->max_dist_inv || !pts->min_dist_inv || !pts->mf_max_distance || !pts->desc)
         return fail(c, YGZF_ERR_INVALID, "null point array");
@@ -730,7 +691,7 @@ static void proj_row_points(PackedTransfer &P, ProjRow &R, const ygzf_fuse_point
     R.keyMatched = -1;
     R.nPoints = n;
 }
-static int proj_run(ygzf_ctx *c, PackedTransfer &P, std::vector<ProjRow> &rows, int mode, int maxPoints, int maxKeys, float th, int nBest,
+static int proj_run(ygzf_ctx *c, PackedTransfer &P, std::vector<ProjRow> &rows, int mode, int slot, int maxPoints, int maxKeys, float th, int nBest,
                     int maxHamming, size_t oI, size_t oD) {
     int rc;
     const size_t iR = P.add_in(rows.data(), sizeof(ProjRow) * rows.size());
@@ -739,7 +700,7 @@ static int proj_run(ygzf_ctx *c, PackedTransfer &P, std::vector<ProjRow> &rows, 
     ProjArgs A;
     A.mode = mode;
     A.nRows = (int) rows.size(); A.maxPoints = maxPoints;
-    A.slice = 64;   // as k_fuse: SearchAndFuse's tens of keyframes x thousands of points give hundreds of workgroups
+    A.slice = 64;   // points per workgroup (four per wave): a forward Fuse of 20 keyframes x 1 500 points and a reverse one of 1 x 30 000 both give ~500 workgroups
     A.base = d;
     A.rows = (const ProjRow *) (d + iR);
     A.th = th;
@@ -747,15 +708,17 @@ static int proj_run(ygzf_ctx *c, PackedTransfer &P, std::vector<ProjRow> &rows, 
     A.bestIdx = (int *) P.d_out(oI);
     A.bestDist = (int *) P.d_out(oD);
     {
-        ProfScope ps(c, KK_PROJ);
+        ProfScope ps(c, slot);
         HIPCHECK(c, launch_proj_search(c->stream, A, maxKeys));
     }
     HIPCHECK(c, hipGetLastError());
     return P.download();
 }
 
-int ygzf_fuse_sim3_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
-                              int *best_idx, int *best_dist) {
+// K keyframes x one point list, a row per keyframe: ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th), src/ORBmatcher.cc:764-868
+// (PM_FUSE; reads mvInvLevelSigma2) and LoopClosing's Fuse(pKF, Scw, ...), :888-1004 (PM_FUSE_SCW)
+static int fuse_rows(ygzf_ctx *c, int mode, bool needSigma, int slot, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts,
+                     const uint8_t *skip, float th, int *best_idx, int *best_dist) {
     if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
     if (n_kf < 0 || n_points < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
     if (n_kf == 0 || n_points == 0) return YGZF_OK;
@@ -763,7 +726,7 @@ int ygzf_fuse_sim3_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, in
     int rc, maxKeys = 0;
     if ((rc = proj_points_check(c, pts, true))) return rc;
     for (int k = 0; k < n_kf; k++) {
-        if ((rc = fuse_kf_check(c, kfs[k], k, false))) return rc;
+        if ((rc = fuse_kf_check(c, kfs[k], k, needSigma))) return rc;
         maxKeys = std::max(maxKeys, kfs[k].view.n);
     }
     HIPCHECK(c, hipSetDevice(c->device));
@@ -780,7 +743,17 @@ int ygzf_fuse_sim3_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, in
         rows[k].out = (long long) ((size_t) k * N);
     }
     const size_t oI = P.add_out(best_idx, 4 * N * n_kf), oD = P.add_out(best_dist, 4 * N * n_kf);
-    return proj_run(c, P, rows, PM_FUSE_SCW, n_points, maxKeys, th, 1, 255, oI, oD);
+    return proj_run(c, P, rows, mode, slot, n_points, maxKeys, th, 1, 255, oI, oD);
+}
+
+int ygzf_fuse_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
+                         int *best_idx, int *best_dist) {
+    return fuse_rows(c, PM_FUSE, true, KK_FUSE, n_kf, kfs, n_points, pts, skip, th, best_idx, best_dist);
+}
+
+int ygzf_fuse_sim3_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
+                              int *best_idx, int *best_dist) {
+    return fuse_rows(c, PM_FUSE_SCW, false, KK_PROJ, n_kf, kfs, n_points, pts, skip, th, best_idx, best_dist);
 }
 
 int ygzf_search_by_projection_sim3(ygzf_ctx *c, const ygzf_fuse_kf *kf, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip,
@@ -802,7 +775,7 @@ int ygzf_search_by_projection_sim3(ygzf_ctx *c, const ygzf_fuse_kf *kf, int n_po
     if (key_matched && kf->view.n > 0) rows[0].keyMatched = (long long) P.add_in(key_matched, (size_t) kf->view.n);
     const size_t E = (size_t) n_points * (size_t) n_best;
     const size_t oI = P.add_out(cand_idx, 4 * E), oD = P.add_out(cand_dist, 4 * E);
-    return proj_run(c, P, rows, PM_PROJ_SCW, n_points, kf->view.n, th, n_best, max_dist, oI, oD);
+    return proj_run(c, P, rows, PM_PROJ_SCW, KK_PROJ, n_points, kf->view.n, th, n_best, max_dist, oI, oD);
 }
 
 int ygzf_search_by_sim3(ygzf_ctx *c, const ygzf_fuse_kf *kf1, const ygzf_fuse_kf *kf2, const ygzf_fuse_points *pts1, const ygzf_fuse_points *pts2,
@@ -835,7 +808,7 @@ int ygzf_search_by_sim3(ygzf_ctx *c, const ygzf_fuse_kf *kf1, const ygzf_fuse_kf
     rows[1].out = n1;
     std::vector<int> bi((size_t) n1 + n2), bd((size_t) n1 + n2);
     const size_t oI = P.add_out(bi.data(), 4 * bi.size()), oD = P.add_out(bd.data(), 4 * bd.size());
-    if ((rc = proj_run(c, P, rows, PM_SIM3, std::max(n1, n2), std::max(n1, n2), th, 1, 255, oI, oD))) return rc;
+    if ((rc = proj_run(c, P, rows, PM_SIM3, KK_PROJ, std::max(n1, n2), std::max(n1, n2), th, 1, 255, oI, oD))) return rc;
     for (int i = 0; i < n1; i++) match1[i] = bd[i] <= th_dist ? bi[i] : -1;                 // :1119-1121
     for (int i = 0; i < n2; i++) match2[i] = bd[n1 + i] <= th_dist ? bi[n1 + i] : -1;       // :1195-1197
     int found = 0;
@@ -857,8 +830,14 @@ int ygzf_search_for_initialization(ygzf_ctx *c, const ygzf_frame_view *F1, const
     for (int i = 0; i < F1->n; i++) { px[i] = prev_matched_xy[2 * i]; py[i] = prev_matched_xy[2 * i + 1]; }
     std::vector<uint8_t> owner(F2->n, 0);
     std::vector<int> match21(F2->n, -1);
-    int rc = projected_match(c, 3, F2, cam, F1->n, nullptr, nullptr, nullptr, px.data(), py.data(), nullptr, nullptr, nullptr, nullptr, F1->desc,
-                             (float) window_size, 0, nnratio, 50, check_orientation, owner.data(), match21.data(), nmatches, F1->keys, matches12);
+    ProjectedQuery Q = {};
+    Q.mode = 3; Q.n_mp = F1->n;
+    Q.proj_x = px.data(); Q.proj_y = py.data();
+    Q.mp_desc = F1->desc;
+    Q.th = (float) window_size; Q.nnratio = nnratio; Q.max_dist = 50; Q.check_ori = check_orientation;
+    Q.owner = owner.data(); Q.match = match21.data(); Q.nmatches = nmatches;
+    Q.last_keys = F1->keys; Q.match12 = matches12;
+    int rc = projected_match(c, F2, cam, Q);
     if (rc) return rc;
     for (int i = 0; i < F1->n; i++)      // :470-474 update prev matched
         if (matches12[i] >= 0) {
@@ -872,8 +851,14 @@ int ygzf_search_by_projection_mappoints(ygzf_ctx *c, const ygzf_frame_view *F, c
                                         const uint8_t *is_bad, const uint8_t *mp_has_obs, const float *proj_x, const float *proj_y,
                                         const float *proj_xr, const float *view_cos, const int *scale_level, const uint8_t *mp_desc, float th,
                                         int check_level, float nnratio, uint8_t *owner, int *match, int *nmatches) {
-    return projected_match(c, 1, F, cam, n_mp, track_in_view, is_bad, mp_has_obs, proj_x, proj_y, proj_xr, view_cos, scale_level, nullptr, mp_desc,
-                           th, check_level, nnratio, 100, 0, owner, match, nmatches);
+    ProjectedQuery Q = {};
+    Q.mode = 1; Q.n_mp = n_mp;
+    Q.track_in_view = track_in_view; Q.is_bad = is_bad; Q.mp_has_obs = mp_has_obs;
+    Q.proj_x = proj_x; Q.proj_y = proj_y; Q.proj_xr = proj_xr; Q.view_cos = view_cos; Q.scale_level = scale_level;
+    Q.mp_desc = mp_desc;
+    Q.th = th; Q.check_level = check_level; Q.nnratio = nnratio; Q.max_dist = 100;
+    Q.owner = owner; Q.match = match; Q.nmatches = nmatches;
+    return projected_match(c, F, cam, Q);
 }
 
 int ygzf_predict_scale_steps(float log_scale_factor, int nlevels, float *steps) {
@@ -918,8 +903,13 @@ int ygzf_search_local_points(ygzf_ctx *c, const ygzf_frame_view *F, const ygzf_c
                              int *nmatches, uint8_t *in_view, float *proj_x, float *proj_y, float *proj_xr, int *level, float *view_cos) {
     if (!in) return fail(c, YGZF_ERR_INVALID, "null argument");
     FrustumHost fr = {in, in_view, proj_x, proj_y, proj_xr, view_cos, level};
-    return projected_match(c, 1, F, cam, n_mp, nullptr, nullptr, mp_has_obs, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, mp_desc, th, check_level,
-                           nnratio, 100, 0, owner, match, nmatches, nullptr, nullptr, &fr);
+    ProjectedQuery Q = {};
+    Q.mode = 1; Q.n_mp = n_mp;
+    Q.mp_has_obs = mp_has_obs; Q.mp_desc = mp_desc;
+    Q.th = th; Q.check_level = check_level; Q.nnratio = nnratio; Q.max_dist = 100;
+    Q.owner = owner; Q.match = match; Q.nmatches = nmatches;
+    Q.fr = &fr;
+    return projected_match(c, F, cam, Q);
 }
 
 int ygzf_features_in_area(ygzf_ctx *c, const ygzf_camera *cam, int n_keys, const ygzf_kp *keys, int n_queries, const float *xyr, const int *levels,
@@ -935,54 +925,43 @@ int ygzf_features_in_area(ygzf_ctx *c, const ygzf_camera *cam, int n_keys, const
     const size_t qBytes = (size_t) n_queries * 12, lBytes = levels ? (size_t) n_queries * 8 : 0;
     const size_t oBytes = (size_t) n_queries * (size_t) cap * 4, nBytes = (size_t) n_queries * 4;
     const size_t nPad = (nBytes + 15) & ~(size_t) 15;
-    if ((size_t) n_keys * sizeof(ygzf_kp) + qBytes + lBytes + nBytes + oBytes <= kPackedMax) {   // one packed copy each way
-        PackedTransfer P(c);
-        const size_t iK = P.add_in(keys, (size_t) n_keys * sizeof(ygzf_kp)), iQ = P.add_in(xyr, qBytes), iL = P.add_in(levels, lBytes);
+    const size_t kBytes = (size_t) n_keys * sizeof(ygzf_kp);
+    const bool packed = kBytes + qBytes + lBytes + nBytes + oBytes <= kPackedMax;   // one packed copy each way; beyond that, staged copies
+    FiaArgs A;
+    A.n = n_keys;
+    A.minX = cam->min_x; A.minY = cam->min_y;
+    grid_inverses(*cam, A.gridInvW, A.gridInvH);
+    A.nq = n_queries;
+    A.cap = cap;
+    PackedTransfer P(c);
+    if (packed) {
+        const size_t iK = P.add_in(keys, kBytes), iQ = P.add_in(xyr, qBytes), iL = P.add_in(levels, lBytes);
         const size_t oN = P.add_out(out_n, nBytes), oI = P.add_out(out_idx, oBytes);
         uint8_t *d;
         if ((rc = P.upload(&d))) return rc;
-        FiaArgs A;
         A.keys = (const ygzf_kp *) (d + iK);
-        A.n = n_keys;
-        A.minX = cam->min_x; A.minY = cam->min_y;
-        A.gridInvW = (float) 64 / (cam->max_x - cam->min_x);
-        A.gridInvH = (float) 48 / (cam->max_y - cam->min_y);
-        A.nq = n_queries;
         A.xyr = (const float *) (d + iQ);
         A.levels = levels ? (const int *) (d + iL) : nullptr;
-        A.cap = cap;
         A.outN = (int *) P.d_out(oN);
         A.outIdx = (int *) P.d_out(oI);
-        {
-            ProfScope ps(c, KK_GRID);
-            HIPCHECK(c, launch_features_in_area(c->stream, A));
-        }
-        HIPCHECK(c, hipGetLastError());
-        return P.download();
+    } else {
+        if ((rc = ensure(c, c->dTmpA, kBytes + 64)) || (rc = ensure(c, c->dTmpB, qBytes + lBytes + 64)) || (rc = ensure(c, c->dTmpC, nPad + oBytes + 64)))
+            return rc;
+        if (n_keys > 0) HIPCHECK(c, hipMemcpyAsync(c->dTmpA.p, keys, kBytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(c->dTmpB.p, xyr, qBytes, hipMemcpyHostToDevice, c->stream));
+        if (levels) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->dTmpB.p + qBytes, levels, lBytes, hipMemcpyHostToDevice, c->stream));
+        A.keys = (const ygzf_kp *) c->dTmpA.p;
+        A.xyr = (const float *) c->dTmpB.p;
+        A.levels = levels ? (const int *) ((uint8_t *) c->dTmpB.p + qBytes) : nullptr;
+        A.outN = (int *) c->dTmpC.p;
+        A.outIdx = (int *) ((uint8_t *) c->dTmpC.p + nPad);
     }
-    if ((rc = ensure(c, c->dTmpA, (size_t) n_keys * sizeof(ygzf_kp) + 64)) || (rc = ensure(c, c->dTmpB, qBytes + lBytes + 64)) ||
-        (rc = ensure(c, c->dTmpC, nPad + oBytes + 64)))
-        return rc;
-    if (n_keys > 0) HIPCHECK(c, hipMemcpyAsync(c->dTmpA.p, keys, (size_t) n_keys * sizeof(ygzf_kp), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(c->dTmpB.p, xyr, qBytes, hipMemcpyHostToDevice, c->stream));
-    if (levels) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->dTmpB.p + qBytes, levels, lBytes, hipMemcpyHostToDevice, c->stream));
-    FiaArgs A;
-    A.keys = (const ygzf_kp *) c->dTmpA.p;
-    A.n = n_keys;
-    A.minX = cam->min_x; A.minY = cam->min_y;
-    A.gridInvW = (float) 64 / (cam->max_x - cam->min_x);   // mfGridElementWidthInv / HeightInv, src/Frame.cc:302-303
-    A.gridInvH = (float) 48 / (cam->max_y - cam->min_y);
-    A.nq = n_queries;
-    A.xyr = (const float *) c->dTmpB.p;
-    A.levels = levels ? (const int *) ((uint8_t *) c->dTmpB.p + qBytes) : nullptr;
-    A.cap = cap;
-    A.outN = (int *) c->dTmpC.p;
-    A.outIdx = (int *) ((uint8_t *) c->dTmpC.p + nPad);
     {
         ProfScope ps(c, KK_GRID);
         HIPCHECK(c, launch_features_in_area(c->stream, A));
     }
     HIPCHECK(c, hipGetLastError());
+    if (packed) return P.download();
     HIPCHECK(c, hipMemcpyAsync(out_n, A.outN, nBytes, hipMemcpyDeviceToHost, c->stream));
     if (oBytes) HIPCHECK(c, hipMemcpyAsync(out_idx, A.outIdx, oBytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
@@ -1078,8 +1057,14 @@ int ygzf_search_by_projection_kf(ygzf_ctx *c, const ygzf_frame_view *cur, const 
     if (!c || !cur || !owner) return fail(c, YGZF_ERR_INVALID, "null argument");
     if (orb_dist < 0 || orb_dist > 256) return fail(c, YGZF_ERR_INVALID, "ORBdist %d outside 0..256", orb_dist);
     for (int i = 0; i < cur->n; i++) owner[i] = owner[i] ? 2 : 0;   // `if (CurrentFrame.mvpMapPoints[i2]) continue;` (:1419): any MapPoint blocks
-    return projected_match(c, 2, cur, cam, n_mp, valid, nullptr, nullptr, proj_x, proj_y, nullptr, nullptr, pred_level, kf_angle, mp_desc, th, 0,
-                           0.f, orb_dist, check_orientation, owner, match, nmatches);
+    ProjectedQuery Q = {};
+    Q.mode = 2; Q.n_mp = n_mp;
+    Q.track_in_view = valid;
+    Q.proj_x = proj_x; Q.proj_y = proj_y; Q.mp_angle = kf_angle; Q.scale_level = pred_level;
+    Q.mp_desc = mp_desc;
+    Q.th = th; Q.max_dist = orb_dist; Q.check_ori = check_orientation;
+    Q.owner = owner; Q.match = match; Q.nmatches = nmatches;
+    return projected_match(c, cur, cam, Q);
 }
 
 }  // extern "C"

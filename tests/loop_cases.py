@@ -23,7 +23,7 @@ def norm_cv(v):
 
 
 def norm_float(v):
-    """k_fuse's (Eigen's) float form."""
+    """PM_FUSE's (Eigen's) float form."""
     return np.sqrt((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2])
 
 

@@ -294,6 +294,38 @@ def test_fuse_batch_equals_single_calls(ex):
     assert (bi[3] == bi[0]).all() and (bi[4] == bi[2]).all()
 
 
+def test_fuse_rows_at_slice_edge_and_empty_keyframe(oracle, ex):
+    """The row table where it can go wrong: 65 points (one past the 64-point slice), a keyframe without keys between a stereo and a mono one,
+    skips at the last point of row 0 and the first of row 2."""
+    rng = np.random.default_rng(21)
+    stereo = make_kf(rng, 752, 480, 300, 8, 1.2, np.eye(3), [0, 0, 0], mbf=40.0, stereo_frac=0.6)
+    empty = dict(make_kf(rng, 752, 480, 16, 8, 1.2, _rot(0.01, 0.02, 0.0), [0.05, 0.0, 0.02]))
+    empty["keys"], empty["desc"] = empty["keys"][:0], empty["desc"][:0]
+    mono = make_kf(rng, 640, 480, 200, 5, 1.5, _rot(-0.03, 0.04, 0.0), [-0.2, 0.05, 0.1])
+    assert stereo["u_right"] is not None and (stereo["u_right"] >= 0).any() and mono["u_right"] is None and len(empty["keys"]) == 0
+    kfs = [stereo, empty, mono]
+    P = 65
+    pts = make_points(rng, [stereo, mono], P)
+    # the two skipped entries are points that do find a key when searched, so a skip byte read at the wrong offset shows
+    hit = [ref_candidates(oracle, kf, *pts, 3.0)[0] >= 0 for kf in (stereo, mono)]
+    a = int(np.nonzero(hit[0])[0][0])
+    b = int(np.nonzero(hit[1] & (np.arange(P) != a))[0][0])
+    order = [b] + [i for i in range(P) if i not in (a, b)] + [a]
+    pts = tuple(x[order] for x in pts)
+    skip = np.zeros((3, P), np.uint8)
+    skip[0, 64] = skip[2, 0] = 1
+    bi, bd = ex.fuse_candidates(kfs, *pts, skip=skip)
+    assert bi.shape == (3, P) and bd.shape == (3, P)
+    for k, kf in enumerate(kfs):
+        ri, rd = ref_candidates(oracle, kf, *pts, 3.0, skip[k])
+        assert (bi[k] == ri).all() and (bd[k] == rd).all(), (k, np.nonzero((bi[k] != ri) | (bd[k] != rd))[0][:10])
+        si, sd = ex.fuse_candidates([kf], *pts, skip=skip[k:k + 1])
+        assert (si[0] == bi[k]).all() and (sd[0] == bd[k]).all(), k
+    assert (bi[skip != 0] == -1).all() and (bd[skip != 0] == 256).all()
+    assert (bi[1] == -1).all() and (bd[1] == 256).all()
+    assert (bi[0, :64] >= 0).any() and (bi[2, 1:] >= 0).any()           # the rows next to the empty one do find keys
+
+
 def test_fuse_reverse_shape(oracle, ex):
     """1 keyframe x 30 000 points (LocalMapping.cc:1273-1304) equals 1 000-point chunks, and the restatement on a sample."""
     rng = np.random.default_rng(11)
