@@ -169,3 +169,29 @@ def test_round6_entry_points_report_misuse():
     with pytest.raises(YgzfError):
         a.phase_clocks(0)                                                              # the product library carries no stamps
     a.close(); b.close()
+
+
+def test_stereo_right_keypoint_count_limit():
+    """ygzf_compute_stereo_matches packs the right index into 16 bits of its key: 65536 right keypoints are refused with YGZF_ERR_INVALID (-1)
+    and a message, nothing is launched, and 65535 are accepted on the same context afterwards"""
+    from orb_ygz_slam_amd import Extractor
+    from orb_ygz_slam_amd.capi import KP_DTYPE, load_library
+    L = load_library()
+    w, h = 320, 240
+    ex = Extractor(300, 1.2, 4, 20, 7, max_width=w, max_height=h, max_batch=2)
+    img = np.ascontiguousarray(synth_frame(9, w, h))
+    p = lambda a: a.ctypes.data_as(C.c_void_p)
+    kl = np.zeros(1, KP_DTYPE)
+    kl["x"], kl["y"] = 200.0, 100.0
+    dl = np.zeros((1, 32), np.uint8)
+    kr = np.zeros(65536, KP_DTYPE)
+    kr["x"], kr["y"] = 180.0, 100.0
+    dr = np.full((65536, 32), 255, np.uint8)
+    dr[65534] = 0                                                        # the one right keypoint within the descriptor threshold: the last index
+    ur, dp = np.full(1, 7, np.float32), np.full(1, 7, np.float32)
+    call = lambda n: L.ygzf_compute_stereo_matches(ex.h, p(img), p(img), w, h, w, 1, p(kl), p(dl), n, p(kr), p(dr), 0.5, 32.0, p(ur), p(dp))
+    assert call(65536) == -1 and b"keypoint counts" in L.ygzf_last_error(ex.h)
+    assert ur[0] == 7 and dp[0] == 7                                     # refused before anything was written
+    assert call(65535) == 0
+    assert ur[0] != 7 and dp[0] != 7
+    ex.close()
