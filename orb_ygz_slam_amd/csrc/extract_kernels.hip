@@ -3,6 +3,8 @@
 //   k_pyr_resize   K1  ORBextractor::ComputePyramid          (reference src/ORBextractor.cc:1129-1150, cv::resize)
 //   k_fast_quads   K2  ComputeKeyPointsOctTree cell loop     (:747-781, cv::FAST 9/16 + per-cell NMS + threshold fallback)
 //   k_octree       K4  DistributeOctTree                      (:533-723) as sort-by-path-key + breadth-first on ranges
+//                      phases: oct_carve | oct_attempt { oct_cell_prefix, oct_key_tables, oct_path_keys, oct_hand_over, oct_order,
+//                      oct_subdivide { oct_head, oct_full_pass, oct_expand_round } } | oct_best_hist / oct_best_sorted | oct_emit_keypoints
 //   k_describe     K5+K6+K7  IC_Angle (:77-101), GaussianBlur 7x7 s=2 (:1010) on the 37x37 patch only,
 //                            computeOrbDescriptor (:105-149)
 //
@@ -1340,686 +1342,664 @@ struct OctShared {  // carved out of dynamic LDS
     unsigned *cand;           // LDS-resident candidate sort buffer(s), optional: 2 x ldsCand (the second one over the node arrays), 4 x ldsCand with global node arrays
 };
 
-// kGlobalNodes: the 19 per-list-position arrays live in a global arena (nodeArena, 19 * cap ints per (frame, level)) instead of LDS --
-// configurations whose per-level feature budget is too large for the LDS plan (e.g. one level with > 2000 features).
+// one of the two node lists: a select between two pointers per array (indexing nlo[] with a run-time value would put OctShared into scratch memory)
+struct OctNodes { int *lo, *cnt, *dep; };
+__device__ __forceinline__ OctNodes oct_nodes(const OctShared &S, int which) {
+    return OctNodes{which ? S.nlo[1] : S.nlo[0], which ? S.ncnt[1] : S.ncnt[0], which ? S.ndep[1] : S.ndep[0]};
+}
 constexpr unsigned kNoKeypoint = 0xFFFFFFFFu;   // procRec.y of a processing position without a keypoint
-//
-// kHist (the plan of configurations whose levels hold tens of thousands of candidates -- 1920x1080 / 4000, 3840x2160 / 8000): NO SORT.  What the
-// tree passes ask of the sorted key array is (a) the child boundaries of a node = counts of candidates per key prefix and (b) the best
-// response per final node.  Both come from a histogram over the key prefixes of depth dm (nIni << 2 dm <= histBins bins, LDS atomics while the
-// keys are computed) and its exclusive prefix sum PS: the node (lo, cnt, dep) starts at the aligned bin f0 with PS[f0] == lo, its child
-// boundaries are PS[f0 + c * 4^(dm - dep - 1)] -- the very values digit_bounds3 finds in the sorted array, so the tree passes run unchanged; the
-// best response per node is one more pass over the candidates (bin -> final node table, LDS atomic max).  A level of 60 000 candidates spent
-// 1.4-1.7 ms in four scattered radix passes through global memory (4.6 GB written per 64-frame launch against 0.9 GB of keys) and 0.2-0.5 ms
-// in tree passes whose every boundary search was 11 dependent global reads; here the candidates are read twice, linearly, and the tree passes
-// stay in LDS.  A tree that wants to split a node BELOW depth dm (a few very crowded spots in an otherwise empty level) raises s_overflow and
-// the workgroup starts over on the sorting path -- same result, the old speed.
-//
-// kBlock: threads per workgroup (1024 / 512 / 256).  The host sizes it per launch with the levels it carries (ygzf_api.hip, plan_oct_sort): a 1024-thread
-// workgroup holds half a CU's wave slots whatever its LDS, so that two of them left no room for the other contexts' FAST and describe waves.  Every loop
-// strides by it; the results do not depend on it.
-template <bool kGlobalNodes, bool kHist, int kBlock>
-__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kHist ? 4 : 8, 8))) void k_octree(const LevelGeom *__restrict__ geom, int nlevels, int levelBase,
-                                                      const unsigned short *__restrict__ cellCnt,
-                                                      const unsigned *__restrict__ slots, int totalCells,
-                                                      long long totalSlots, unsigned *__restrict__ candKey0,
-                                                      unsigned *__restrict__ candVal0, unsigned *__restrict__ candKey1,
-                                                      unsigned *__restrict__ candVal1, unsigned *__restrict__ candXY,
-                                                      long long candStride, unsigned *__restrict__ lvlKpXY,
-                                                      unsigned char *__restrict__ lvlKpScore, int *__restrict__ lvlKpCnt,
-                                                      int *__restrict__ lvlCandCnt, uint2 *__restrict__ procRec,
-                                                      int kpStride, int cap, int ldsCand, long long *dbg, int *__restrict__ nodeArena,
-                                                      int regionInts, int histBins, int *gHist, int *gDone, int doneTarget, int spinBudget) {
-    static_assert(!(kGlobalNodes && kHist), "the histogram plan keeps the node arrays in LDS");
-    extern __shared__ __attribute__((aligned(16))) int dyn[];
-    __shared__ int histT[radix_hist_ints(kBlock / 64)];
-    __shared__ int s_tmp[20];
-    __shared__ unsigned long long s_tmp64[17];
-    __shared__ int s_n, s_nE, s_cut, s_flagA, s_overflow;
-    __shared__ int s_head[4];
-    const int tid = threadIdx.x;
-    const int l = blockIdx.x + levelBase, f = blockIdx.y;
-    // kHist, launches of a few frames (gridDim.z > 1): a level of one 3840x2160 frame is 60 000 candidates whose keys took ONE compute unit 95 us while
-    // 250 others had nothing to do.  The workgroups z = 1 .. gridDim.z - 1 of a (level, frame) are helpers: each computes the keys of its share of the
-    // candidates (keys and positions in the global candidate arrays as always, its bin counts into a slice of gHist), releases, bumps gDone and
-    // leaves; workgroup 0 does its own share, waits for the others, adds their counts to its own and goes on alone.  gDone only ever grows (the host
-    // passes the value this launch brings it to): should the helpers not arrive within the spin budget -- every compute unit held by waiting
-    // workgroups 0 of many contexts at once -- workgroup 0 stops waiting, computes the whole level itself and ignores the slices; helpers that come
-    // late write the same keys to the same places and bump a counter nobody reads again before the next launch.  The host launches helpers only while ALL workgroups of the launch fit the device together (ygzf_api.hip), so nobody waits for
-    // a workgroup that cannot start.
-    const int parts = kHist && gHist ? (int) gridDim.z : 1, part = kHist ? (int) blockIdx.z : 0;
-#define OSTAMP(k) do { if (dbg && tid == 0 && f == 0 && part == 0) dbg[l * 8 + (k)] = wall_clock64(); } while (0)
-    OSTAMP(0);
-    int bfsEv = 0;
+
+// What the phases of one (level, frame) workgroup share.  The first part is fixed once the workgroup has read its level; the second part is what
+// an attempt at the level (oct_attempt) leaves for the next phase.
+struct OctLevel {
+    int tid, l, f, parts, part;   // workgroups of this (level, frame) and this one's index: helpers are 1 .. parts - 1 (histogram plan, gridDim.z)
+    LevelGeom g;
+    OctShared S;
+    int nCells, passEv;           // (passEv: tree-pass stamps written so far, -DYGZF_PHASE_CLOCK)
+    int *PS;                      // kHist: histBins + 1 ints behind the region the cell table, the key tables and (later) the node arrays share
+    unsigned *candB;              // LDS node arrays, sort plan: the candidates' second sort buffer (2 * ldsCand words) lies over the cell table and the
+                                  // node arrays -- both idle while the candidates are sorted; the first one (2 * ldsCand words) behind that region
+    unsigned *xTab;               // key tables (oct_key_tables): xTab, yTab = xTab + lenX, orgTab = yTab + lenY
+    const unsigned short *cc;
+    const unsigned *sl;           // this frame's and level's cell counts and slots
+    unsigned *key0, *val0, *key1, *val1, *xy;   // candidate arrays: global scratch, or LDS when M <= ldsCand
+    int dm, nBins, binShift;      // kHist: depth of the histogram's key prefixes, its bins, key >> binShift = bin
+    int *lvlCnt, *gd, *gh;        // this level's keypoint count; helpers: its hand-over counter and the first helper's slice of histBins counts
+    int *histT, *tmp, *flagA, *overflow, *cut, *head;   // the kernel's static LDS
+    unsigned long long *tmp64;
+    // ---- per attempt ----
+    bool hist, inLds;             // this attempt runs the histogram plan; the candidates are sorted in LDS
+    int M;                        // candidates of the level
+    unsigned *skeys, *svals;      // where the ordered keys / values ended up (sort plan)
+    int n, cur, nE;               // the tree: nodes of list `cur`, expandable ones among them
+};
+
+// of an attempt: the tree stands / this workgroup is finished with the level (a helper, or no candidates) / once more without helpers / once more on the sorting path
+enum OctOutcome { kOctDone, kOctLeft, kOctAgainAlone, kOctAgainSorted };
+__device__ __forceinline__ void oct_stamp(const OctLevel &w, long long *dbg, int k) {
+    if (dbg && w.tid == 0 && w.f == 0 && w.part == 0) dbg[w.l * 8 + k] = wall_clock64();
+}
 // (the tree passes' own stamps exist in the -DYGZF_PHASE_CLOCK build only: eight conditional stamps inside the pass loops cost the product build 10 % more vector
 // instructions in this kernel -- 23 k per frame -- although the branch is never taken)
-#ifndef YGZF_PHASE_CLOCK
-#define OBFS(nn) do { } while (0)
-#else
-#define OBFS(nn) do { if (dbg && tid == 0 && f == 0 && part == 0 && bfsEv < 8) { dbg[16 * 8 + 16 + l * 16 + 2 * bfsEv] = (nn); dbg[16 * 8 + 16 + l * 16 + 2 * bfsEv + 1] = wall_clock64(); bfsEv++; } } while (0)
+__device__ __forceinline__ void oct_pass_stamp(OctLevel &w, long long *dbg, int nn) {
+#ifdef YGZF_PHASE_CLOCK
+    if (dbg && w.tid == 0 && w.f == 0 && w.part == 0 && w.passEv < 8) { dbg[16 * 8 + 16 + w.l * 16 + 2 * w.passEv] = nn; dbg[16 * 8 + 16 + w.l * 16 + 2 * w.passEv + 1] = wall_clock64(); w.passEv++; }
 #endif
-    const LevelGeom g = geom[l];
-    const int nCells = g.nCols * g.nRows;
-    int *lvlCnt = lvlKpCnt + f * nlevels + l;
-    int *gd = kHist && parts > 1 ? gDone + (f * nlevels + l) : nullptr;
-    auto helper_leaves = [&]() { if (tid == 0) __hip_atomic_fetch_add(gd, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT); };   // (every helper, whatever way it leaves)
-    if (nCells <= 0 || g.nCols <= 0) {
-        if (part != 0) { helper_leaves(); return; }
-        if (tid == 0) { *lvlCnt = 0; lvlCandCnt[f * nlevels + l] = 0; }
-        for (int i = tid; i < g.kpCap; i += kBlock) procRec[(long long) f * kpStride + g.kpBase + i] = make_uint2(0u, kNoKeypoint);
-        return;
+}
+__device__ __forceinline__ void oct_helper_leaves(const OctLevel &w) {   // (every helper, whatever way it leaves)
+    if (w.tid == 0) __hip_atomic_fetch_add(w.gd, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// a level without cells or without candidates: no keypoints, no work for k_describe (a helper just leaves)
+template <int kBlock> __device__ __forceinline__ void oct_empty_level(const OctArgs &a, const OctLevel &w) {
+    if (w.part != 0) { oct_helper_leaves(w); return; }
+    if (w.tid == 0) { *w.lvlCnt = 0; a.lvlCandCnt[w.f * a.nlevels + w.l] = 0; }
+    for (int i = w.tid; i < w.g.kpCap; i += kBlock) a.procRec[(long long) w.f * a.kpStride + w.g.kpBase + i] = make_uint2(0u, kNoKeypoint);
+}
+
+// ---- LDS carve-up ----
+template <bool kGlobalNodes, bool kHist> __device__ __forceinline__ void oct_carve(const OctArgs &a, OctLevel &w, int *dyn) {
+    OctShared &S = w.S;
+    const int cap = a.cap;
+    int *p = dyn;
+    w.PS = nullptr; w.candB = nullptr; S.cellPref = p;
+    if (kHist) w.PS = dyn + a.regionInts;      // (the node arrays start at dyn as well: the cell prefix table is dead once the keys exist)
+    else p += (w.nCells + 1 + 3) & ~3;         // (16-byte aligned node arrays: cap is a multiple of 4)
+    int *candLds = p;
+    if (kGlobalNodes) p = a.nodeArena + ((long long) blockIdx.y * a.nlevels + w.l) * (19LL * cap);
+    for (int b = 0; b < 2; b++) { S.nlo[b] = p; p += cap; S.ncnt[b] = p; p += cap; S.ndep[b] = p; p += cap; }
+    S.kArr = p; p += cap; S.eArr = p; p += cap; S.sArr = p; p += cap;
+    S.b1 = p; p += cap; S.b2 = p; p += cap; S.b3 = p; p += cap;
+    S.Epos = p; p += cap; S.Ecnt = p; p += cap;
+    for (int b = 0; b < 2; b++) { S.sk[b] = (unsigned *) p; p += cap; S.sv[b] = (unsigned *) p; p += cap; }
+    S.flag = p; p += cap;
+    if (kGlobalNodes) S.cand = (unsigned *) candLds;   // 4 * ldsCand words: key/val double buffers when the level's candidates fit
+    else if (!kHist) {
+        w.candB = (unsigned *) dyn;
+        S.cand = (unsigned *) dyn + max((int) (p - dyn), 2 * a.ldsCand);   // (p - dyn: a multiple of 4, as is ldsCand)
     }
-    OctShared S;
-    int *PS = nullptr;        // kHist: histBins + 1 ints behind the region the cell table, the key tables and (later) the node arrays share
-    unsigned *candB = nullptr;   // LDS node arrays, sort plan: the candidates' second sort buffer (2 * ldsCand words) lies over the cell table and the
-                                 // node arrays -- both idle while the candidates are sorted; the first one (2 * ldsCand words) behind that region
-    {
-        int *p = dyn;
-        S.cellPref = p;
-        if (kHist) PS = dyn + regionInts;        // (the node arrays start at dyn as well: the cell prefix table is dead once the keys exist)
-        else p += (nCells + 1 + 3) & ~3;         // (16-byte aligned node arrays: cap is a multiple of 4)
-        int *candLds = p;
-        if (kGlobalNodes) p = nodeArena + ((long long) blockIdx.y * nlevels + l) * (19LL * cap);
-        for (int b = 0; b < 2; b++) { S.nlo[b] = p; p += cap; S.ncnt[b] = p; p += cap; S.ndep[b] = p; p += cap; }
-        S.kArr = p; p += cap; S.eArr = p; p += cap; S.sArr = p; p += cap;
-        S.b1 = p; p += cap; S.b2 = p; p += cap; S.b3 = p; p += cap;
-        S.Epos = p; p += cap; S.Ecnt = p; p += cap;
-        for (int b = 0; b < 2; b++) { S.sk[b] = (unsigned *) p; p += cap; S.sv[b] = (unsigned *) p; p += cap; }
-        S.flag = p; p += cap;
-        if (kGlobalNodes) S.cand = (unsigned *) candLds;   // 4 * ldsCand words: key/val double buffers when the level's candidates fit
-        else if (!kHist) {
-            candB = (unsigned *) dyn;
-            S.cand = (unsigned *) dyn + max((int) (p - dyn), 2 * ldsCand);   // (p - dyn: a multiple of 4, as is ldsCand)
+    // the key tables, when they are used: in the node arrays (idle until the tree passes), kHist: behind the cell prefix table
+    w.xTab = (unsigned *) (kHist ? dyn + w.nCells + 1 : S.nlo[0]);
+}
+
+// ---- 1. candidate offsets per cell (cell-major order == the reference's vToDistributeKeys order); returns M ----
+template <int kBlock> __device__ __forceinline__ int oct_cell_prefix(const OctArgs &a, const OctLevel &w) {
+    const OctShared &S = w.S;
+    for (int i = w.tid; i < w.nCells; i += kBlock) S.cellPref[i] = w.cc[i];
+    __syncthreads();
+    const int M = block_scan_array(S.cellPref, w.nCells, w.tmp);
+    if (w.tid == 0) { S.cellPref[w.nCells] = M; if (w.part == 0) a.lvlCandCnt[w.f * a.nlevels + w.l] = M; }
+    __syncthreads();
+    return M;
+}
+
+// ---- 2a. key tables ----
+// A workgroup has ONE CU: 2800 candidates x ~300 instructions of cell decode (a division), root (a float division) and ten
+// subdivision steps were 7 us of a 752x480 level 0.  x and y subdivide independently, so the key is the OR of a per-column word
+// (root, x bits spread to the even positions) and a per-row word (y bits on the odd positions): both tables and the cells' origins
+// are built once per workgroup in the node arrays (idle until the tree passes) when they fit there.
+template <int kBlock> __device__ __forceinline__ void oct_key_tables(const OctLevel &w, int lenX, int lenY) {
+    const LevelGeom &g = w.g;
+    unsigned *xTab = w.xTab, *yTab = xTab + lenX, *orgTab = yTab + lenY;
+    auto spread = [](unsigned v) {
+        v = (v | (v << 8)) & 0x00FF00FFu;
+        v = (v | (v << 4)) & 0x0F0F0F0Fu;
+        v = (v | (v << 2)) & 0x33333333u;
+        return (v | (v << 1)) & 0x55555555u;
+    };
+    auto halvings = [&](int v, int lo, int hi) {   // one bit per subdivision of [lo, hi) with DivideNode's ceil-halving: v in the upper part?
+        unsigned k = 0;
+        for (int d = 0; d < g.depth; d++) {
+            const int m = lo + ((hi - lo + 1) >> 1);
+            const unsigned b = v >= m;
+            if (b) lo = m; else hi = m;
+            k = (k << 1) | b;
+        }
+        return k;
+    };
+    for (int t = w.tid; t < lenX + lenY + w.nCells; t += kBlock) {
+        if (t < lenX) {
+            const int root = min((int) ((float) t / g.hX), g.nIni - 1);
+            xTab[t] = ((unsigned) root << (2 * g.depth)) | spread(halvings(t, (int) (g.hX * (float) root), (int) (g.hX * (float) (root + 1))));
+        } else if (t < lenX + lenY) {
+            yTab[t - lenX] = spread(halvings(t - lenX, 0, g.regH)) << 1;
+        } else {
+            const int c = t - lenX - lenY;
+            const int ci = c / g.nCols, cj = c - ci * g.nCols;
+            orgTab[c] = (unsigned) (cj * g.wCell) | ((unsigned) (ci * g.hCell) << 16);
         }
     }
-    const unsigned short *cc = cellCnt + (long long) f * totalCells + g.cellBase;
-    const unsigned *sl = slots + (long long) f * totalSlots + g.slotBase;
-    unsigned *key0 = candKey0 + (long long) f * candStride + g.candBase;   // global scratch (used when M > ldsCand)
-    unsigned *val0 = candVal0 + (long long) f * candStride + g.candBase;
-    unsigned *key1 = candKey1 + (long long) f * candStride + g.candBase;
-    unsigned *val1 = candVal1 + (long long) f * candStride + g.candBase;
-    unsigned *xy = candXY + (long long) f * candStride + g.candBase;
-
-    // kHist: depth dm of the histogram's key prefixes -- as deep as the bin budget allows (a level whose tree is fully resolved at dm cannot overflow)
-    int dm = 0;
-    if (kHist) {
-        dm = g.depth;
-        while (dm > 0 && ((long long) g.nIni << (2 * dm)) > (long long) histBins) dm--;
-    }
-    bool useHist = kHist && dm >= 1;
-    const int nBins = g.nIni << (2 * dm);
-    const int binShift = 2 * (g.depth - dm);
-    if (part != 0 && !useHist) { helper_leaves(); return; }   // (no histogram for this level: workgroup 0 sorts, alone)
-    bool alone = false;                  // workgroup 0 gave up waiting for its helpers
-    int *gh = kHist && parts > 1 ? gHist + ((long long) f * nlevels + l) * (parts - 1) * histBins : nullptr;   // one slice of histBins counts per helper
-restart:   // (kHist: a second time, on the sorting path, after the tree asked for a split below depth dm)
-    if (kHist && tid == 0) s_overflow = 0;
-    // ---- 1. candidate offsets per cell (cell-major order == the reference's vToDistributeKeys order) ----
-    for (int i = tid; i < nCells; i += kBlock) S.cellPref[i] = cc[i];
     __syncthreads();
-    const int M = block_scan_array(S.cellPref, nCells, s_tmp);
-    if (tid == 0) { S.cellPref[nCells] = M; if (part == 0) lvlCandCnt[f * nlevels + l] = M; }
-    __syncthreads();
-    if (M == 0) {
-        if (part != 0) { helper_leaves(); return; }
-        if (tid == 0) *lvlCnt = 0;
-        for (int i = tid; i < g.kpCap; i += kBlock) procRec[(long long) f * kpStride + g.kpBase + i] = make_uint2(0u, kNoKeypoint);
-        return;
-    }
-    OSTAMP(1);
-    // ---- 2. path keys: one thread per candidate (its cell by binary search in the prefix table) ----
-    const bool inLds = M <= ldsCand;
-    if (inLds) {
-        key0 = S.cand; val0 = S.cand + ldsCand;
-        if (candB) { key1 = candB; val1 = candB + ldsCand; }
-        else { key1 = S.cand + 2 * ldsCand; val1 = S.cand + 3 * ldsCand; }
-    }
-    // A workgroup has ONE CU: 2800 candidates x ~300 instructions of cell decode (a division), root (a float division) and ten
-    // subdivision steps were 7 us of a 752x480 level 0.  x and y subdivide independently, so the key is the OR of a per-column word
-    // (root, x bits spread to the even positions) and a per-row word (y bits on the odd positions): both tables and the cells' origins
-    // are built once per workgroup in the node arrays (idle until the tree passes) when they fit there.
-    const int lenX = max(g.regW, g.nCols * g.wCell) + 9, lenY = max(g.regH, g.nRows * g.hCell) + 9;
-    const bool useTab = (kHist ? lenX + lenY + nCells <= regionInts - (nCells + 1) : lenX + lenY + nCells <= 19 * cap) && g.depth <= 15;
-    unsigned *xTab = (unsigned *) (kHist ? dyn + nCells + 1 : S.nlo[0]), *yTab = xTab + lenX, *orgTab = yTab + lenY;
+}
 
-    if (useTab) {
-        auto spread = [](unsigned v) {
-            v = (v | (v << 8)) & 0x00FF00FFu;
-            v = (v | (v << 4)) & 0x0F0F0F0Fu;
-            v = (v | (v << 2)) & 0x33333333u;
-            return (v | (v << 1)) & 0x55555555u;
-        };
-        for (int t = tid; t < lenX + lenY + nCells; t += kBlock) {
-            if (t < lenX) {
-                const int x = t;
-                int root = (int) ((float) x / g.hX);
-                root = min(root, g.nIni - 1);
-                int xl = (int) (g.hX * (float) root), xr = (int) (g.hX * (float) (root + 1));
-                unsigned kx = 0;
-                for (int d = 0; d < g.depth; d++) {
-                    const int mx = xl + ((xr - xl + 1) >> 1);
-                    const unsigned bx = x >= mx;
-                    if (bx) xl = mx; else xr = mx;
-                    kx = (kx << 1) | bx;
-                }
-                xTab[t] = ((unsigned) root << (2 * g.depth)) | spread(kx);
-            } else if (t < lenX + lenY) {
-                const int y = t - lenX;
-                int yl = 0, yr = g.regH;
-                unsigned ky = 0;
-                for (int d = 0; d < g.depth; d++) {
-                    const int my = yl + ((yr - yl + 1) >> 1);
-                    const unsigned by = y >= my;
-                    if (by) yl = my; else yr = my;
-                    ky = (ky << 1) | by;
-                }
-                yTab[y] = spread(ky) << 1;
+// ---- 2b. path keys: one thread per candidate (its cell by binary search in the prefix table); histogram plan: the bin counts into PS ----
+// four candidates per thread at a time: their binary searches advance together (the LDS reads of a step travel together) and their
+// slot reads are all in flight before the first key is assembled.  This workgroup takes share `part` of `shares`.
+template <int kBlock> __device__ __forceinline__ void oct_path_keys(const OctLevel &w, bool useTab, int lenX, int lenY, int shares) {
+    const LevelGeom &g = w.g; const OctShared &S = w.S;
+    const int tid = w.tid, M = w.M, nCells = w.nCells;
+    const unsigned *xTab = w.xTab, *yTab = xTab + lenX, *orgTab = yTab + lenY;
+    int steps = 0;
+    while ((1 << steps) < nCells) steps++;
+    constexpr int kKU = 4;
+    for (int i0 = tid + w.part * kKU * kBlock; i0 < M; i0 += shares * kKU * kBlock) {
+        int ia[kKU], a[kKU], b[kKU];
+#pragma unroll
+        for (int u = 0; u < kKU; u++) { ia[u] = min(i0 + u * kBlock, M - 1); a[u] = 0; b[u] = nCells; }
+        for (int st = 0; st < steps; st++) {             // a[u] = last cell c with cellPref[c] <= ia[u]
+#pragma unroll
+            for (int u = 0; u < kKU; u++) {
+                const int m = (a[u] + b[u]) >> 1;
+                const bool go = b[u] - a[u] > 1, le = S.cellPref[m] <= ia[u];
+                a[u] = go && le ? m : a[u];
+                b[u] = go && !le ? m : b[u];
+            }
+        }
+        unsigned e[kKU];
+        int ox[kKU], oy[kKU];
+#pragma unroll
+        for (int u = 0; u < kKU; u++) {
+            const int c = a[u], k = ia[u] - S.cellPref[c];
+            e[u] = w.sl[(long long) c * g.slotCap + k];
+            if (useTab) {
+                const unsigned o = orgTab[c];
+                ox[u] = (int) (o & 0xFFFFu); oy[u] = (int) (o >> 16);
             } else {
-                const int c = t - lenX - lenY;
                 const int ci = c / g.nCols, cj = c - ci * g.nCols;
-                orgTab[c] = (unsigned) (cj * g.wCell) | ((unsigned) (ci * g.hCell) << 16);
+                ox[u] = cj * g.wCell; oy[u] = ci * g.hCell;
             }
         }
-        __syncthreads();
-    }
-    if (kHist && useHist) {
-        for (int b = tid; b <= nBins; b += kBlock) PS[b] = 0;
-        __syncthreads();
-    }
-    {
-        // four candidates per thread at a time: their binary searches advance together (the LDS reads of a step travel together) and their
-        // slot reads are all in flight before the first key is assembled
-        int steps = 0;
-        while ((1 << steps) < nCells) steps++;
-        constexpr int kKU = 4;
-        const int shares = kHist && useHist && !alone ? parts : 1;   // (the sorting path after a restart, or no helpers in sight: workgroup 0 takes everything)
-        for (int i0 = tid + part * kKU * kBlock; i0 < M; i0 += shares * kKU * kBlock) {
-            int ia[kKU], a[kKU], b[kKU];
+        int binOf[kKU];
 #pragma unroll
-            for (int u = 0; u < kKU; u++) { ia[u] = min(i0 + u * kBlock, M - 1); a[u] = 0; b[u] = nCells; }
-            for (int st = 0; st < steps; st++) {             // a[u] = last cell c with cellPref[c] <= ia[u]
-#pragma unroll
-                for (int u = 0; u < kKU; u++) {
-                    const int m = (a[u] + b[u]) >> 1;
-                    const bool go = b[u] - a[u] > 1, le = S.cellPref[m] <= ia[u];
-                    a[u] = go && le ? m : a[u];
-                    b[u] = go && !le ? m : b[u];
-                }
-            }
-            unsigned e[kKU];
-            int ox[kKU], oy[kKU];
-#pragma unroll
-            for (int u = 0; u < kKU; u++) {
-                const int c = a[u], k = ia[u] - S.cellPref[c];
-                e[u] = sl[(long long) c * g.slotCap + k];
-                if (useTab) {
-                    const unsigned o = orgTab[c];
-                    ox[u] = (int) (o & 0xFFFFu);
-                    oy[u] = (int) (o >> 16);
+        for (int u = 0; u < kKU; u++) {
+            const int i = i0 + u * kBlock;
+            binOf[u] = -2 - (tid & 63);
+            if (i < M) {
+                const int x = (int) (e[u] & 255u) + ox[u], y = (int) ((e[u] >> 8) & 255u) + oy[u];
+                const unsigned key = useTab ? (xTab[x] | yTab[y]) : path_key(x, y, g);
+                if (w.hist) {
+                    const unsigned bin = key >> w.binShift;
+                    binOf[u] = (int) bin;
+                    w.key0[i] = bin | ((e[u] >> 16) << 16);      // bin < 65536; the score rides along for the selection pass
                 } else {
-                    const int ci = c / g.nCols, cj = c - ci * g.nCols;
-                    ox[u] = cj * g.wCell;
-                    oy[u] = ci * g.hCell;
+                    w.key0[i] = key;
+                    w.val0[i] = ((e[u] >> 16) << 24) | (0xFFFFFFu - (unsigned) i);  // max() picks best score, then smallest index
                 }
+                w.xy[i] = (unsigned) x | ((unsigned) y << 16);
             }
-            int binOf[kKU];
+        }
+        if (w.hist) {   // (uniform per workgroup; every lane of the wave takes part in the row operations)
 #pragma unroll
             for (int u = 0; u < kKU; u++) {
-                const int i = i0 + u * kBlock;
-                binOf[u] = -2 - (tid & 63);
-                if (i < M) {
-                    const int x = (int) (e[u] & 255u) + ox[u], y = (int) ((e[u] >> 8) & 255u) + oy[u];
-                    const unsigned key = useTab ? (xTab[x] | yTab[y]) : path_key(x, y, g);
-                    if (kHist && useHist) {
-                        const unsigned bin = key >> binShift;
-                        binOf[u] = (int) bin;
-                        key0[i] = bin | ((e[u] >> 16) << 16);      // bin < 65536; the score rides along for the selection pass
-                    } else {
-                        key0[i] = key;
-                        val0[i] = ((e[u] >> 16) << 24) | (0xFFFFFFu - (unsigned) i);  // max() picks best score, then smallest index
-                    }
-                    xy[i] = (unsigned) x | ((unsigned) y << 16);
-                }
-            }
-            if (kHist && useHist) {   // (uniform per workgroup; every lane of the wave takes part in the row operations)
-#pragma unroll
-                for (int u = 0; u < kKU; u++) {
-                    const int len = row_run_length(binOf[u], tid & 63);
-                    if (binOf[u] >= 0 && row_run_last(binOf[u])) atomicAdd(&PS[binOf[u]], len);
-                }
+                const int len = row_run_length(binOf[u], tid & 63);
+                if (binOf[u] >= 0 && row_run_last(binOf[u])) atomicAdd(&w.PS[binOf[u]], len);
             }
         }
     }
-    if (kHist && useHist && parts > 1 && !alone) {
-        // (counts in a slice of its own per helper, plain stores: 60 000 device-scope atomics on one histogram ran at 9 per nanosecond for the whole
-        // device -- every level of a 3840x2160 pair waited 95 us for them)
-        __syncthreads();
-        if (part != 0) {
-            int *mine = gh + (long long) (part - 1) * histBins;
-            for (int b = tid; b < nBins; b += kBlock) mine[b] = PS[b];
-        }
-        // Release / acquire by ONE thread per workgroup, the barriers carrying the other threads' accesses along: an agent-scope release is a write-back
-        // of the XCD's whole L2 -- executed by every wave of every workgroup (`__threadfence()` in all threads, the portable idiom) it made every level
-        // of a 3840x2160 pair wait 95 us for 6000 of them.
-        __syncthreads();                       // every store of this workgroup has reached the L2 (the barrier waits for vmcnt(0)) ...
-        if (part != 0) {
-            helper_leaves();                   // ... and leaves it with this release
-            return;
-        }
-        if (tid == 0) {
-            int spins = 0;
-            bool here;
-            while (!(here = __hip_atomic_load(gd, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= doneTarget) && spins < spinBudget) { __builtin_amdgcn_s_sleep(8); spins++; }
-            s_flagA = here ? 1 : 0;
-        }
-        __syncthreads();
-        if (!s_flagA) {                        // (uniform) nobody came: the whole level again, alone
-            alone = true;
-            if (dbg && tid == 0) {
-                atomicAdd((unsigned long long *) &dbg[kOctDbgAlone + l], 1ull);
-                if (f < 64) atomicOr((unsigned long long *) &dbg[kOctDbgAloneFrames], 1ull << f);
-            }
-            __syncthreads();
-            goto restart;
-        }
-        for (int b = tid; b < nBins; b += kBlock) {
-            int v = PS[b];
-            for (int q = 0; q < parts - 1; q++) v += gh[(long long) q * histBins + b];
-            PS[b] = v;
-        }
+}
+
+// ---- 2c. the helper hand-over (histogram plan, parts > 1): a helper stores its counts and leaves (kOctLeft); workgroup 0 waits for the helpers and adds
+//      their counts to its own (kOctDone), or stops waiting after the spin budget (kOctAgainAlone) ----
+template <int kBlock> __device__ __forceinline__ OctOutcome oct_hand_over(const OctArgs &a, const OctLevel &w) {
+    const int tid = w.tid, nBins = w.nBins;
+    // (counts in a slice of its own per helper, plain stores: 60 000 device-scope atomics on one histogram ran at 9 per nanosecond for the whole
+    // device -- every level of a 3840x2160 pair waited 95 us for them)
+    __syncthreads();
+    if (w.part != 0) {
+        int *mine = w.gh + (long long) (w.part - 1) * a.histBins;
+        for (int b = tid; b < nBins; b += kBlock) mine[b] = w.PS[b];
+    }
+    // Release / acquire by ONE thread per workgroup, the barriers carrying the other threads' accesses along: an agent-scope release is a write-back
+    // of the XCD's whole L2 -- executed by every wave of every workgroup (`__threadfence()` in all threads, the portable idiom) it made every level
+    // of a 3840x2160 pair wait 95 us for 6000 of them.
+    __syncthreads();                       // every store of this workgroup has reached the L2 (the barrier waits for vmcnt(0)) ...
+    if (w.part != 0) {
+        oct_helper_leaves(w);              // ... and leaves it with this release
+        return kOctLeft;
+    }
+    if (tid == 0) {
+        int spins = 0;
+        bool here;
+        while (!(here = __hip_atomic_load(w.gd, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= a.doneTarget) && spins < a.spinBudget) { __builtin_amdgcn_s_sleep(8); spins++; }
+        *w.flagA = here ? 1 : 0;
     }
     __syncthreads();
-    OSTAMP(2);
-    // ---- 3. sort by path key ----
-    unsigned *skeys = key0, *svals = val0;
-    if (kHist && useHist) {
-        block_scan_array(PS, nBins, s_tmp);        // exclusive: PS[b] = candidates in front of bin b in path-key order
-        if (tid == 0) PS[nBins] = M;
+    if (!*w.flagA) {                       // (uniform) nobody came: the whole level again, alone
+        if (a.dbg && tid == 0) {
+            atomicAdd((unsigned long long *) &a.dbg[kOctDbgAlone + w.l], 1ull);
+            if (w.f < 64) atomicOr((unsigned long long *) &a.dbg[kOctDbgAloneFrames], 1ull << w.f);
+        }
+        __syncthreads();
+        return kOctAgainAlone;
+    }
+    for (int b = tid; b < nBins; b += kBlock) {
+        int v = w.PS[b];
+        for (int q = 0; q < w.parts - 1; q++) v += w.gh[(long long) q * a.histBins + b];
+        w.PS[b] = v;
+    }
+    return kOctDone;
+}
+
+// ---- 3. order by path key: the prefix sum of the bin counts, or the sort ----
+template <int kBlock> __device__ __forceinline__ void oct_order(OctLevel &w) {
+    w.skeys = w.key0; w.svals = w.val0;
+    if (w.hist) {
+        block_scan_array(w.PS, w.nBins, w.tmp);        // exclusive: PS[b] = candidates in front of bin b in path-key order
+        if (w.tid == 0) w.PS[w.nBins] = w.M;
         __syncthreads();
     } else {
-        block_radix_sort<kBlock / 64>(key0, val0, key1, val1, M, g.keyBits, histT, s_tmp, &skeys, &svals);
-        if (inLds && candB && skeys == key1) {   // (uniform) an odd number of passes ended over the node arrays: back to the first buffer
-            for (int i = tid; i < M; i += kBlock) { key0[i] = key1[i]; val0[i] = val1[i]; }
+        unsigned *sk, *sv;
+        block_radix_sort<kBlock / 64>(w.key0, w.val0, w.key1, w.val1, w.M, w.g.keyBits, w.histT, w.tmp, &sk, &sv);
+        w.skeys = sk; w.svals = sv;
+        if (w.inLds && w.candB && w.skeys == w.key1) {   // (uniform) an odd number of passes ended over the node arrays: back to the first buffer
+            for (int i = w.tid; i < w.M; i += kBlock) { w.key0[i] = w.key1[i]; w.val0[i] = w.val1[i]; }
             __syncthreads();
-            skeys = key0;
-            svals = val0;
+            w.skeys = w.key0; w.svals = w.val0;
         }
     }
-    OSTAMP(3);
-    // child boundaries of the node (lo, cnt, dep): a_c = first position in [lo, lo + cnt] whose child digit is >= c
-    auto bounds = [&](int lo, int cnt, int dep, int *a1, int *a2, int *a3) {
-        if (kHist && useHist) {
-            if (dep + 1 > dm) {                    // finer than the histogram: start over on the sorting path (the dummy answer keeps every loop finite)
-                s_overflow = 1;
-                *a1 = *a2 = *a3 = lo + cnt;
-                return;
-            }
-            const int sh = 2 * (dm - dep);         // a node of depth dep spans 2^sh bins, aligned
-            int a = 0, b = nBins >> sh;            // its index among the nodes of its depth: the largest j with PS[j << sh] <= lo (the node is not empty)
-            while (b - a > 1) {
-                const int m = (a + b) >> 1;
-                if (PS[m << sh] <= lo) a = m; else b = m;
-            }
-            const int f0 = a << sh, s1 = 1 << (sh - 2);
-            *a1 = PS[f0 + s1]; *a2 = PS[f0 + 2 * s1]; *a3 = PS[f0 + 3 * s1];
-        } else
-            digit_bounds3(skeys, lo, cnt, 2 * (g.depth - (dep + 1)), a1, a2, a3);
-    };
-    // ---- 4. breadth-first subdivision on ranges ----
-    const int D = g.depth;
-    const int N = g.nFeat;
-    // children of node (lo, cnt, dep) with boundaries a1..a3 into list `nxt`; exK / exE / exS = the exclusive sums over the nodes before it
-    auto emit = [&](int nxt, int lo, int cnt, int dep, int a1, int a2, int a3, int exK, int exE, int exS, int sumK) {
-        if (cnt == 1) {
-            const int p = sumK + exS;
-            (nxt ? S.nlo[1] : S.nlo[0])[p] = lo; (nxt ? S.ncnt[1] : S.ncnt[0])[p] = 1; (nxt ? S.ndep[1] : S.ndep[0])[p] = dep;
-        } else {
-            const int bb[5] = {lo, a1, a2, a3, lo + cnt};
-            int k = 0;
-            for (int c = 0; c < 4; c++) k += (bb[c + 1] - bb[c]) > 0;
-            int p = sumK - (exK + k);  // children of later parents sit in front (push_front)
-            int epos[4];
-            for (int c = 3; c >= 0; c--) {   // list order n4,n3,n2,n1
-                const int cc2 = bb[c + 1] - bb[c];
-                epos[c] = p;
-                if (cc2 > 0) { (nxt ? S.nlo[1] : S.nlo[0])[p] = bb[c]; (nxt ? S.ncnt[1] : S.ncnt[0])[p] = cc2; (nxt ? S.ndep[1] : S.ndep[0])[p] = dep + 1; p++; }
-            }
-            int es = exE;
-            for (int c = 0; c < 4; c++) {    // creation order n1..n4
-                const int cc2 = bb[c + 1] - bb[c];
-                if (cc2 > 1) { S.Epos[es] = epos[c]; S.Ecnt[es] = cc2; es++; }
+}
+
+// first bin of the (non-empty) node that starts at candidate `lo` and spans 2^sh bins, aligned: its index among the nodes of its depth is the
+// largest j with PS[j << sh] <= lo
+__device__ __forceinline__ int oct_first_bin(const int *PS, int nBins, int sh, int lo) {
+    int a = 0, b = nBins >> sh;
+    while (b - a > 1) {
+        const int m = (a + b) >> 1;
+        if (PS[m << sh] <= lo) a = m; else b = m;
+    }
+    return a << sh;
+}
+// child boundaries of the node (lo, cnt, dep): a_c = first position in [lo, lo + cnt] whose child digit is >= c
+__device__ __forceinline__ void oct_bounds(const OctLevel &w, int lo, int cnt, int dep, int *a1, int *a2, int *a3) {
+    if (w.hist) {
+        if (dep + 1 > w.dm) {                  // finer than the histogram: start over on the sorting path (the dummy answer keeps every loop finite)
+            *w.overflow = 1;
+            *a1 = *a2 = *a3 = lo + cnt;
+            return;
+        }
+        const int sh = 2 * (w.dm - dep);       // a node of depth dep spans 2^sh bins, aligned
+        const int f0 = oct_first_bin(w.PS, w.nBins, sh, lo), s1 = 1 << (sh - 2);
+        *a1 = w.PS[f0 + s1]; *a2 = w.PS[f0 + 2 * s1]; *a3 = w.PS[f0 + 3 * s1];
+    } else
+        digit_bounds3(w.skeys, lo, cnt, 2 * (w.g.depth - (dep + 1)), a1, a2, a3);
+}
+// of the four children [lo, a1), [a1, a2), [a2, a3), [a3, hi): k = the non-empty ones, e = those with more than one point (expandable)
+__device__ __forceinline__ void oct_child_counts(int lo, int a1, int a2, int a3, int hi, int *k, int *e) {
+    const int c0 = a1 - lo, c1 = a2 - a1, c2 = a3 - a2, c3 = hi - a3;
+    *k = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
+    *e = (c0 > 1) + (c1 > 1) + (c2 > 1) + (c3 > 1);
+}
+// the non-empty children of node (lo, cnt, dep) into list `out` from position p on, and the expandable ones among them into (ePos, eCnt) from entry es on
+template <typename T> __device__ __forceinline__ void oct_place_children(const OctNodes &out, int lo, int cnt, int dep, int a1, int a2, int a3, int p, T *ePos, T *eCnt, int es) {
+    const int bb[5] = {lo, a1, a2, a3, lo + cnt};
+    int epos[4];
+    for (int c = 3; c >= 0; c--) {   // list order n4,n3,n2,n1
+        const int cc2 = bb[c + 1] - bb[c];
+        epos[c] = p;
+        if (cc2 > 0) { out.lo[p] = bb[c]; out.cnt[p] = cc2; out.dep[p] = dep + 1; p++; }
+    }
+    for (int c = 0; c < 4; c++) {    // creation order n1..n4
+        const int cc2 = bb[c + 1] - bb[c];
+        if (cc2 > 1) { ePos[es] = (T) epos[c]; eCnt[es] = (T) cc2; es++; }
+    }
+}
+// a full pass's output for node (lo, cnt, dep) with boundaries a1..a3 into list `out`; exK / exE / exS = the exclusive sums over the nodes before it
+__device__ __forceinline__ void oct_emit(const OctShared &S, const OctNodes &out, int lo, int cnt, int dep, int a1, int a2, int a3, int exK, int exE, int exS, int sumK) {
+    if (cnt == 1) {
+        const int p = sumK + exS;
+        out.lo[p] = lo; out.cnt[p] = 1; out.dep[p] = dep;
+    } else {
+        int k, e;
+        oct_child_counts(lo, a1, a2, a3, lo + cnt, &k, &e);
+        oct_place_children(out, lo, cnt, dep, a1, a2, a3, sumK - (exK + k), S.Epos, S.Ecnt, exE);   // children of later parents sit in front (push_front)
+    }
+}
+
+// ---- 4a. the head of the subdivision on ONE wave, the block waiting at one barrier: the roots (:566-575, a lane each) and every full pass
+//      (:588-640) while the list has at most 64 nodes (2, 8, 32 for a 752x480 level) -- bounds, the three prefix sums as one wave scan, the
+//      children, all on the wave's lanes, with nothing but the wave's own LDS order between the passes.  Leaves (n, cur, nE, state) in head[] ----
+__device__ __forceinline__ void oct_head(const OctLevel &w) {
+    const LevelGeom &g = w.g; const OctShared &S = w.S;
+    const int M = w.M, D = g.depth, N = g.nFeat, lane = lane_id();
+    int n = 0, cur = 0, nE = 0, state = 0;   // state: 0 = go on block-wide, 1 = finished, 2 = continue with the expand phase
+    if (g.nIni <= 64) {
+        int hi = M;                           // first index of a root > lane
+        if (lane < g.nIni) {
+            if (w.hist) hi = w.PS[(lane + 1) << (2 * w.dm)];
+            else {
+                int a = 0, b = M;
+                while (a < b) {
+                    const int m = (a + b) >> 1;
+                    if ((int) (w.skeys[m] >> (2 * D)) <= lane) a = m + 1; else b = m;
+                }
+                hi = a;
             }
         }
-    };
-    // -- the head of the subdivision on ONE wave, the block waiting at one barrier: the roots (:566-575, a lane each) and every full pass
-    //    (:588-640) while the list has at most 64 nodes (2, 8, 32 for a 752x480 level) -- bounds, the three prefix sums as one wave scan, the
-    //    children, all on the wave's lanes, with nothing but the wave's own LDS order between the passes
-    if (wave_id() == 0) {
-        const int lane = lane_id();
-        int n = 0, cur = 0, nE = 0, state = 0;   // state: 0 = go on block-wide, 1 = finished, 2 = continue with the expand phase
-        if (g.nIni <= 64) {
-            int hi = M;                           // first index of a root > lane
-            if (lane < g.nIni) {
-                if (kHist && useHist) hi = PS[(lane + 1) << (2 * dm)];
-                else {
-                    int a = 0, b = M;
-                    while (a < b) {
-                        const int m = (a + b) >> 1;
-                        if ((int) (skeys[m] >> (2 * D)) <= lane) a = m + 1; else b = m;
-                    }
-                    hi = a;
-                }
-            }
-            int lo = __shfl_up(hi, 1);
-            if (lane == 0) lo = 0;
-            const bool some = lane < g.nIni && hi > lo;   // empty roots are erased
-            const unsigned long long bal = __ballot(some);
-            if (some) {
-                const int p = __popcll(bal & ((1ull << lane) - 1ull));
-                S.nlo[0][p] = lo; S.ncnt[0][p] = hi - lo; S.ndep[0][p] = 0;
-            }
-            n = __popcll(bal);
-        } else {
-            if (lane == 0) {
-                int lo = 0;
-                for (int r = 0; r < g.nIni; r++) {
-                    int a = lo, b = M;
-                    if (kHist && useHist) a = b = PS[(r + 1) << (2 * dm)];
-                    while (a < b) {
-                        const int m = (a + b) >> 1;
-                        if ((int) (skeys[m] >> (2 * D)) <= r) a = m + 1; else b = m;
-                    }
-                    if (a > lo) { S.nlo[0][n] = lo; S.ncnt[0][n] = a - lo; S.ndep[0][n] = 0; n++; }
-                    lo = a;
-                }
-            }
-            n = __builtin_amdgcn_readfirstlane(n);
+        int lo = __shfl_up(hi, 1);
+        if (lane == 0) lo = 0;
+        const bool some = lane < g.nIni && hi > lo;   // empty roots are erased
+        const unsigned long long bal = __ballot(some);
+        if (some) {
+            const int p = __popcll(bal & ((1ull << lane) - 1ull));
+            S.nlo[0][p] = lo; S.ncnt[0][p] = hi - lo; S.ndep[0][p] = 0;
         }
+        n = __popcll(bal);
+    } else {
+        if (lane == 0) {
+            int lo = 0;
+            for (int r = 0; r < g.nIni; r++) {
+                int a = lo, b = M;
+                if (w.hist) a = b = w.PS[(r + 1) << (2 * w.dm)];
+                while (a < b) {
+                    const int m = (a + b) >> 1;
+                    if ((int) (w.skeys[m] >> (2 * D)) <= r) a = m + 1; else b = m;
+                }
+                if (a > lo) { S.nlo[0][n] = lo; S.ncnt[0][n] = a - lo; S.ndep[0][n] = 0; n++; }
+                lo = a;
+            }
+        }
+        n = __builtin_amdgcn_readfirstlane(n);
+    }
+    wave_lds_sync();
+    while (n <= 64) {
+        const int prevSize = n, nxt = cur ^ 1;
+        const OctNodes in = oct_nodes(S, cur);
+        const bool act = lane < n;
+        int lo = 0, cnt = 0, dep = 0, a1 = 0, a2 = 0, a3 = 0, k = 0, e = 0;
+        if (act) {
+            cnt = in.cnt[lane]; lo = in.lo[lane]; dep = in.dep[lane];
+            if (cnt > 1) {
+                oct_bounds(w, lo, cnt, dep, &a1, &a2, &a3);
+                oct_child_counts(lo, a1, a2, a3, lo + cnt, &k, &e);
+            }
+        }
+        const unsigned long long mine = (unsigned long long) (unsigned) k | ((unsigned long long) (unsigned) e << 21) |
+                                        ((unsigned long long) (act && cnt == 1 ? 1u : 0u) << 42);
+        const unsigned long long incl = wave_incl_scan_u64(mine), ex = incl - mine;
+        const unsigned long long tot = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane((int) (incl >> 32), 63) << 32) |
+                                       (unsigned) __builtin_amdgcn_readlane((int) incl, 63);
+        const int sumK = (int) (tot & 0x1FFFFFu);
+        if (act) oct_emit(S, oct_nodes(S, nxt), lo, cnt, dep, a1, a2, a3, (int) (ex & 0x1FFFFFu), (int) ((ex >> 21) & 0x1FFFFFu), (int) (ex >> 42), sumK);
         wave_lds_sync();
-        while (n <= 64) {
-            const int prevSize = n, nxt = cur ^ 1;
-            const bool act = lane < n;
-            int lo = 0, cnt = 0, dep = 0, a1 = 0, a2 = 0, a3 = 0, k = 0, e = 0;
-            if (act) {
-                cnt = (cur ? S.ncnt[1] : S.ncnt[0])[lane];
-                lo = (cur ? S.nlo[1] : S.nlo[0])[lane];
-                dep = (cur ? S.ndep[1] : S.ndep[0])[lane];
-                if (cnt > 1) {
-                    bounds(lo, cnt, dep, &a1, &a2, &a3);
-                    const int c0 = a1 - lo, c1 = a2 - a1, c2 = a3 - a2, c3 = lo + cnt - a3;
-                    k = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
-                    e = (c0 > 1) + (c1 > 1) + (c2 > 1) + (c3 > 1);
-                }
-            }
-            const unsigned long long mine = (unsigned long long) (unsigned) k | ((unsigned long long) (unsigned) e << 21) |
-                                            ((unsigned long long) (act && cnt == 1 ? 1u : 0u) << 42);
-            const unsigned long long incl = wave_incl_scan_u64(mine), ex = incl - mine;
-            const unsigned long long tot = ((unsigned long long) (unsigned) __builtin_amdgcn_readlane((int) (incl >> 32), 63) << 32) |
-                                           (unsigned) __builtin_amdgcn_readlane((int) incl, 63);
-            const int sumK = (int) (tot & 0x1FFFFFu);
-            if (act) emit(nxt, lo, cnt, dep, a1, a2, a3, (int) (ex & 0x1FFFFFu), (int) ((ex >> 21) & 0x1FFFFFu), (int) (ex >> 42), sumK);
-            wave_lds_sync();
-            cur = nxt;
-            n = sumK + (int) (tot >> 42);
-            nE = (int) ((tot >> 21) & 0x1FFFFFu);
-            if (n >= N || n == prevSize) { state = 1; break; }
-            if (n + 3 * nE > N) { state = 2; break; }
+        cur = nxt;
+        n = sumK + (int) (tot >> 42);
+        nE = (int) ((tot >> 21) & 0x1FFFFFu);
+        if (n >= N || n == prevSize) { state = 1; break; }
+        if (n + 3 * nE > N) { state = 2; break; }
+    }
+    if (lane == 0) { w.head[0] = n; w.head[1] = cur; w.head[2] = nE; w.head[3] = state; }
+}
+
+// ---- 4b. a full pass (:588-640): every node with more than one point is divided ----
+template <int kBlock> __device__ __forceinline__ void oct_full_pass(OctLevel &w) {
+    const OctShared &S = w.S;
+    const int tid = w.tid, n = w.n, nxt = w.cur ^ 1;
+    const OctNodes in = oct_nodes(S, w.cur), out = oct_nodes(S, nxt);
+    int totK, totE, totS;
+    for (int i = tid; i < n; i += kBlock) {
+        const int cnt = in.cnt[i];
+        int k = 0, e = 0;
+        if (cnt > 1) {
+            const int lo = in.lo[i];
+            int a1, a2, a3;
+            oct_bounds(w, lo, cnt, in.dep[i], &a1, &a2, &a3);
+            S.b1[i] = a1; S.b2[i] = a2; S.b3[i] = a3;
+            oct_child_counts(lo, a1, a2, a3, lo + cnt, &k, &e);
         }
-        if (lane == 0) { s_head[0] = n; s_head[1] = cur; s_head[2] = nE; s_head[3] = state; }
+        S.kArr[i] = k; S.eArr[i] = e; S.sArr[i] = (cnt == 1);
     }
     __syncthreads();
-    int n = s_head[0], cur = s_head[1];
-    int nE = s_head[2];
-    OBFS(n);
-    bool finish = s_head[3] == 1, toExpand = s_head[3] == 2;
+    block_scan_array3(S.kArr, S.eArr, S.sArr, n, w.tmp64, &totK, &totE, &totS);
+    for (int i = tid; i < n; i += kBlock) {
+        const int cnt = in.cnt[i], lo = in.lo[i], dep = in.dep[i];
+        oct_emit(S, out, lo, cnt, dep, cnt > 1 ? S.b1[i] : 0, cnt > 1 ? S.b2[i] : 0, cnt > 1 ? S.b3[i] : 0, S.kArr[i], S.eArr[i], S.sArr[i], totK);
+    }
+    __syncthreads();
+    w.cur = nxt; w.n = totK + totS; w.nE = totE;
+}
+
+// The expandable nodes' keys sk[0][0 .. nE) (size << seqBits | creation sequence, all distinct) in ascending order into sk[1] / sv[1], nE <= kBlock.
+// A few hundred distinct keys: the position of a key is the number of smaller keys -- counted off
+// LDS reads, no histogram, no scan, ONE barrier (the radix sort: three passes of four).  T = 1 .. 16 adjacent lanes share a key, each
+// counting a quarter-aligned slice of the list with 16-byte reads: one thread per key reading word by word made a round of 512
+// expandable nodes 8192 wave-wide LDS reads -- 14 of the 22 us of a 1920x1080 level's only expand round.
+// (launches of many frames have other workgroups to fill the wait: there one thread per key issues the fewest instructions)
+template <int kBlock> __device__ __forceinline__ void oct_rank_sort(const OctLevel &w, int nE) {
+    const OctShared &S = w.S;
+    int tl = 0;
+    while (gridDim.y <= 16 && tl < 4 && (nE << (tl + 1)) <= kBlock) tl++;
+    const int T = 1 << tl, j = w.tid >> tl, sub = w.tid & (T - 1);
+    const bool vec = (((unsigned) (uintptr_t) S.sk[0]) & 15u) == 0;   // (LDS offset; the host rounds the list capacity to a multiple of 4)
+    unsigned key = 0;
+    int rank = 0;
+    if (j < nE) {
+        key = S.sk[0][j];
+        const int per = (((nE + T - 1) >> tl) + 3) & ~3;
+        int q = sub * per;
+        const int q1 = min(nE, q + per);
+        // rank += (k < key) as compare + add-with-carry: two instructions per key (the compiler's select-and-add form is three)
+        auto count = [&](unsigned k) { asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc" : "+v"(rank) : "v"(k), "v"(key) : "vcc"); };
+        if (vec)
+            for (; q + 4 <= q1; q += 4) {
+                const uint4 k4 = *(const uint4 *) &S.sk[0][q];
+                count(k4.x); count(k4.y); count(k4.z); count(k4.w);
+            }
+        for (; q < q1; q++) count(S.sk[0][q]);
+    }
+    for (int d = 1; d < T; d <<= 1) rank += __shfl_xor(rank, d);
+    if (j < nE && sub == 0) { S.sk[1][rank] = key; S.sv[1][rank] = S.sv[0][j]; }
+    __syncthreads();
+}
+
+// ---- 4c. a round of the "expand the biggest first" phase (:647-700), nE > 0 ----
+template <int kBlock> __device__ __forceinline__ void oct_expand_round(OctLevel &w) {
+    const OctShared &S = w.S; const OctNodes in = oct_nodes(S, w.cur);
+    const int tid = w.tid, n = w.n, nE = w.nE, N = w.g.nFeat;
+    int seqBits = 1, cntBits = 1;
+    while ((1 << seqBits) < max(nE, 2)) seqBits++;
+    while ((1 << cntBits) <= w.M) cntBits++;
+    for (int j = tid; j < nE; j += kBlock) { S.sk[0][j] = ((unsigned) S.Ecnt[j] << seqBits) | (unsigned) j; S.sv[0][j] = (unsigned) j; }
+    for (int j = tid; j < n; j += kBlock) S.flag[j] = 0;
+    if (tid == 0) *w.cut = nE - 1;
+    __syncthreads();
+    unsigned *ek, *ev;
+    if (nE <= kBlock) { oct_rank_sort<kBlock>(w, nE); ek = S.sk[1]; ev = S.sv[1]; }
+    else
+        block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], nE, seqBits + cntBits, w.histT, w.tmp, &ek, &ev);
+    // processing order j: descending (size, creation seq)
+    for (int j = tid; j < nE; j += kBlock) {
+        const int pos = S.Epos[(int) ev[nE - 1 - j]];
+        const int cnt = in.cnt[pos], lo = in.lo[pos];
+        int a1, a2, a3, k, e;
+        oct_bounds(w, lo, cnt, in.dep[pos], &a1, &a2, &a3);
+        S.b1[j] = a1; S.b2[j] = a2; S.b3[j] = a3;
+        oct_child_counts(lo, a1, a2, a3, lo + cnt, &k, &e);
+        S.kArr[j] = k - 1; S.eArr[j] = e;   // (k - 1: growth of the list)
+    }
+    __syncthreads();
+    block_scan_array(S.kArr, nE, w.tmp);  // exclusive growth before j
+    // children of the j-th processed node (k) and, in kArr[j], the growth of the list before it
+    auto children = [&](int j) {
+        const int pos = S.Epos[(int) ev[nE - 1 - j]];
+        const int cnt = in.cnt[pos], lo = in.lo[pos];
+        int k, e;
+        oct_child_counts(lo, S.b1[j], S.b2[j], S.b3[j], lo + cnt, &k, &e);
+        return k;
+    };
+    for (int j = tid; j < nE; j += kBlock) {
+        const int excl = S.kArr[j], incl = excl + children(j) - 1;
+        if (n + incl >= N && n + excl < N) *w.cut = j;  // first expansion that reaches N nodes: break
+    }
+    __syncthreads();
+    const int nProc = *w.cut + 1;
+    // nodes j >= nProc are not expanded: no children, no new expandable entries
+    for (int j = tid; j < nE; j += kBlock) {
+        if (j >= nProc) S.eArr[j] = 0;
+        else S.flag[S.Epos[(int) ev[nE - 1 - j]]] = 1;
+    }
+    __syncthreads();
+    const int totE2 = block_scan_array(S.eArr, nE, w.tmp);
+    // children of the processed nodes: total = growth + nProc (growth before nProc-1 plus its own)
+    const int totC = S.kArr[nProc - 1] + (nProc - 1) + children(nProc - 1);
+    // unprocessed old nodes keep their order behind the new children
+    for (int i = tid; i < n; i += kBlock) S.sArr[i] = 1 - S.flag[i];
+    __syncthreads();
+    block_scan_array(S.sArr, n, w.tmp);
+    const int nxt = w.cur ^ 1;
+    const OctNodes out = oct_nodes(S, nxt);
+    for (int i = tid; i < n; i += kBlock) {
+        if (!S.flag[i]) {
+            const int p = totC + S.sArr[i];
+            out.lo[p] = in.lo[i]; out.cnt[p] = in.cnt[i]; out.dep[p] = in.dep[i];
+        }
+    }
+    // new expandable list goes to the sort buffers first (Epos/Ecnt are still being read)
+    unsigned *nEpos = (ek == S.sk[0]) ? S.sk[1] : S.sk[0];
+    unsigned *nEcnt = (ev == S.sv[0]) ? S.sv[1] : S.sv[0];
+    for (int j = tid; j < nProc; j += kBlock) {
+        const int pos = S.Epos[(int) ev[nE - 1 - j]];
+        const int cnt = in.cnt[pos], lo = in.lo[pos], dep = in.dep[pos];
+        const int before = S.kArr[j] + j;     // children created by earlier-processed nodes
+        oct_place_children(out, lo, cnt, dep, S.b1[j], S.b2[j], S.b3[j], totC - (before + children(j)), nEpos, nEcnt, S.eArr[j]);
+    }
+    __syncthreads();
+    for (int j = tid; j < totE2; j += kBlock) { S.Epos[j] = (int) nEpos[j]; S.Ecnt[j] = (int) nEcnt[j]; }
+    __syncthreads();
+    w.cur = nxt; w.n = totC + (n - nProc); w.nE = totE2;
+}
+
+// ---- 4. breadth-first subdivision on ranges: the head, full passes while every node may divide, then expand rounds until the list holds N nodes or stops growing ----
+template <int kBlock> __device__ __forceinline__ void oct_subdivide(OctLevel &w, long long *dbg) {
+    const int N = w.g.nFeat;
+    if (wave_id() == 0) oct_head(w);
+    __syncthreads();
+    w.n = w.head[0]; w.cur = w.head[1]; w.nE = w.head[2];
+    oct_pass_stamp(w, dbg, w.n);
+    bool finish = w.head[3] == 1, toExpand = w.head[3] == 2;
+    while (!finish && !toExpand) {
+        const int prevSize = w.n;
+        oct_full_pass<kBlock>(w);
+        oct_pass_stamp(w, dbg, w.n);
+        if (w.n >= N || w.n == prevSize) finish = true;
+        else if (w.n + 3 * w.nE > N) toExpand = true;
+    }
     while (!finish) {
-        if (!toExpand) {
-            const int prevSize = n;
-            // -- full pass (:588-640): every node with more than one point is divided
-            int totK, totE, totS;
-            const int nxt = cur ^ 1;
-            for (int i = tid; i < n; i += kBlock) {
-                const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[i];
-                int k = 0, e = 0;
-                if (cnt > 1) {
-                    const int lo = (cur ? S.nlo[1] : S.nlo[0])[i];
-                    int a1, a2, a3;
-                    bounds(lo, cnt, (cur ? S.ndep[1] : S.ndep[0])[i], &a1, &a2, &a3);
-                    S.b1[i] = a1; S.b2[i] = a2; S.b3[i] = a3;
-                    const int c0 = a1 - lo, c1 = a2 - a1, c2 = a3 - a2, c3 = lo + cnt - a3;
-                    k = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0);
-                    e = (c0 > 1) + (c1 > 1) + (c2 > 1) + (c3 > 1);
-                }
-                S.kArr[i] = k; S.eArr[i] = e; S.sArr[i] = (cnt == 1);
-            }
-            __syncthreads();
-            block_scan_array3(S.kArr, S.eArr, S.sArr, n, s_tmp64, &totK, &totE, &totS);
-            for (int i = tid; i < n; i += kBlock) {
-                const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[i], lo = (cur ? S.nlo[1] : S.nlo[0])[i], dep = (cur ? S.ndep[1] : S.ndep[0])[i];
-                emit(nxt, lo, cnt, dep, cnt > 1 ? S.b1[i] : 0, cnt > 1 ? S.b2[i] : 0, cnt > 1 ? S.b3[i] : 0, S.kArr[i], S.eArr[i], S.sArr[i], totK);
-            }
-            __syncthreads();
-            cur = nxt;
-            n = totK + totS;
-            nE = totE;
-            OBFS(n);
-            if (n >= N || n == prevSize) { finish = true; break; }
-            if (n + 3 * nE <= N) continue;
-        }
-        toExpand = false;
-        {
-            // -- "expand the biggest first" phase (:647-700)
-            while (!finish) {
-                const int prev2 = n;
-                if (nE == 0) { finish = true; break; }  // nothing left to expand: list size cannot change (:696)
-                int seqBits = 1;
-                while ((1 << seqBits) < max(nE, 2)) seqBits++;
-                int cntBits = 1;
-                while ((1 << cntBits) <= M) cntBits++;
-                for (int j = tid; j < nE; j += kBlock) {
-                    S.sk[0][j] = ((unsigned) S.Ecnt[j] << seqBits) | (unsigned) j;
-                    S.sv[0][j] = (unsigned) j;
-                }
-                for (int j = tid; j < n; j += kBlock) S.flag[j] = 0;
-                if (tid == 0) s_cut = nE - 1;
-                __syncthreads();
-                unsigned *ek, *ev;
-                if (nE <= kBlock) {
-                    // a few hundred distinct keys (they carry the creation sequence): the position of a key is the number of smaller keys -- counted off
-                    // LDS reads, no histogram, no scan, ONE barrier (the radix sort: three passes of four).  T = 1 .. 16 adjacent lanes share a key, each
-                    // counting a quarter-aligned slice of the list with 16-byte reads: one thread per key reading word by word made a round of 512
-                    // expandable nodes 8192 wave-wide LDS reads -- 14 of the 22 us of a 1920x1080 level's only expand round.
-                    // (launches of many frames have other workgroups to fill the wait: there one thread per key issues the fewest instructions)
-                    int tl = 0;
-                    while (gridDim.y <= 16 && tl < 4 && (nE << (tl + 1)) <= kBlock) tl++;
-                    const int T = 1 << tl, j = tid >> tl, sub = tid & (T - 1);
-                    const bool vec = (((unsigned) (uintptr_t) S.sk[0]) & 15u) == 0;   // (LDS offset; the host rounds the list capacity to a multiple of 4)
-                    unsigned key = 0;
-                    int rank = 0;
-                    if (j < nE) {
-                        key = S.sk[0][j];
-                        const int per = (((nE + T - 1) >> tl) + 3) & ~3;
-                        int q = sub * per;
-                        const int q1 = min(nE, q + per);
-                        // rank += (k < key) as compare + add-with-carry: two instructions per key (the compiler's select-and-add form is three)
-                        auto count = [&](unsigned k) { asm("v_cmp_lt_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, 0, %0, vcc" : "+v"(rank) : "v"(k), "v"(key) : "vcc"); };
-                        if (vec)
-                            for (; q + 4 <= q1; q += 4) {
-                                const uint4 k4 = *(const uint4 *) &S.sk[0][q];
-                                count(k4.x); count(k4.y); count(k4.z); count(k4.w);
-                            }
-                        for (; q < q1; q++) count(S.sk[0][q]);
-                    }
-                    for (int d = 1; d < T; d <<= 1) rank += __shfl_xor(rank, d);
-                    if (j < nE && sub == 0) {
-                        S.sk[1][rank] = key;
-                        S.sv[1][rank] = S.sv[0][j];
-                    }
-                    __syncthreads();
-                    ek = S.sk[1];
-                    ev = S.sv[1];
-                } else
-                    block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], nE, seqBits + cntBits, histT, s_tmp, &ek, &ev);
-                // processing order j: descending (size, creation seq)
-                for (int j = tid; j < nE; j += kBlock) {
-                    const int e = (int) ev[nE - 1 - j];
-                    const int pos = S.Epos[e];
-                    const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[pos], lo = (cur ? S.nlo[1] : S.nlo[0])[pos];
-                    int a1, a2, a3;
-                    bounds(lo, cnt, (cur ? S.ndep[1] : S.ndep[0])[pos], &a1, &a2, &a3);
-                    S.b1[j] = a1; S.b2[j] = a2; S.b3[j] = a3;
-                    const int c0 = a1 - lo, c1 = a2 - a1, c2 = a3 - a2, c3 = lo + cnt - a3;
-                    S.kArr[j] = (c0 > 0) + (c1 > 0) + (c2 > 0) + (c3 > 0) - 1;  // growth of the list
-                    S.eArr[j] = (c0 > 1) + (c1 > 1) + (c2 > 1) + (c3 > 1);
-                }
-                __syncthreads();
-                block_scan_array(S.kArr, nE, s_tmp);  // exclusive growth before j
-                for (int j = tid; j < nE; j += kBlock) {
-                    const int e = (int) ev[nE - 1 - j];
-                    const int pos = S.Epos[e];
-                    const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[pos], lo = (cur ? S.nlo[1] : S.nlo[0])[pos];
-                    const int bb[5] = {lo, S.b1[j], S.b2[j], S.b3[j], lo + cnt};
-                    int k = 0;
-                    for (int c = 0; c < 4; c++) k += (bb[c + 1] - bb[c]) > 0;
-                    const int excl = S.kArr[j], incl = excl + k - 1;
-                    if (n + incl >= N && n + excl < N) s_cut = j;  // first expansion that reaches N nodes: break
-                }
-                __syncthreads();
-                const int nProc = s_cut + 1;
-                // nodes j >= nProc are not expanded: no children, no new expandable entries
-                for (int j = tid; j < nE; j += kBlock) {
-                    if (j >= nProc) S.eArr[j] = 0;
-                    else S.flag[S.Epos[(int) ev[nE - 1 - j]]] = 1;
-                }
-                __syncthreads();
-                const int totE2 = block_scan_array(S.eArr, nE, s_tmp);
-                // children of the processed nodes: total = growth + nProc
-                int totC;
-                {
-                    // growth before nProc-1 plus its own
-                    const int jl = nProc - 1;
-                    const int e = (int) ev[nE - 1 - jl];
-                    const int pos = S.Epos[e];
-                    const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[pos], lo = (cur ? S.nlo[1] : S.nlo[0])[pos];
-                    const int bb[5] = {lo, S.b1[jl], S.b2[jl], S.b3[jl], lo + cnt};
-                    int k = 0;
-                    for (int c = 0; c < 4; c++) k += (bb[c + 1] - bb[c]) > 0;
-                    totC = S.kArr[jl] + jl + k;
-                }
-                // unprocessed old nodes keep their order behind the new children
-                for (int i = tid; i < n; i += kBlock) S.sArr[i] = 1 - S.flag[i];
-                __syncthreads();
-                block_scan_array(S.sArr, n, s_tmp);
-                const int nxt2 = cur ^ 1;
-                for (int i = tid; i < n; i += kBlock) {
-                    if (!S.flag[i]) {
-                        const int p = totC + S.sArr[i];
-                        (nxt2 ? S.nlo[1] : S.nlo[0])[p] = (cur ? S.nlo[1] : S.nlo[0])[i]; (nxt2 ? S.ncnt[1] : S.ncnt[0])[p] = (cur ? S.ncnt[1] : S.ncnt[0])[i]; (nxt2 ? S.ndep[1] : S.ndep[0])[p] = (cur ? S.ndep[1] : S.ndep[0])[i];
-                    }
-                }
-                // new expandable list goes to the sort buffers first (Epos/Ecnt are still being read)
-                unsigned *nEpos = (ek == S.sk[0]) ? S.sk[1] : S.sk[0];
-                unsigned *nEcnt = (ev == S.sv[0]) ? S.sv[1] : S.sv[0];
-                for (int j = tid; j < nProc; j += kBlock) {
-                    const int e = (int) ev[nE - 1 - j];
-                    const int pos = S.Epos[e];
-                    const int cnt = (cur ? S.ncnt[1] : S.ncnt[0])[pos], lo = (cur ? S.nlo[1] : S.nlo[0])[pos], dep = (cur ? S.ndep[1] : S.ndep[0])[pos];
-                    const int bb[5] = {lo, S.b1[j], S.b2[j], S.b3[j], lo + cnt};
-                    int k = 0;
-                    for (int c = 0; c < 4; c++) k += (bb[c + 1] - bb[c]) > 0;
-                    const int before = S.kArr[j] + j;     // children created by earlier-processed nodes
-                    int p = totC - (before + k);
-                    int epos[4];
-                    for (int c = 3; c >= 0; c--) {
-                        const int cc2 = bb[c + 1] - bb[c];
-                        epos[c] = p;
-                        if (cc2 > 0) { (nxt2 ? S.nlo[1] : S.nlo[0])[p] = bb[c]; (nxt2 ? S.ncnt[1] : S.ncnt[0])[p] = cc2; (nxt2 ? S.ndep[1] : S.ndep[0])[p] = dep + 1; p++; }
-                    }
-                    int es = S.eArr[j];
-                    for (int c = 0; c < 4; c++) {
-                        const int cc2 = bb[c + 1] - bb[c];
-                        if (cc2 > 1) { nEpos[es] = (unsigned) epos[c]; nEcnt[es] = (unsigned) cc2; es++; }
-                    }
-                }
-                __syncthreads();
-                for (int j = tid; j < totE2; j += kBlock) { S.Epos[j] = (int) nEpos[j]; S.Ecnt[j] = (int) nEcnt[j]; }
-                __syncthreads();
-                cur = nxt2;
-                n = totC + (n - nProc);
-                nE = totE2;
-                OBFS(-n);
-                if (n >= N || n == prev2) finish = true;
-            }
+        const int prevSize = w.n;
+        if (w.nE == 0) break;  // nothing left to expand: list size cannot change (:696)
+        oct_expand_round<kBlock>(w);
+        oct_pass_stamp(w, dbg, -w.n);
+        if (w.n >= N || w.n == prevSize) finish = true;
+    }
+}
+
+// One attempt at the level, steps 1 - 4: from the cell counts to the final node list (w.n nodes in list w.cur).
+//   useHist   histogram plan (kHist only); an attempt that had to split a node below depth dm asks for another one on the sorting path
+//   alone     workgroup 0 takes every candidate itself; an attempt whose helpers did not arrive within the spin budget asks for another one alone
+template <bool kHist, int kBlock> __device__ __forceinline__ OctOutcome oct_attempt(const OctArgs &a, OctLevel &w, bool useHist, bool alone) {
+    const LevelGeom &g = w.g; const int tid = w.tid;
+    w.hist = kHist && useHist;
+    if (kHist && tid == 0) *w.overflow = 0;
+    w.M = oct_cell_prefix<kBlock>(a, w);
+    if (w.M == 0) { oct_empty_level<kBlock>(a, w); return kOctLeft; }
+    oct_stamp(w, a.dbg, 1);
+    w.inLds = w.M <= a.ldsCand;
+    if (w.inLds) {
+        w.key0 = w.S.cand; w.val0 = w.S.cand + a.ldsCand;
+        if (w.candB) { w.key1 = w.candB; w.val1 = w.candB + a.ldsCand; }
+        else { w.key1 = w.S.cand + 2 * a.ldsCand; w.val1 = w.S.cand + 3 * a.ldsCand; }
+    }
+    const int lenX = max(g.regW, g.nCols * g.wCell) + 9, lenY = max(g.regH, g.nRows * g.hCell) + 9;
+    const bool useTab = (kHist ? lenX + lenY + w.nCells <= a.regionInts - (w.nCells + 1) : lenX + lenY + w.nCells <= 19 * a.cap) && g.depth <= 15;
+    if (useTab) oct_key_tables<kBlock>(w, lenX, lenY);
+    if (w.hist) {
+        for (int b = tid; b <= w.nBins; b += kBlock) w.PS[b] = 0;
+        __syncthreads();
+    }
+    const bool shared = w.hist && w.parts > 1 && !alone;   // (the sorting path after a restart, or no helpers in sight: workgroup 0 takes everything)
+    oct_path_keys<kBlock>(w, useTab, lenX, lenY, shared ? w.parts : 1);
+    if (shared) {
+        const OctOutcome o = oct_hand_over<kBlock>(a, w);
+        if (o != kOctDone) return o;
+    }
+    __syncthreads();
+    oct_stamp(w, a.dbg, 2);
+    oct_order<kBlock>(w);
+    oct_stamp(w, a.dbg, 3);
+    oct_subdivide<kBlock>(w, a.dbg);
+    if (w.hist && *w.overflow) {   // (uniform: every write of the flag lies before the barrier that ended the tree passes)
+        __syncthreads();
+        if (a.dbg && tid == 0) atomicAdd((unsigned long long *) &a.dbg[16 * 8 + w.l], 1ull);   // restarts of this level over the launch's frames
+        return kOctAgainSorted;
+    }
+    return kOctDone;
+}
+
+// ---- 5a. best response per node (:702-720), histogram plan: into kArr[node] ----
+template <int kBlock> __device__ __forceinline__ void oct_best_hist(const OctLevel &w) {
+    const OctShared &S = w.S; const OctNodes in = oct_nodes(S, w.cur);
+    const int tid = w.tid, n = w.n, M = w.M, lane = lane_id(), wave = wave_id();
+    int *PS = w.PS;
+    // first bin and log2 of the bin count of every final node (PS is still the prefix table)
+    for (int i = tid; i < n; i += kBlock) {
+        const int sh = 2 * (w.dm - in.dep[i]);
+        S.b1[i] = oct_first_bin(PS, w.nBins, sh, in.lo[i]);
+        S.b2[i] = sh;
+        S.kArr[i] = 0;
+    }
+    __syncthreads();
+    // bin -> final node, written over the prefix table (sixteen lanes per node; bins outside every node hold no candidate)
+    for (int i0 = wave * 4; i0 < n; i0 += (kBlock / 64) * 4) {
+        const int i = i0 + (lane >> 4), sl16 = lane & 15;
+        if (i < n) {
+            const int f0 = S.b1[i], len = 1 << S.b2[i];
+            for (int k = sl16; k < len; k += 16) PS[f0 + k] = i;
         }
     }
-    if (kHist && useHist) {
-        if (s_overflow) {          // (uniform: every write of the flag lies before the barrier that ended the tree passes)
-            __syncthreads();
-            useHist = false;
-            if (dbg && tid == 0) atomicAdd((unsigned long long *) &dbg[16 * 8 + l], 1ull);   // restarts of this level over the launch's frames
-            goto restart;
+    __syncthreads();
+    // the candidates once more, linearly: best (score, then smallest index) per node
+    constexpr int kFU = 4;   // (every load of a round in flight before the first LDS operation: 60 dependent global round trips per thread were 40 us of a 3840x2160 level)
+    for (int i0 = tid; i0 < M; i0 += kFU * kBlock) {
+        unsigned v[kFU];
+#pragma unroll
+        for (int u = 0; u < kFU; u++) v[u] = w.key0[min(i0 + u * kBlock, M - 1)];
+#pragma unroll
+        for (int u = 0; u < kFU; u++) {
+            const int i = i0 + u * kBlock;
+            const int node = i < M ? PS[v[u] & 0xFFFFu] : -2 - lane;
+            const unsigned best = row_run_max(node, ((v[u] >> 16) << 24) | (0xFFFFFFu - (unsigned) i));
+            if (node >= 0 && row_run_last(node)) atomicMax((unsigned *) &S.kArr[node], best);
         }
     }
-    OSTAMP(4);
-    // ---- 5. best response per node (:702-720), output in list order ----
-    unsigned *oxy = lvlKpXY + (long long) f * kpStride + g.kpBase;
-    unsigned char *osc = lvlKpScore + (long long) f * kpStride + g.kpBase;
-    const int lane = lane_id(), wave = wave_id();
-    if (kHist && useHist) {
-        // first bin and log2 of the bin count of every final node (PS is still the prefix table)
-        for (int i = tid; i < n; i += kBlock) {
-            const int lo = (cur ? S.nlo[1] : S.nlo[0])[i], sh = 2 * (dm - (cur ? S.ndep[1] : S.ndep[0])[i]);
-            int a = 0, b = nBins >> sh;
-            while (b - a > 1) {
-                const int m = (a + b) >> 1;
-                if (PS[m << sh] <= lo) a = m; else b = m;
-            }
-            S.b1[i] = a << sh;
-            S.b2[i] = sh;
-            S.kArr[i] = 0;
-        }
-        __syncthreads();
-        // bin -> final node, written over the prefix table (sixteen lanes per node; bins outside every node hold no candidate)
-        for (int i0 = wave * 4; i0 < n; i0 += (kBlock / 64) * 4) {
-            const int i = i0 + (lane >> 4), sl16 = lane & 15;
-            if (i < n) {
-                const int f0 = S.b1[i], len = 1 << S.b2[i];
-                for (int k = sl16; k < len; k += 16) PS[f0 + k] = i;
-            }
-        }
-        __syncthreads();
-        // the candidates once more, linearly: best (score, then smallest index) per node
-        constexpr int kFU = 4;   // (every load of a round in flight before the first LDS operation: 60 dependent global round trips per thread were 40 us of a 3840x2160 level)
-        for (int i0 = tid; i0 < M; i0 += kFU * kBlock) {
-            unsigned w[kFU];
-#pragma unroll
-            for (int u = 0; u < kFU; u++) w[u] = key0[min(i0 + u * kBlock, M - 1)];
-#pragma unroll
-            for (int u = 0; u < kFU; u++) {
-                const int i = i0 + u * kBlock;
-                const int node = i < M ? PS[w[u] & 0xFFFFu] : -2 - lane;
-                const unsigned v = row_run_max(node, ((w[u] >> 16) << 24) | (0xFFFFFFu - (unsigned) i));
-                if (node >= 0 && row_run_last(node)) atomicMax((unsigned *) &S.kArr[node], v);
-            }
-        }
-    } else
-    for (int i0 = wave * 4; i0 < n; i0 += (kBlock / 64) * 4) {   // sixteen lanes (a DPP row) per node: arg-max over its range (LDS / DPP only);
-        const int i = i0 + (lane >> 4), sl16 = lane & 15;           // the final nodes hold ~10 candidates each
+}
+
+// ---- 5b. best response per node, sort plan: sixteen lanes (a DPP row) per node, arg-max over its range (LDS / DPP only); the final nodes hold ~10 candidates each ----
+template <int kBlock> __device__ __forceinline__ void oct_best_sorted(const OctLevel &w) {
+    const OctShared &S = w.S; const OctNodes in = oct_nodes(S, w.cur);
+    const int n = w.n, lane = lane_id(), wave = wave_id();
+    for (int i0 = wave * 4; i0 < n; i0 += (kBlock / 64) * 4) {
+        const int i = i0 + (lane >> 4), sl16 = lane & 15;
         const bool ok = i < n;
-        const int lo = ok ? (cur ? S.nlo[1] : S.nlo[0])[i] : 0, cnt = ok ? (cur ? S.ncnt[1] : S.ncnt[0])[i] : 0;
+        const int lo = ok ? in.lo[i] : 0, cnt = ok ? in.cnt[i] : 0;
         unsigned best = 0;
-        for (int k = sl16; k < cnt; k += 16) best = max(best, svals[lo + k]);
+        for (int k = sl16; k < cnt; k += 16) best = max(best, w.svals[lo + k]);
         best = max(best, (unsigned) __builtin_amdgcn_update_dpp(0, (int) best, 0xB1, 0xF, 0xF, true));    // quad_perm [1,0,3,2]
         best = max(best, (unsigned) __builtin_amdgcn_update_dpp(0, (int) best, 0x4E, 0xF, 0xF, true));    // quad_perm [2,3,0,1]
         best = max(best, (unsigned) __builtin_amdgcn_update_dpp(0, (int) best, 0x141, 0xF, 0xF, true));   // row_half_mirror
         best = max(best, (unsigned) __builtin_amdgcn_update_dpp(0, (int) best, 0x140, 0xF, 0xF, true));   // row_mirror
         if (ok && sl16 == 0) S.kArr[i] = (int) best;
     }
-    __syncthreads();
+}
+
+// ---- 6. output in list order (lvlKpXY, lvlKpScore, the count) and k_describe's work list procRec in processing order ----
+template <int kBlock> __device__ __forceinline__ void oct_emit_keypoints(const OctArgs &a, const OctLevel &w) {
+    const OctShared &S = w.S; const LevelGeom &g = w.g;
+    const int tid = w.tid, n = w.n;
+    unsigned *oxy = a.lvlKpXY + (long long) w.f * a.kpStride + g.kpBase;
+    unsigned char *osc = a.lvlKpScore + (long long) w.f * a.kpStride + g.kpBase;
     for (int i = tid; i < n; i += kBlock) {         // a thread per node: the dependent global read of the winner's position, all in flight at once
         const unsigned best = (unsigned) S.kArr[i];
         const unsigned idx = 0xFFFFFFu - (best & 0xFFFFFFu);
-        const unsigned p = xy[idx];
+        const unsigned p = w.xy[idx];
         const unsigned kx = (p & 0xFFFFu) + kBorder, ky = (p >> 16) + kBorder;
         oxy[i] = kx | (ky << 16);
         osc[i] = (unsigned char) (best >> 24);
@@ -2031,27 +2011,100 @@ restart:   // (kHist: a second time, on the sorting path, after the tree asked f
         S.sv[0][i] = (unsigned) i;
     }
     __syncthreads();
-    {
-        // (launches of a few frames -- one Tracking frame -- keep the list order: the sort buys cache locality across many frames' windows and
-        // costs two block-wide passes of its own)
-        unsigned *ok = S.sk[0], *ov = S.sv[0];
-        if (gridDim.y > 4) block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], n, 12, histT, s_tmp, &ok, &ov);
-        // k_describe's work list: processing position i -> (x | y << 16, score | list position << 8) in ONE record, so that a describe wave
-        // knows its keypoint after a single memory round trip (it used to follow procOrder -> position / score: two dependent ones)
-        // (score | list position << 8 | level << 24; positions past the level's count carry kNoKeypoint so that the wave there leaves at once)
-        uint2 *pr = procRec + (long long) f * kpStride + g.kpBase;
-        for (int i = tid; i < g.kpCap; i += kBlock) {
-            if (i < n) {
-                const unsigned li = ov[i];
-                pr[i] = make_uint2((unsigned) S.b1[li], (unsigned) S.b2[li] | (li << 8) | ((unsigned) l << 24));
-            } else pr[i] = make_uint2(0u, kNoKeypoint);
-        }
+    // (launches of a few frames -- one Tracking frame -- keep the list order: the sort buys cache locality across many frames' windows and
+    // costs two block-wide passes of its own)
+    unsigned *ok = S.sk[0], *ov = S.sv[0];
+    if (gridDim.y > 4) block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], n, 12, w.histT, w.tmp, &ok, &ov);
+    // k_describe's work list: processing position i -> (x | y << 16, score | list position << 8) in ONE record, so that a describe wave
+    // knows its keypoint after a single memory round trip (it used to follow procOrder -> position / score: two dependent ones)
+    // (score | list position << 8 | level << 24; positions past the level's count carry kNoKeypoint so that the wave there leaves at once)
+    uint2 *pr = a.procRec + (long long) w.f * a.kpStride + g.kpBase;
+    for (int i = tid; i < g.kpCap; i += kBlock) {
+        if (i < n) {
+            const unsigned li = ov[i];
+            pr[i] = make_uint2((unsigned) S.b1[li], (unsigned) S.b2[li] | (li << 8) | ((unsigned) w.l << 24));
+        } else pr[i] = make_uint2(0u, kNoKeypoint);
     }
-    if (tid == 0) *lvlCnt = n;
-    OSTAMP(5);
-    if (dbg && tid == 0 && f == 0) { dbg[l * 8 + 6] = M; dbg[l * 8 + 7] = n; }
-#undef OSTAMP
-#undef OBFS
+    if (tid == 0) *w.lvlCnt = n;
+}
+
+// kGlobalNodes: the 19 per-list-position arrays live in a global arena (nodeArena, 19 * cap ints per (frame, level)) instead of LDS --
+// configurations whose per-level feature budget is too large for the LDS plan (e.g. one level with > 2000 features).
+//
+// kHist (the plan of configurations whose levels hold tens of thousands of candidates -- 1920x1080 / 4000, 3840x2160 / 8000): NO SORT.  What the
+// tree passes ask of the sorted key array is (a) the child boundaries of a node = counts of candidates per key prefix and (b) the best
+// response per final node.  Both come from a histogram over the key prefixes of depth dm (nIni << 2 dm <= histBins bins, LDS atomics while the
+// keys are computed) and its exclusive prefix sum PS: the node (lo, cnt, dep) starts at the aligned bin f0 with PS[f0] == lo, its child
+// boundaries are PS[f0 + c * 4^(dm - dep - 1)] -- the very values digit_bounds3 finds in the sorted array, so the tree passes run unchanged; the
+// best response per node is one more pass over the candidates (bin -> final node table, LDS atomic max).  A level of 60 000 candidates spent
+// 1.4-1.7 ms in four scattered radix passes through global memory (4.6 GB written per 64-frame launch against 0.9 GB of keys) and 0.2-0.5 ms
+// in tree passes whose every boundary search was 11 dependent global reads; here the candidates are read twice, linearly, and the tree passes
+// stay in LDS.  A tree that wants to split a node BELOW depth dm (a few very crowded spots in an otherwise empty level) raises the overflow flag and
+// the workgroup starts over on the sorting path -- same result, the old speed.
+//
+// kHist, launches of a few frames (gridDim.z > 1): a level of one 3840x2160 frame is 60 000 candidates whose keys took ONE compute unit 95 us while
+// 250 others had nothing to do.  The workgroups z = 1 .. gridDim.z - 1 of a (level, frame) are helpers: each computes the keys of its share of the
+// candidates (keys and positions in the global candidate arrays as always, its bin counts into a slice of gHist), releases, bumps gDone and
+// leaves; workgroup 0 does its own share, waits for the others, adds their counts to its own and goes on alone.  gDone only ever grows (the host
+// passes the value this launch brings it to): should the helpers not arrive within the spin budget -- every compute unit held by waiting
+// workgroups 0 of many contexts at once -- workgroup 0 stops waiting, computes the whole level itself and ignores the slices; helpers that come
+// late write the same keys to the same places and bump a counter nobody reads again before the next launch.  The host launches helpers only while ALL workgroups of the launch fit the device together (ygzf_api.hip), so nobody waits for
+// a workgroup that cannot start.
+//
+// kBlock: threads per workgroup (1024 / 512 / 256).  The host sizes it per launch with the levels it carries (ygzf_api.hip, plan_oct_sort): a 1024-thread
+// workgroup holds half a CU's wave slots whatever its LDS, so that two of them left no room for the other contexts' FAST and describe waves.  Every loop
+// strides by it; the results do not depend on it.
+template <bool kGlobalNodes, bool kHist, int kBlock>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kHist ? 4 : 8, 8))) void k_octree(OctArgs a) {
+    static_assert(!(kGlobalNodes && kHist), "the histogram plan keeps the node arrays in LDS");
+    extern __shared__ __attribute__((aligned(16))) int dyn[];
+    __shared__ int histT[radix_hist_ints(kBlock / 64)];
+    __shared__ int s_tmp[20];
+    __shared__ unsigned long long s_tmp64[17];
+    __shared__ int s_cut, s_flagA, s_overflow;
+    __shared__ int s_head[4];
+    OctLevel w;
+    w.tid = threadIdx.x; w.l = blockIdx.x + a.levelBase; w.f = blockIdx.y; w.passEv = 0;
+    w.parts = kHist && a.gHist ? (int) gridDim.z : 1; w.part = kHist ? (int) blockIdx.z : 0;
+    w.histT = histT; w.tmp = s_tmp; w.tmp64 = s_tmp64; w.cut = &s_cut; w.flagA = &s_flagA; w.overflow = &s_overflow; w.head = s_head;
+    oct_stamp(w, a.dbg, 0);
+    w.g = a.geom[w.l];
+    const LevelGeom &g = w.g;
+    w.nCells = g.nCols * g.nRows;
+    w.lvlCnt = a.lvlKpCnt + w.f * a.nlevels + w.l;
+    w.gd = kHist && w.parts > 1 ? a.gDone + (w.f * a.nlevels + w.l) : nullptr;
+    w.gh = kHist && w.parts > 1 ? a.gHist + ((long long) w.f * a.nlevels + w.l) * (w.parts - 1) * a.histBins : nullptr;   // one slice of histBins counts per helper
+    if (w.nCells <= 0 || g.nCols <= 0) { oct_empty_level<kBlock>(a, w); return; }
+    oct_carve<kGlobalNodes, kHist>(a, w, dyn);
+    w.cc = a.cellCnt + (long long) w.f * a.totalCells + g.cellBase;
+    w.sl = a.slots + (long long) w.f * a.totalSlots + g.slotBase;
+    const long long cand = (long long) w.f * a.candStride + g.candBase;   // global scratch (the sort buffers: used when M > ldsCand)
+    w.key0 = a.candKey0 + cand; w.val0 = a.candVal0 + cand; w.key1 = a.candKey1 + cand; w.val1 = a.candVal1 + cand; w.xy = a.candXY + cand;
+    // kHist: depth dm of the histogram's key prefixes -- as deep as the bin budget allows (a level whose tree is fully resolved at dm cannot overflow)
+    w.dm = 0;
+    if (kHist) {
+        w.dm = g.depth;
+        while (w.dm > 0 && ((long long) g.nIni << (2 * w.dm)) > (long long) a.histBins) w.dm--;
+    }
+    w.nBins = g.nIni << (2 * w.dm);
+    w.binShift = 2 * (g.depth - w.dm);
+    // what survives an attempt at the level: the plan, and whether workgroup 0 gave up waiting for its helpers
+    bool useHist = kHist && w.dm >= 1, alone = false;
+    if (w.part != 0 && !useHist) { oct_helper_leaves(w); return; }   // (no histogram for this level: workgroup 0 sorts, alone)
+    for (;;) {
+        const OctOutcome o = oct_attempt<kHist, kBlock>(a, w, useHist, alone);
+        if (o == kOctLeft) return;
+        if (o == kOctDone) break;
+        if (o == kOctAgainAlone) alone = true;
+        else useHist = false;                  // (kOctAgainSorted)
+    }
+    oct_stamp(w, a.dbg, 4);
+    if (w.hist) oct_best_hist<kBlock>(w);
+    else oct_best_sorted<kBlock>(w);
+    __syncthreads();
+    oct_emit_keypoints<kBlock>(a, w);
+    oct_stamp(w, a.dbg, 5);
+    if (a.dbg && w.tid == 0 && w.f == 0) { a.dbg[w.l * 8 + 6] = w.M; a.dbg[w.l * 8 + 7] = w.n; }
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -2739,31 +2792,14 @@ hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist) {
     return e;
 }
 
-// levels [level0, level0 + nLaunchLevels) of every frame; histBins > 0 selects the histogram plan (regionInts ints shared by the cell table, the
-// key tables and the node arrays, then histBins + 1 ints of prefix table).  block: threads per workgroup of the sort plan with LDS node arrays
-// (1024, 512 or 256); the other two plans run 1024.
-void launch_octree(hipStream_t st, const LevelGeom *dGeom, int nlevels, int level0, int nLaunchLevels, const unsigned short *cellCnt, const unsigned *slots,
-                   int totalCells, long long totalSlots, unsigned *k0, unsigned *v0, unsigned *k1, unsigned *v1, unsigned *xy,
-                   long long candStride, unsigned *lvlKpXY, unsigned char *lvlKpScore, int *lvlKpCnt, int *lvlCandCnt,
-                   uint2 *procRec, int kpStride, int cap, int ldsCand, size_t ldsBytes, int nFrames, long long *dbg, int *nodeArena,
-                   int regionInts, int histBins, int helpers, int *gHist, int *gDone, int doneTarget, int spinBudget, int block) {
-    if (histBins > 0)
-        hipLaunchKernelGGL((k_octree<false, true, kOctBlock>), dim3(nLaunchLevels, nFrames, helpers > 1 && gHist ? helpers : 1), dim3(kOctBlock), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells,
-                           totalSlots, k0, v0, k1, v1, xy, candStride, lvlKpXY, lvlKpScore, lvlKpCnt, lvlCandCnt, procRec, kpStride, cap, 0,
-                           dbg, nullptr, regionInts, histBins, helpers > 1 ? gHist : nullptr, gDone, doneTarget, spinBudget);
-    else if (nodeArena)
-        hipLaunchKernelGGL((k_octree<true, false, kOctBlock>), dim3(nLaunchLevels, nFrames), dim3(kOctBlock), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells,
-                           totalSlots, k0, v0, k1, v1, xy, candStride, lvlKpXY, lvlKpScore, lvlKpCnt, lvlCandCnt, procRec, kpStride, cap, ldsCand,
-                           dbg, nodeArena, 0, 0, nullptr, nullptr, 0, 0);
-    else {
-#define YGZF_OCT_SORT_LAUNCH(B)                                                                                                                      \
-        hipLaunchKernelGGL((k_octree<false, false, B>), dim3(nLaunchLevels, nFrames), dim3(B), ldsBytes, st, dGeom, nlevels, level0, cellCnt, slots, totalCells, \
-                           totalSlots, k0, v0, k1, v1, xy, candStride, lvlKpXY, lvlKpScore, lvlKpCnt, lvlCandCnt, procRec, kpStride, cap, ldsCand,   \
-                           dbg, nodeArena, 0, 0, nullptr, nullptr, 0, 0)
-        if (block == 256) YGZF_OCT_SORT_LAUNCH(256);
-        else if (block == 512) YGZF_OCT_SORT_LAUNCH(512);
-        else YGZF_OCT_SORT_LAUNCH(1024);
-#undef YGZF_OCT_SORT_LAUNCH
+void launch_octree(hipStream_t st, const OctArgs &a, int nLaunchLevels, int nFrames, size_t ldsBytes, int block, int helpers) {
+    const dim3 grid(nLaunchLevels, nFrames, helpers);
+    switch (a.histBins > 0 ? 1 : a.nodeArena ? 2 : block) {
+        case 1: hipLaunchKernelGGL((k_octree<false, true, kOctBlock>), grid, dim3(kOctBlock), ldsBytes, st, a); break;
+        case 2: hipLaunchKernelGGL((k_octree<true, false, kOctBlock>), grid, dim3(kOctBlock), ldsBytes, st, a); break;
+        case 256: hipLaunchKernelGGL((k_octree<false, false, 256>), grid, dim3(256), ldsBytes, st, a); break;
+        case 512: hipLaunchKernelGGL((k_octree<false, false, 512>), grid, dim3(512), ldsBytes, st, a); break;
+        default: hipLaunchKernelGGL((k_octree<false, false, 1024>), grid, dim3(1024), ldsBytes, st, a); break;
     }
 }
 

@@ -84,12 +84,39 @@ size_t octree_lds_bytes(int maxCellsPerLevel, int cap, int ldsCand, bool globalN
 int octree_lds_cand(int maxCellsPerLevel, int cap, size_t budget);   // the sort plan's candidate budget within `budget` bytes of LDS node arrays + buffers (0: < 256)
 size_t octree_hist_lds_bytes(int regionInts, int histBins);
 hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist);
-void launch_octree(hipStream_t st, const LevelGeom *dGeom, int nlevels, int level0, int nLaunchLevels, const unsigned short *cellCnt, const unsigned *slots,
-                   int totalCells, long long totalSlots, unsigned *k0, unsigned *v0, unsigned *k1, unsigned *v1, unsigned *xy,
-                   long long candStride, unsigned *lvlKpXY, unsigned char *lvlKpScore, int *lvlKpCnt, int *lvlCandCnt,
-                   uint2 *procRec, int kpStride, int cap, int ldsCand, size_t ldsBytes, int nFrames, long long *dbg, int *nodeArena,
-                   int regionInts, int histBins, int helpers = 1, int *gHist = nullptr, int *gDone = nullptr, int doneTarget = 0, int spinBudget = 0,
-                   int block = kOctBlock);
+// One launch of k_octree: levels [levelBase, levelBase + gridDim.x) of gridDim.y frames, one workgroup per (level, frame) -- the histogram plan
+// with gridDim.z - 1 helper workgroups beside it.  histBins > 0 selects the histogram plan, nodeArena the sort plan with node arrays in global memory.
+struct OctArgs {
+    // inputs from FAST (frame f at f * totalCells / f * totalSlots)
+    const LevelGeom *geom;
+    int nlevels, levelBase;
+    const unsigned short *cellCnt;   // candidates per cell
+    const unsigned *slots;           // x | y << 8 | score << 16 within the cell
+    int totalCells;
+    long long totalSlots;
+    // candidate scratch, frame f at f * candStride: key / value double buffers of the sort (levels whose candidates exceed ldsCand), positions
+    unsigned *candKey0, *candVal0, *candKey1, *candVal1, *candXY;
+    long long candStride;
+    // outputs, frame f at f * kpStride (the counts: f * nlevels + level); procRec is k_describe's work list
+    unsigned *lvlKpXY;
+    unsigned char *lvlKpScore;
+    int *lvlKpCnt, *lvlCandCnt;
+    uint2 *procRec;
+    int kpStride;
+    // list and LDS sizes: list capacity of the launch's levels (a multiple of 4); sort plan: candidates of a level that are sorted in LDS (0 in the
+    // histogram plan); nullable: 19 * cap ints per (frame, level) for the node arrays instead of LDS
+    int cap, ldsCand;
+    int *nodeArena;
+    // histogram plan (histBins > 0): regionInts ints shared by the cell table, the key tables and the node arrays, then histBins + 1 ints of prefix table
+    int regionInts, histBins;
+    // helper hand-over (gHist non-null: gridDim.z workgroups per (level, frame)): one slice of histBins counts per helper; per (frame, level) the helpers
+    // that have left, only ever growing, and the value this launch brings it to; sleeps after which workgroup 0 stops waiting
+    int *gHist, *gDone;
+    int doneTarget, spinBudget;
+    long long *dbg;                  // nullable: kOctDbgWords phase stamps and counters (YGZF_DEBUG=oct)
+};
+// block: threads per workgroup of the sort plan with LDS node arrays (1024, 512 or 256); the other two plans run kOctBlock.  helpers: gridDim.z
+void launch_octree(hipStream_t st, const OctArgs &a, int nLaunchLevels, int nFrames, size_t ldsBytes, int block, int helpers);
 constexpr int kOctDbgAlone = 16 * 8 + 16 + 16 * 16;  // per level: six phase stamps, M, n; then per level the workgroups that left the histogram plan; then per level up to 8 (list size, time) pairs of the tree passes;
 constexpr int kOctDbgAloneFrames = kOctDbgAlone + 16; // then per level the workgroups 0 that gave up waiting for their helpers (computed the level alone); then a mask of the frames (< 64) where that happened
 constexpr int kOctDbgWords = kOctDbgAloneFrames + 1;

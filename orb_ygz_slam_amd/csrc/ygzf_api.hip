@@ -390,6 +390,36 @@ std::vector<OctSortGroup> ygzf::plan_oct_sort(const Geometry &G, int L, bool one
     return out;
 }
 
+// A histogram-plan launch of levels [l0, l0 + n): list capacity, the region the cell table, the key tables and the node arrays share, and the bins
+// within 150 KB of LDS -- first the key tables go, then (unless binsEnv pins them) the bins are halved down to 1024.  The bins wanted: 8192, or with
+// perNode sixteen per node the largest level may end with (a tree of N leaves rarely splits below the depth that offers 16 N cells; if it does, the
+// level restarts on the sorting path) -- the prefix sum over 8192 bins was 3.3 of a level's 29 us, over 2048 it is 1.  False when the launch does not
+// fit even so.
+static bool size_oct_hist_group(const Geometry &G, int l0, int n, int binsEnv, bool perNode, ygzf_ctx::OctGroup *out) {
+    ygzf_ctx::OctGroup grp;
+    grp.l0 = l0;
+    grp.n = n;
+    int cells = 0, tabs = 0;
+    for (int l = l0; l < l0 + n; l++) {
+        const LevelGeom &g = G.lv[l];
+        const int nc = g.nCols * g.nRows;
+        grp.cap = std::max(grp.cap, (g.kpCap + 3) & ~3);
+        cells = std::max(cells, nc + 1);
+        if (nc > 0) tabs = std::max(tabs, nc + 1 + std::max(g.regW, g.nCols * g.wCell) + 9 + std::max(g.regH, g.nRows * g.hCell) + 9 + nc);
+    }
+    if (grp.cap < 4) grp.cap = 4;
+    const size_t budget = 150 * 1024;
+    int want = perNode ? 1024 : 8192;
+    while (want < 16 * grp.cap && want < 8192) want *= 2;
+    grp.histBins = binsEnv >= 4 && binsEnv <= 8192 ? binsEnv : want;
+    grp.regionInts = std::max(std::max(19 * grp.cap, cells), tabs);
+    if (octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.regionInts = std::max(19 * grp.cap, cells);   // keys without the tables
+    while (grp.histBins > 1024 && !binsEnv && octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.histBins /= 2;
+    grp.lds = octree_hist_lds_bytes(grp.regionInts, grp.histBins);
+    *out = grp;
+    return grp.lds <= budget;
+}
+
 int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
     if (w < 1 || h < 1) return fail(c, YGZF_ERR_INVALID, "image size %dx%d", w, h);
     if (w > c->maxW || h > c->maxH) return fail(c, YGZF_ERR_INVALID, "image %dx%d exceeds the context maximum %dx%d", w, h, c->maxW, c->maxH);
@@ -470,26 +500,12 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
         if (wantHist) {
             bool ok = true;
             for (int l = 0; l < L && ok;) {
+                int n = 1;
+                while (l + n < L && 2 * G.lv[l + n].kpCap > G.lv[l].kpCap) n++;
                 ygzf_ctx::OctGroup grp;
-                grp.l0 = l;
-                int cells = 0, tabs = 0;
-                for (; l < L && (grp.n == 0 || 2 * G.lv[l].kpCap > G.lv[grp.l0].kpCap); l++, grp.n++) {
-                    const LevelGeom &g = G.lv[l];
-                    const int nc = g.nCols * g.nRows;
-                    grp.cap = std::max(grp.cap, (g.kpCap + 3) & ~3);
-                    cells = std::max(cells, nc + 1);
-                    if (nc > 0)
-                        tabs = std::max(tabs, nc + 1 + std::max(g.regW, g.nCols * g.wCell) + 9 + std::max(g.regH, g.nRows * g.hCell) + 9 + nc);
-                }
-                if (grp.cap < 4) grp.cap = 4;
-                const size_t budget = 150 * 1024;
-                grp.histBins = binsEnv >= 4 && binsEnv <= 8192 ? binsEnv : 8192;
-                grp.regionInts = std::max(std::max(19 * grp.cap, cells), tabs);
-                if (octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.regionInts = std::max(19 * grp.cap, cells);   // keys without the tables
-                while (grp.histBins > 1024 && !binsEnv && octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.histBins /= 2;
-                grp.lds = octree_hist_lds_bytes(grp.regionInts, grp.histBins);
-                if (grp.lds > budget) ok = false;
+                ok = size_oct_hist_group(G, l, n, binsEnv, false, &grp);
                 c->octGroups.push_back(grp);
+                l += n;
             }
             if (!ok) c->octGroups.clear();
         }
@@ -498,30 +514,7 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
         // the largest (with a handful of workgroups nobody else wants the LDS).  Launches of up to 128 workgroups take it (YGZF_OCT_SMALL_WGS; YGZF_OCT_PLAN=sort: never).
         c->haveOctSmall = false;
         if (!forced_is("oct_plan", "sort")) {
-            ygzf_ctx::OctGroup grp;
-            grp.l0 = 0;
-            grp.n = L;
-            int cells = 0, tabs = 0;
-            for (int l = 0; l < L; l++) {
-                const LevelGeom &g = G.lv[l];
-                const int nc = g.nCols * g.nRows;
-                grp.cap = std::max(grp.cap, (g.kpCap + 3) & ~3);
-                cells = std::max(cells, nc + 1);
-                if (nc > 0) tabs = std::max(tabs, nc + 1 + std::max(g.regW, g.nCols * g.wCell) + 9 + std::max(g.regH, g.nRows * g.hCell) + 9 + nc);
-            }
-            if (grp.cap < 4) grp.cap = 4;
-            const size_t budget = 150 * 1024;
-            // bins: sixteen per node the largest level may end with (a tree of N leaves rarely splits below the depth that offers 16 N cells; if it
-            // does, the level restarts on the sorting path) -- the prefix sum over 8192 bins was 3.3 of a level's 29 us, over 2048 it is 1
-            int want = 1024;
-            while (want < 16 * grp.cap && want < 8192) want *= 2;
-            grp.histBins = binsEnv >= 4 && binsEnv <= 8192 ? binsEnv : want;
-            grp.regionInts = std::max(std::max(19 * grp.cap, cells), tabs);
-            if (octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.regionInts = std::max(19 * grp.cap, cells);
-            while (grp.histBins > 1024 && !binsEnv && octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.histBins /= 2;
-            grp.lds = octree_hist_lds_bytes(grp.regionInts, grp.histBins);
-            if (grp.lds <= budget) {
-                c->octSmall = grp;
+            if (size_oct_hist_group(G, 0, L, binsEnv, true, &c->octSmall)) {
                 c->haveOctSmall = true;
                 HIPCHECK(c, octree_prepare(0, false, true));
             }
@@ -725,18 +718,34 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
         }
         int smallHelpers = 0;   // workgroups per (level, frame) of the small plan's launch (0: another plan)
         bool sortGroups = false;   // the sort plan's level groups ran (c->octSortGroups)
+        bool oneLaunch = false;    // ... or the sort plan's single launch of all levels (node arrays in LDS or in the global arena)
         {
             hipStream_t so = c->stream;
             ProfScope ps(c, KK_OCTREE, so);
+            // what every plan's launch shares; a plan adds the levels, its list and LDS sizes and what is its own
+            auto oct_args = [&](int l0, int cap) {
+                OctArgs a{};
+                a.geom = dGeom; a.nlevels = L; a.levelBase = l0; a.cap = cap; a.dbg = odbg;
+                a.cellCnt = (const unsigned short *) c->dCellCnt.p; a.slots = (const unsigned *) c->dSlots.p; a.totalCells = G.totalCells; a.totalSlots = G.totalSlots;
+                a.candKey0 = (unsigned *) c->dK0.p; a.candVal0 = (unsigned *) c->dV0.p; a.candKey1 = (unsigned *) c->dK1.p; a.candVal1 = (unsigned *) c->dV1.p;
+                a.candXY = (unsigned *) c->dXY.p; a.candStride = G.candStride; a.procRec = (uint2 *) c->dProcOrder.p; a.kpStride = G.kpStride;
+                a.lvlKpXY = (unsigned *) c->dLvlXY.p; a.lvlKpScore = (unsigned char *) c->dLvlScore.p; a.lvlKpCnt = (int *) c->dLvlCnt.p; a.lvlCandCnt = (int *) c->dLvlCand.p;
+                return a;
+            };
+            auto hist_args = [&](const ygzf_ctx::OctGroup &grp) {   // (the histogram plan sorts nothing in LDS: ldsCand stays 0)
+                OctArgs a = oct_args(grp.l0, grp.cap);
+                a.regionInts = grp.regionInts; a.histBins = grp.histBins;
+                return a;
+            };
             const bool small = c->haveOctSmall && nFrames * L <= c->octSmallWgs;
             if (small) {
                 const auto &grp = c->octSmall;
+                OctArgs a = hist_args(grp);
                 // helper workgroups for the keys of a level (k_octree): as many as keep the WHOLE launch resident at one workgroup per compute unit
                 // (workgroup 0 of a level waits for its helpers), at most 8, and only where a level is worth the hand-over (a few microseconds)
                 int helpers = c->octHelpersForced;
                 if (helpers < 0) helpers = G.totalCells >= 2000 ? std::min(8, std::max(1, c->cuCount) / std::max(1, nFrames * L)) : 1;
                 helpers = std::max(1, std::min(helpers, std::min(8, std::max(1, c->cuCount / std::max(1, nFrames * L)))));
-                int *gHist = nullptr, *gDone = nullptr;
                 if (helpers > 1) {
                     const size_t words = (size_t) nFrames * L * (helpers - 1) * grp.histBins, bytes = (words + 64) * sizeof(int) + (size_t) nFrames * L * sizeof(int);
                     int rcH = ensure(c, c->dOctHist, bytes);
@@ -754,39 +763,27 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
                         c->octDoneTarget = 0;
                     }
                     c->octDoneTarget += helpers - 1;
-                    gHist = (int *) c->dOctHist.p;
-                    gDone = gHist + words;
+                    a.gHist = (int *) c->dOctHist.p;       // (helpers only with a gHist: without one the launch has one workgroup per level)
+                    a.gDone = a.gHist + words;
                 }
                 smallHelpers = helpers;
-                launch_octree(so, dGeom, L, grp.l0, grp.n, (const unsigned short *) c->dCellCnt.p, (const unsigned *) c->dSlots.p,
-                              G.totalCells, G.totalSlots, (unsigned *) c->dK0.p, (unsigned *) c->dV0.p, (unsigned *) c->dK1.p,
-                              (unsigned *) c->dV1.p, (unsigned *) c->dXY.p, G.candStride, (unsigned *) c->dLvlXY.p,
-                              (unsigned char *) c->dLvlScore.p, (int *) c->dLvlCnt.p, (int *) c->dLvlCand.p,
-                              (uint2 *) c->dProcOrder.p, G.kpStride, grp.cap, 0, grp.lds, nFrames, odbg, nullptr, grp.regionInts, grp.histBins,
-                              helpers, gHist, gDone, c->octDoneTarget, c->octHelperSpin);
+                a.doneTarget = c->octDoneTarget; a.spinBudget = c->octHelperSpin;
+                launch_octree(so, a, grp.n, nFrames, grp.lds, kOctBlock, helpers);
             } else if (c->octGroups.empty() && !c->octSortGroups.empty()) {
                 sortGroups = true;
-                for (const auto &grp : c->octSortGroups)
-                    launch_octree(so, dGeom, L, grp.l0, grp.n, (const unsigned short *) c->dCellCnt.p, (const unsigned *) c->dSlots.p,
-                                  G.totalCells, G.totalSlots, (unsigned *) c->dK0.p, (unsigned *) c->dV0.p, (unsigned *) c->dK1.p,
-                                  (unsigned *) c->dV1.p, (unsigned *) c->dXY.p, G.candStride, (unsigned *) c->dLvlXY.p,
-                                  (unsigned char *) c->dLvlScore.p, (int *) c->dLvlCnt.p, (int *) c->dLvlCand.p,
-                                  (uint2 *) c->dProcOrder.p, G.kpStride, grp.cap, grp.ldsCand, grp.lds, nFrames, odbg, nullptr, 0, 0,
-                                  1, nullptr, nullptr, 0, 0, grp.block);
-            } else if (c->octGroups.empty())
-                launch_octree(so, dGeom, L, 0, L, (const unsigned short *) c->dCellCnt.p, (const unsigned *) c->dSlots.p,
-                              G.totalCells, G.totalSlots, (unsigned *) c->dK0.p, (unsigned *) c->dV0.p, (unsigned *) c->dK1.p,
-                              (unsigned *) c->dV1.p, (unsigned *) c->dXY.p, G.candStride, (unsigned *) c->dLvlXY.p,
-                              (unsigned char *) c->dLvlScore.p, (int *) c->dLvlCnt.p, (int *) c->dLvlCand.p,
-                              (uint2 *) c->dProcOrder.p, G.kpStride, G.kpCapMax, c->octLdsCand, c->octLds, nFrames, odbg,
-                              c->octGlobalNodes ? (int *) c->dOctNodes.p : nullptr, 0, 0);
-            else
-                for (const auto &grp : c->octGroups)
-                    launch_octree(so, dGeom, L, grp.l0, grp.n, (const unsigned short *) c->dCellCnt.p, (const unsigned *) c->dSlots.p,
-                                  G.totalCells, G.totalSlots, (unsigned *) c->dK0.p, (unsigned *) c->dV0.p, (unsigned *) c->dK1.p,
-                                  (unsigned *) c->dV1.p, (unsigned *) c->dXY.p, G.candStride, (unsigned *) c->dLvlXY.p,
-                                  (unsigned char *) c->dLvlScore.p, (int *) c->dLvlCnt.p, (int *) c->dLvlCand.p,
-                                  (uint2 *) c->dProcOrder.p, G.kpStride, grp.cap, 0, grp.lds, nFrames, odbg, nullptr, grp.regionInts, grp.histBins);
+                for (const auto &grp : c->octSortGroups) {
+                    OctArgs a = oct_args(grp.l0, grp.cap);
+                    a.ldsCand = grp.ldsCand;
+                    launch_octree(so, a, grp.n, nFrames, grp.lds, grp.block, 1);
+                }
+            } else if (c->octGroups.empty()) {
+                oneLaunch = true;
+                OctArgs a = oct_args(0, G.kpCapMax);
+                a.ldsCand = c->octLdsCand;
+                a.nodeArena = c->octGlobalNodes ? (int *) c->dOctNodes.p : nullptr;
+                launch_octree(so, a, L, nFrames, c->octLds, kOctBlock, 1);
+            } else
+                for (const auto &grp : c->octGroups) launch_octree(so, hist_args(grp), grp.n, nFrames, grp.lds, kOctBlock, 1);
         }
         if (odbg) {
             long long st[kOctDbgWords];
@@ -815,6 +812,9 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
                     fprintf(stderr, " levels %d-%d threads %d cap %d candidates %d lds %zu;", grp.l0, grp.l0 + grp.n - 1, grp.block, grp.cap, grp.ldsCand, grp.lds);
                 fprintf(stderr, "]\n");
             }
+            if (oneLaunch)
+                fprintf(stderr, "[ygzf octree single launch: levels 0-%d cap %d candidates %d lds %zu node arrays in %s]\n", L - 1, G.kpCapMax, c->octLdsCand, c->octLds,
+                        c->octGlobalNodes ? "the arena" : "lds");
             if (smallHelpers) {
                 fprintf(stderr, "[ygzf octree small plan: %d frames, %d workgroups per level; workgroups 0 that gave up waiting for their helpers, per level:", nFrames, smallHelpers);
                 for (int l = 0; l < L; l++) fprintf(stderr, " %lld", st[kOctDbgAlone + l]);

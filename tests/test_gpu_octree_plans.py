@@ -1,8 +1,10 @@
 """DistributeOctTree (src/ORBextractor.cc:533-723) on the device has two plans (extract_kernels.hip, k_octree): candidates SORTED by path key
 (levels whose candidates fit LDS: the 752x480 class) and the HISTOGRAM plan (1920x1080 / 3840x2160: counts per key prefix + prefix sum instead
 of a sort; a tree that splits below the histogram's depth sends its workgroup back to the sorting path).  Same bytes from every plan, from the
-fall-back between them, and from launches grouped by level: octree list order per level, keypoints, descriptors -- against the oracle."""
+fall-back between them, and from launches grouped by level: octree list order per level, keypoints, descriptors -- against the oracle.  A list
+capacity too large for either plan's LDS leaves the sorting kernel with its node arrays in a global arena: the last test here."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -131,3 +133,55 @@ def test_helpers_are_what_the_large_frame_takes(oracle):
     for fld in ("x", "y", "size", "angle", "response", "octave", "class_id"):
         assert (res[0][0][fld] == ok[fld]).all(), fld
     assert np.array_equal(od, res[0][1])
+
+
+_ARENA = re.compile(r"\[ygzf octree single launch: levels 0-(\d+) cap (\d+) candidates (\d+) lds (\d+) node arrays in (the arena|lds)\]")
+_LEVEL = re.compile(r"\[ygzf octree lvl (\d+), 10ns ticks\].* M=(\d+) n=(\d+)")
+_PLANS = re.compile(r"\[ygzf octree (small|histogram|sort) plan")
+
+
+@pytest.mark.parametrize("make,spills", [
+    (lambda: np.random.default_rng(3).integers(0, 256, (240, 320), dtype=np.uint8), True),   # level 0: 5867 candidates (oracle), 2728 kept
+    (lambda: synth_frame(44, 320, 240), False),                                              # level 0: 395 candidates, all kept
+], ids=["noise", "synth"])
+def test_node_arrays_in_the_global_arena(oracle, capfd, make, spills):
+    """320x240 / 2 levels / 5000 features: level 0's list holds 2732 nodes, 19 x 2732 ints of node arrays fit neither LDS plan, and the one kernel left
+    is k_octree<true, false, 1024> with the node arrays in a global arena -- asserted from the YGZF_DEBUG=oct report, which names the launch.  The noise
+    image's level 0 holds more candidates than the launch sorts in LDS (and more than the tree may keep), the synthetic frame's stays below: the sort
+    through global memory and the one in LDS.  Three frames, two launches on the one context -- the oracle's tree."""
+    from orb_ygz_slam_amd import Extractor
+    w, h, nl, nf = 320, 240, 2, 5000
+    img = make()
+    old = os.environ.get("YGZF_DEBUG")
+    os.environ["YGZF_DEBUG"] = "oct"
+    try:
+        ex = Extractor(nf, 1.2, nl, 20, 7, max_width=w, max_height=h, max_batch=3)
+    finally:
+        if old is None:
+            os.environ.pop("YGZF_DEBUG", None)
+        else:
+            os.environ["YGZF_DEBUG"] = old
+    oex = oracle.Extractor(nf, 1.2, nl, 20, 7)
+    imgs = np.stack([img, np.ascontiguousarray(img[::-1]), img])
+    for rep in range(2):
+        capfd.readouterr()
+        ex.extract_batch_host(imgs)
+        err = capfd.readouterr().err
+        assert not _PLANS.search(err), "another octree plan ran"
+        launches = _ARENA.findall(err)
+        assert len(launches) == 1, "the single launch did not run (exactly once)"
+        last, cap, lds_cand, _, where = launches[0]
+        assert (int(last), int(cap), where) == (nl - 1, 2732, "the arena")
+        M = {int(l): (int(m), int(n)) for l, m, n in _LEVEL.findall(err)}   # frame 0
+        assert sorted(M) == list(range(nl))
+        print("ldsCand %s, frame 0 (M, n) per level %r" % (lds_cand, M))
+        if spills:
+            assert M[0][0] > int(lds_cand) and M[0][0] > M[0][1]
+        else:
+            assert 0 < M[0][0] <= int(lds_cand)
+        _cmp_frame(oracle, ex, oex, imgs[0], frame=0)
+        _cmp_frame(oracle, ex, oex, imgs[1], frame=1)
+        k0, d0 = ex.batch_fetch(0)
+        k2, d2 = ex.batch_fetch(2)
+        assert np.array_equal(k0, k2) and np.array_equal(d0, d2)
+    ex.close()
