@@ -302,6 +302,29 @@ int ygzf_search_by_bow(ygzf_ctx *ctx, int n_nodes, const int *kf_off, const int 
                        const uint8_t *kf_valid, const ygzf_kp *kf_keys, const uint8_t *kf_desc, int n_f, const ygzf_kp *f_keys, const uint8_t *f_desc,
                        float nnratio, int check_orientation, int *match, int *nmatches);
 
+/* ---- ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, vector<MapPoint*> &vpMatches12)   src/ORBmatcher.cc:480-595, for one KF1
+ *      against n_cand candidate KF2s (LoopClosing::ComputeSim3, src/LoopClosing.cc:238-261: one call per consistent candidate, always
+ *      against the current keyframe) ------------------------------------------------------------------------------------------------------
+ * Per candidate the joined node list of the FeatureVector merge-join (:507-575), as for ygzf_search_by_bow.  valid1[i] / valid[i] = the
+ * MapPoint in slot i of KF1 / the candidate exists and is not bad; a candidate feature without one is never best and never second best
+ * (:527-533).  Accepted iff bestDist1 < TH_LOW (:548, strict) and bestDist1 < nnratio * bestDist2; an accepted candidate feature is
+ * taken for the KF1 features after it (vbMatched2) and stays taken when the rotation check culls the match.
+ * match12 (n_cand x n1 ints, row = candidate): candidate feature whose MapPoint lands in vpMatches12[i]; -1 none; -2 culled by the
+ * rotation check.  nmatches (n_cand ints).  Both are preset (-1 / 0) before any error return.  n_cand = 0, n1 = 0, or a candidate with
+ * n = 0 or n_nodes = 0: nothing to match, YGZF_OK.  At most 4096 candidate features per node.  The call uses scratch buffers only: a
+ * context in the middle of a batch keeps its state. */
+typedef struct ygzf_bow_kf_candidate {
+    int n;                      /* pKF2->N */
+    const ygzf_kp *keys;        /* pKF2->mvKeys */
+    const uint8_t *desc;        /* n x 32 */
+    const uint8_t *valid;       /* MapPoint in slot i exists and is not bad */
+    int n_nodes;                /* nodes common to both FeatureVectors, ascending id */
+    const int *off1, *idx1;     /* KF1 features of node k: idx1[off1[k] .. off1[k+1]) */
+    const int *off2, *idx2;     /* KF2 features of node k */
+} ygzf_bow_kf_candidate;
+int ygzf_search_by_bow_kf(ygzf_ctx *ctx, int n1, const ygzf_kp *keys1, const uint8_t *desc1, const uint8_t *valid1, int n_cand,
+                          const ygzf_bow_kf_candidate *cands, float nnratio, int check_orientation, int *match12, int *nmatches);
+
 /* ---- ORBmatcher::SearchForTriangulation(KeyFrame *pKF1, KeyFrame *pKF2, Matrix3f &F12, vector<pair<size_t,size_t>> &vMatchedPairs,
  *      const bool bOnlyStereo)   src/ORBmatcher.cc:596-741, with CheckDistEpipolarLine :136-153 (LocalMapping::CreateNewMapPoints) -----------
  * Joined node list as for ygzf_search_by_bow: node k pairs the features idx1[off1[k] .. off1[k+1]) of KF1 with idx2[off2[k] .. off2[k+1])

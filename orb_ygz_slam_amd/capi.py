@@ -49,6 +49,11 @@ class FusePoints(C.Structure):
                 ("mf_max_distance", C.c_void_p), ("desc", C.c_void_p)]
 
 
+class BowKfCandidate(C.Structure):
+    _fields_ = [("n", C.c_int), ("keys", C.c_void_p), ("desc", C.c_void_p), ("valid", C.c_void_p), ("n_nodes", C.c_int), ("off1", C.c_void_p),
+                ("idx1", C.c_void_p), ("off2", C.c_void_p), ("idx2", C.c_void_p)]
+
+
 class Sim3Transforms(C.Structure):
     _fields_ = [("R1w", C.c_float * 9), ("t1w", C.c_float * 3), ("R2w", C.c_float * 9), ("t2w", C.c_float * 3), ("sR12", C.c_float * 9),
                 ("t12", C.c_float * 3), ("sR21", C.c_float * 9), ("t21", C.c_float * 3)]
@@ -152,6 +157,7 @@ def load_library(build_if_missing=True):
     L.ygzf_search_for_initialization.argtypes = [vp, C.POINTER(FrameView), C.POINTER(FrameView), C.POINTER(Camera), vp, C.c_int, C.c_float, C.c_int,
                                                  vp, ip]
     L.ygzf_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, vp, ip]
+    L.ygzf_search_by_bow_kf.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(BowKfCandidate), C.c_float, C.c_int, vp, vp]
     L.ygzf_search_for_triangulation.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(FrameView), vp, C.POINTER(FrameView), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(Camera), C.c_int, C.c_int, vp, ip]
     L.ygzf_fuse_candidates.argtypes = [vp, C.c_int, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
@@ -599,6 +605,36 @@ class Extractor:
         self._ck(self.L.ygzf_search_by_bow(self.h, len(ko) - 1, _p(ko), _p(ki), _p(fo), _p(fi), len(kk), _p(kv), _p(kk), _p(kd), len(fk), _p(fk),
                                            _p(fd), nnratio, int(check_ori), _p(match), C.byref(n)))
         return n.value, match[:len(fk)]
+
+    def search_by_bow_kf(self, kf1, cands, nnratio=0.75, check_ori=True):
+        """ORBmatcher::SearchByBoW(KF1, KF2) for one KF1 against K candidates in one call -> (match12[K, n1], nmatches[K]).  kf1: dict with keys
+        (KP_DTYPE), desc, valid (bytes: the slot's MapPoint exists and is not bad); cands: dicts with keys, desc, valid and the joined node
+        list off1, idx1 (KF1 features), off2, idx2 (the candidate's).  match12: candidate feature, -1 none, -2 culled by the rotation check.
+        An entry that is None goes down as a null pointer; "n" / "n_nodes" override the counts taken from keys / off1."""
+        keep = []
+
+        def arr(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dt)
+            keep.append(a)
+            return a.ctypes.data
+
+        def count(d, key, a, less=0):
+            return int(d[key]) if key in d else (0 if d.get(a) is None else max(len(d[a]) - less, 0))
+
+        n1 = count(kf1, "n", "keys")
+        K = len(cands)
+        recs = (BowKfCandidate * max(K, 1))()
+        for k, q in enumerate(cands):
+            recs[k] = BowKfCandidate(count(q, "n", "keys"), arr(q.get("keys"), KP_DTYPE), arr(q.get("desc"), np.uint8), arr(q.get("valid"), np.uint8),
+                                     count(q, "n_nodes", "off1", 1), arr(q.get("off1"), np.int32), arr(q.get("idx1"), np.int32),
+                                     arr(q.get("off2"), np.int32), arr(q.get("idx2"), np.int32))
+        match12 = np.full((max(K, 1), max(n1, 1)), -1, np.int32)
+        nm = np.zeros(max(K, 1), np.int32)
+        self._ck(self.L.ygzf_search_by_bow_kf(self.h, n1, arr(kf1.get("keys"), KP_DTYPE), arr(kf1.get("desc"), np.uint8), arr(kf1.get("valid"), np.uint8),
+                                              K, recs, nnratio, int(check_ori), _p(match12), _p(nm)))
+        return match12[:K, :max(n1, 0)].copy(), nm[:K].copy()
 
     def search_for_triangulation(self, off1, idx1, off2, idx2, kf1, kf2, scale_factors2, level_sigma2_2, F12, Cw1, R2w, t2w, cam2,
                                  only_stereo=False, check_ori=True):

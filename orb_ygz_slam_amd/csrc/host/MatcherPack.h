@@ -26,6 +26,15 @@ struct PackMaxDistanceTag {
 template struct PackMemberOf<PackMaxDistanceTag, &MapPoint::mfMaxDistance>;
 inline float max_distance(MapPoint *mp) { return mp->*member_ptr(PackMaxDistanceTag()); }
 
+// the rows of an N x 32 descriptor matrix as one block: the Mat's own buffer when it is continuous, a packed copy in `hold` otherwise
+inline const uint8_t *desc_rows(const cv::Mat &D, int n, std::vector<uint8_t> &hold) {
+    if (n <= 0) return nullptr;
+    if (D.isContinuous() && D.cols == 32) return D.ptr<uint8_t>(0);
+    hold.resize((size_t) n * 32);
+    for (int i = 0; i < n; i++) std::memcpy(&hold[(size_t) i * 32], D.ptr<uint8_t>(i), 32);
+    return hold.data();
+}
+
 // A keyframe's keys, descriptors (copied into `hold` when the cv::Mat is not 32 contiguous bytes per row), mvuRight, scale tables, mvInvLevelSigma2,
 // image bounds and mfLogScaleFactor; fx fy cx cy mbf from `cam` (SearchBySim3 projects both directions with pKF1's).  The pose is the caller's.
 inline bool pack_keyframe(KeyFrame *pKF, const KeyFrame *cam, ygzf_fuse_kf &f, std::vector<uint8_t> &hold, const char *who) {
@@ -33,14 +42,7 @@ inline bool pack_keyframe(KeyFrame *pKF, const KeyFrame *cam, ygzf_fuse_kf &f, s
     const int n = pKF->N;
     f.view.n = n;
     f.view.keys = (const ygzf_kp *) pKF->mvKeys.data();
-    const cv::Mat &D = pKF->mDescriptors;
-    if (n > 0 && !(D.isContinuous() && D.cols == 32)) {
-        hold.resize((size_t) n * 32);
-        for (int i = 0; i < n; i++) std::memcpy(&hold[(size_t) i * 32], D.ptr<uint8_t>(i), 32);
-        f.view.desc = hold.data();
-    } else {
-        f.view.desc = n > 0 ? D.ptr<uint8_t>(0) : nullptr;
-    }
+    f.view.desc = desc_rows(pKF->mDescriptors, n, hold);
     f.view.u_right = (int) pKF->mvuRight.size() == n ? pKF->mvuRight.data() : nullptr;
     f.view.scale_factors = pKF->mvScaleFactors.data();
     f.view.nlevels = pKF->mnScaleLevels;

@@ -4,8 +4,8 @@
 //   ORBmatcher(float, bool), DescriptorDistance, the three Tracking-side SearchByProjection overloads, SearchByBoW(KeyFrame*, Frame&, ...),
 //   SearchForInitialization, SearchForTriangulation, FindDirectProjection   (src/ORBmatcher.cc:36-133, 155-263, 375-478, 596-741, 1218-1602);
 // the other LocalMapping / LoopClosing members have their device forms in files of their own, linked beside this one where wanted
-// (link recipe): Fuse(KeyFrame*, const vector<MapPoint*>&, th) in ORBmatcherFuse.cc; Fuse(KF, Scw, ...), SearchBySim3 and
-// SearchByProjection(KF, Scw, ...) in ORBmatcherLoop.cc.  SearchByBoW(KF, KF, ...) keeps its reference body.
+// (link recipe): Fuse(KeyFrame*, const vector<MapPoint*>&, th) in ORBmatcherFuse.cc; Fuse(KF, Scw, ...), SearchBySim3,
+// SearchByProjection(KF, Scw, ...) and SearchByBoW(KF, KF, ...) in ORBmatcherLoop.cc.
 #include "ORBextractor.h"   // first: inside the reference tree this is the replacement header (same include guard)
 #include "ORBmatcher.h"     // the reference's own header (reference tree) or standalone/ORBmatcher.h, by include path
 #include "ygz_compat.h"

@@ -1,13 +1,13 @@
-// ORBmatcherLoop.cc -- the three projection searches LoopClosing calls, over libygzf (product code, host side):
+// ORBmatcherLoop.cc -- the four matcher searches LoopClosing calls, over libygzf (product code, host side):
+//   ORBmatcher::SearchByBoW(pKF1, pKF2, vpMatches12)                     src/ORBmatcher.cc:480-595    ygzf_search_by_bow_kf
 //   ORBmatcher::Fuse(pKF, Scw, vpPoints, th, vpReplacePoint)            src/ORBmatcher.cc:888-1004   ygzf_fuse_sim3_candidates
 //   ORBmatcher::SearchByProjection(pKF, Scw, vpPoints, vpMatched, th)   :265-373                     ygzf_search_by_projection_sim3
 //   ORBmatcher::SearchBySim3(pKF1, pKF2, vpMatches12, s12, R12, t12, th) :1006-1216                  ygzf_search_by_sim3
-// and ygz::SearchAndFuseBatch, the loop of LoopClosing::SearchAndFuse as one batch (ORBmatcherLoop.h).  The candidate searches run on the
-// device; everything that reads or writes the map runs here in the reference's order (LoopApply.h says why that is exact); the Scw / Sim3
-// algebra stays on the host (ORBmatcherLoop.h).
-// Kept apart from ORBmatcher.cc, like ORBmatcherFuse.cc: inside the reference tree this file supplies these three strong members beside the
+// and ygz::SearchAndFuseBatch / ygz::SearchByBoWBatch, the loops of LoopClosing::SearchAndFuse and LoopClosing::ComputeSim3 as one batch each
+// (ORBmatcherLoop.h).  The candidate searches run on the device; everything that reads or writes the map runs here in the reference's order
+// (LoopApply.h says why that is exact); the Scw / Sim3 algebra and the FeatureVector merge-join stay on the host (ORBmatcherLoop.h).
+// Kept apart from ORBmatcher.cc, like ORBmatcherFuse.cc: inside the reference tree this file supplies these four strong members beside the
 // weakened ORBmatcher.o (link recipe), while ORBmatcher.cc keeps the member set the boundary build pins.
-// SearchByBoW(KeyFrame*, KeyFrame*, ..) is not a projection search and keeps its reference body.
 #include "ORBextractor.h"   // first: inside the reference tree this is the replacement header (same include guard)
 #include "ORBmatcher.h"
 #include "ygz_compat.h"
@@ -71,7 +71,103 @@ int search_and_fuse(const std::vector<KeyFrame *> &kfs, const std::vector<Pose> 
     for (int k : r.nFused) n += k;
     return n;
 }
+
+// SearchByBoW(pKF1, pKF2) for one pKF1 against `cands` as one ygzf_search_by_bow_kf call: per candidate the FeatureVector merge-join of
+// src/ORBmatcher.cc:507-575 (equal node ids, lower_bound on a miss) and the "MapPoint exists and is not bad" masks of :512-516 / :527-533 run
+// here; the per-node brute force, the vbMatched2 chain and the rotation histogram run on the device.  out[k] comes back with one slot per
+// KF1 key, all NULL on failure (reported, returns false).
+bool search_by_bow_kf(KeyFrame *pKF1, const std::vector<KeyFrame *> &cands, float nnratio, bool checkOri, std::vector<std::vector<MapPoint *>> &out,
+                      std::vector<int> &nm, const char *who) {
+    const std::vector<MapPoint *> vpMapPoints1 = pKF1->GetMapPointMatches();   // one snapshot for the batch
+    const size_t K = cands.size(), N1 = vpMapPoints1.size();
+    out.assign(K, std::vector<MapPoint *>(N1, static_cast<MapPoint *>(nullptr)));
+    nm.assign(K, 0);
+    if (K == 0 || N1 == 0) return true;
+    if ((int) N1 != pKF1->N) {
+        ygzf_host::report_failure(who, "GetMapPointMatches does not have one slot per key");
+        return false;
+    }
+    std::vector<uint8_t> valid1(N1), hold1;
+    for (size_t i = 0; i < N1; i++) valid1[i] = vpMapPoints1[i] && !vpMapPoints1[i]->isBad();
+    struct Side {
+        std::vector<MapPoint *> mps;
+        std::vector<uint8_t> valid, hold;
+        std::vector<int> off1, idx1, off2, idx2;
+    };
+    std::vector<Side> side(K);
+    std::vector<ygzf_bow_kf_candidate> q(K);
+    const DBoW2::FeatureVector &vFeatVec1 = pKF1->mFeatVec;
+    for (size_t k = 0; k < K; k++) {
+        KeyFrame *pKF2 = cands[k];
+        Side &S = side[k];
+        S.mps = pKF2->GetMapPointMatches();
+        const size_t N2 = S.mps.size();
+        if ((int) N2 != pKF2->N) {
+            ygzf_host::report_failure(who, "GetMapPointMatches does not have one slot per key");
+            return false;
+        }
+        S.valid.resize(N2);
+        for (size_t i = 0; i < N2; i++) S.valid[i] = S.mps[i] && !S.mps[i]->isBad();
+        const DBoW2::FeatureVector &vFeatVec2 = pKF2->mFeatVec;
+        S.off1.push_back(0);
+        S.off2.push_back(0);
+        DBoW2::FeatureVector::const_iterator f1it = vFeatVec1.begin(), f2it = vFeatVec2.begin();
+        const DBoW2::FeatureVector::const_iterator f1end = vFeatVec1.end(), f2end = vFeatVec2.end();
+        while (f1it != f1end && f2it != f2end) {
+            if (f1it->first == f2it->first) {
+                S.idx1.insert(S.idx1.end(), f1it->second.begin(), f1it->second.end());
+                S.idx2.insert(S.idx2.end(), f2it->second.begin(), f2it->second.end());
+                S.off1.push_back((int) S.idx1.size());
+                S.off2.push_back((int) S.idx2.size());
+                f1it++;
+                f2it++;
+            } else if (f1it->first < f2it->first) {
+                f1it = vFeatVec1.lower_bound(f2it->first);
+            } else {
+                f2it = vFeatVec2.lower_bound(f1it->first);
+            }
+        }
+        ygzf_bow_kf_candidate &Q = q[k];
+        Q.n = (int) N2;
+        Q.keys = (const ygzf_kp *) pKF2->mvKeys.data();
+        Q.desc = desc_rows(pKF2->mDescriptors, (int) N2, S.hold);
+        Q.valid = S.valid.data();
+        Q.n_nodes = (int) S.off1.size() - 1;
+        Q.off1 = S.off1.data(); Q.idx1 = S.idx1.data(); Q.off2 = S.off2.data(); Q.idx2 = S.idx2.data();
+    }
+    ygzf_host::Lease lease(ORBextractor::sDevice);
+    if (!lease) return false;
+    std::vector<int> match12(K * N1 + 1);
+    const int rc = ygzf_search_by_bow_kf(lease.get(), (int) N1, (const ygzf_kp *) pKF1->mvKeys.data(), desc_rows(pKF1->mDescriptors, (int) N1, hold1),
+                                         valid1.data(), (int) K, q.data(), nnratio, checkOri, match12.data(), nm.data());
+    if (rc != YGZF_OK) {
+        ygzf_host::report_failure(who, ygzf_last_error(lease.get()));
+        nm.assign(K, 0);
+        return false;
+    }
+    for (size_t k = 0; k < K; k++)
+        for (size_t i = 0; i < N1; i++)
+            if (match12[k * N1 + i] >= 0) out[k][i] = side[k].mps[match12[k * N1 + i]];   // :550
+    return true;
+}
 }  // namespace
+
+int SearchByBoWBatch(KeyFrame *pKF1, const std::vector<KeyFrame *> &candidates, float nnratio, bool checkOrientation,
+                     std::vector<std::vector<MapPoint *>> &vvpMatches12, std::vector<int> &nmatches) {
+    search_by_bow_kf(pKF1, candidates, nnratio, checkOrientation, vvpMatches12, nmatches, "ygz::SearchByBoWBatch");
+    int enough = 0;
+    for (int n : nmatches) enough += n >= 20;   // src/LoopClosing.cc:251
+    return enough;
+}
+
+// src/ORBmatcher.cc:480-595: a batch of one
+int ORBmatcher::SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches12) {
+    std::vector<std::vector<MapPoint *>> out;
+    std::vector<int> nm;
+    search_by_bow_kf(pKF1, std::vector<KeyFrame *>{pKF2}, mfNNratio, mbCheckOrientation, out, nm, "ygz::ORBmatcher::SearchByBoW(KF, KF)");
+    vpMatches12.swap(out[0]);
+    return nm[0];
+}
 
 int SearchAndFuseBatch(const std::vector<std::pair<KeyFrame *, cv::Mat>> &poses, const std::vector<MapPoint *> &loopPoints, float th) {
     std::vector<KeyFrame *> kfs;

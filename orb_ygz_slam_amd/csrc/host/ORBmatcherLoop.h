@@ -1,4 +1,5 @@
 // ORBmatcherLoop.h -- the loop-closing side of ygz::ORBmatcher over the device (host/ORBmatcherLoop.cc):
+//   ygz::SearchByBoWBatch: the SearchByBoW(mpCurrentKF, pKF, ..) loop of LoopClosing::ComputeSim3 as one device batch (declared below).
 //   ygz::SearchAndFuseBatch: the loop of LoopClosing::SearchAndFuse (src/LoopClosing.cc:549-568) -- per corrected keyframe
 //   Fuse(pKF, Scw, loopPoints, th, vpReplace), then vpReplace[i]->Replace(loopPoints[i]) -- as one device batch with the same final graph
 //   (host/LoopApply.h says why).  `poses` in the order the reference iterates CorrectedPosesMap (std::map order).  Returns the summed nFused of
@@ -23,6 +24,15 @@ int SearchAndFuseBatch(const std::vector<std::pair<KeyFrame *, cv::Mat>> &poses,
 // row = keyframe) of every pair with skip[k * P + i] == 0, before any map update.  false: device failure (reported).
 bool SearchAndFuseCandidates(const std::vector<std::pair<KeyFrame *, cv::Mat>> &poses, const std::vector<MapPoint *> &points,
                              const std::vector<uint8_t> &skip, float th, std::vector<int> &bestIdx, std::vector<int> &bestDist);
+
+// The loop of LoopClosing::ComputeSim3 (src/LoopClosing.cc:238-261) -- per consistent candidate ORBmatcher(nnratio, checkOrientation)
+// .SearchByBoW(mpCurrentKF, pKF, vvpMapPointMatches[i]) -- as one device call.  Callers pass live candidates only (the reference discards
+// pKF->isBad() before the search, :244-247).  pKF1's GetMapPointMatches() snapshot is taken ONCE for the batch (the sequential loop takes it
+// again per candidate); every candidate's own snapshot is taken once, as in the member.  vvpMatches12[k] / nmatches[k]: vpMatches12 and the
+// return value of the k-th call.  Returns the number of candidates with nmatches >= 20 (:251).  A device failure goes through
+// ygzf_host::report_failure: every vvpMatches12[k] is all NULL, every nmatches[k] is 0.
+int SearchByBoWBatch(KeyFrame *pKF1, const std::vector<KeyFrame *> &candidates, float nnratio, bool checkOrientation,
+                     std::vector<std::vector<MapPoint *>> &vvpMatches12, std::vector<int> &nmatches);
 
 namespace loop {
 // Scw (4 x 4, CV_32F) -> Rcw (row-major), tcw, Ow

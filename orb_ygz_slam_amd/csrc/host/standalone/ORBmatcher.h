@@ -1,8 +1,8 @@
 // standalone/ORBmatcher.h -- ygz::ORBmatcher's public interface (reference include/ORBmatcher.h:38-149) for builds WITHOUT the reference
 // tree (this repository's tests: no OpenCV / Eigen installed).  Inside the reference tree this file is not used: ORBmatcher.cc is compiled
 // against the reference's own, unchanged include/ORBmatcher.h (found first on the include path) and defines the members listed under
-// "hot path" below; of the remaining members the two Fuse overloads, SearchBySim3 and SearchByProjection(KF, Scw, ...) have device forms in
-// ORBmatcherFuse.cc / ORBmatcherLoop.cc and SearchByBoW(KF, KF, ...) keeps its reference body (INTEGRATION.md shows the link recipe).
+// "hot path" below; the remaining members -- the two Fuse overloads, SearchBySim3, SearchByProjection(KF, Scw, ...) and
+// SearchByBoW(KF, KF, ...) -- have device forms in ORBmatcherFuse.cc / ORBmatcherLoop.cc (INTEGRATION.md shows the link recipe).
 #ifndef ORBMATCHER_H
 #define ORBMATCHER_H
 #include <set>
@@ -39,7 +39,7 @@ public:
     bool FindDirectProjection(KeyFrame *ref, Frame *curr, MapPoint *mp, Vector2f &px_curr, int &search_level);
 
     // ---- outside the hot path (LocalMapping / LoopClosing threads): device forms in host/ORBmatcherFuse.cc (the first Fuse) and
-    //      host/ORBmatcherLoop.cc (the three projection searches of LoopClosing); SearchByBoW(KF, KF, ...) stays the reference's body --------
+    //      host/ORBmatcherLoop.cc (the three projection searches and the SearchByBoW(KF, KF, ...) of LoopClosing) ------------------------------
     int SearchByProjection(KeyFrame *pKF, cv::Mat Scw, const std::vector<MapPoint *> &vpPoints, std::vector<MapPoint *> &vpMatched, int th);
     int SearchByBoW(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches12);
     int SearchBySim3(KeyFrame *pKF1, KeyFrame *pKF2, std::vector<MapPoint *> &vpMatches12, const float &s12, const cv::Mat &R12, const cv::Mat &t12,

@@ -206,6 +206,28 @@ void launch_bow(hipStream_t st, int nNodes, const int *kfOff, const int *kfIdx, 
                 const ygzf_kp *kfKeys, const uint8_t *kfDesc, int nF, const ygzf_kp *fKeys, const uint8_t *fDesc, float nnratio, int checkOri, int *match,
                 unsigned char *binOf, int *hist, int *nmatches);
 
+// SearchByBoW(KeyFrame, KeyFrame) for one KF1 against nCand candidates (match_kernels.hip: k_bow_kf_nodes, k_bow_kf_finish).  Every array lives
+// in one device block; a candidate's arrays are byte offsets from `base`.  match12 (nCand x n1 ints) pre-set to -1; tail (kBowKfTail ints per
+// candidate: [0] nmatches, [4 .. 34) the rotation histogram) to 0; binOf (nCand x n1 bytes) is scratch.
+constexpr int kBowKfTail = 64;
+struct BowKfCand {
+    long long keys2, desc2, valid2, off1, idx1, off2, idx2;
+};
+struct BowKfArgs {
+    int nCand, nItems, n1;          // nItems = itemBase[nCand]: one wave per (candidate, joined node)
+    const uint8_t *base;
+    const BowKfCand *cands;
+    const int *itemBase;            // nCand + 1 entries: prefix of the candidates' node counts
+    const ygzf_kp *keys1;
+    const uint8_t *desc1, *valid1;
+    float nnratio;
+    int checkOri;
+    int *match12;
+    unsigned char *binOf;
+    int *tail;
+};
+void launch_bow_kf(hipStream_t st, const BowKfArgs &A);
+
 // SearchForTriangulation per-node brute force with the epipolar tests (match_kernels.hip); match12 (n1 ints) pre-set to -1, hist (30 ints) and
 // nmatches to 0
 struct TriArgs {

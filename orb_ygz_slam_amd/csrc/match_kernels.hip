@@ -1410,9 +1410,9 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int nNodes, const int *__rest
     if (lane == 0 && count) atomicAdd(nmatches, count);
 }
 
-__global__ __launch_bounds__(256) void k_bow_finish(int nF, int checkOri, int *__restrict__ match, const unsigned char *__restrict__ binOf,
-                                                    const int *__restrict__ hist, int *__restrict__ nmatches) {
-    if (!checkOri) return;
+// ComputeThreeMaxima + the cull of one match array by one workgroup (k_bow_finish: the launch's only one; k_bow_kf_finish: one per candidate)
+__device__ __forceinline__ void bow_finish(int nF, int *__restrict__ match, const unsigned char *__restrict__ binOf, const int *__restrict__ hist,
+                                           int *__restrict__ nmatches) {
     __shared__ int s_removed;
     if (threadIdx.x == 0) s_removed = 0;
     __syncthreads();
@@ -1437,6 +1437,12 @@ __global__ __launch_bounds__(256) void k_bow_finish(int nF, int checkOri, int *_
     if (threadIdx.x == 0) *nmatches -= s_removed;
 }
 
+__global__ __launch_bounds__(256) void k_bow_finish(int nF, int checkOri, int *__restrict__ match, const unsigned char *__restrict__ binOf,
+                                                    const int *__restrict__ hist, int *__restrict__ nmatches) {
+    if (!checkOri) return;
+    bow_finish(nF, match, binOf, hist, nmatches);
+}
+
 void launch_bow(hipStream_t st, int nNodes, const int *kfOff, const int *kfIdx, const int *fOff, const int *fIdx, const uint8_t *kfValid,
                 const ygzf_kp *kfKeys, const uint8_t *kfDesc, int nF, const ygzf_kp *fKeys, const uint8_t *fDesc, float nnratio, int checkOri, int *match,
                 unsigned char *binOf, int *hist, int *nmatches) {
@@ -1447,7 +1453,108 @@ void launch_bow(hipStream_t st, int nNodes, const int *kfOff, const int *kfIdx, 
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// ORBmatcher::SearchForTriangulation  src/ORBmatcher.cc:596-741 with CheckDistEpipolarLine :136-153 (LocalMapping::CreateNewMapPoints).
+// ORBmatcher::SearchByBoW(KeyFrame*, KeyFrame*, vector<MapPoint*>&)  src/ORBmatcher.cc:480-595 for one KF1 against K candidates
+// (LoopClosing::ComputeSim3, src/LoopClosing.cc:238-261).  Not k_bow_nodes with the sides swapped: the gate is bestDist1 < TH_LOW (:548,
+// strict), a KF2 feature without a good MapPoint is never a candidate (:527-533: neither best nor second best), the "already matched" state
+// is vbMatched2 (:529, :551; the rotation cull does not clear it) and the result is indexed by the KF1 feature.
+// One wave per (candidate, joined node), items of all candidates flattened (itemBase: prefix of the candidates' node counts).  The wave
+// walks the node's KF1 features in list order (vbMatched2 chains them), its lanes spread over the node's KF2 list in rounds of 64.  A lane
+// keeps its round-0 KF2 descriptor and validity in registers across the walk: nodes of <= 64 KF2 features (the usual case) read KF2 once.
+// ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_bow_kf_nodes(BowKfArgs A) {
+    const int lane = m_lane();
+    const int item = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (item >= A.nItems) return;
+    int lo = 0, hi = A.nCand;       // itemBase[lo] <= item < itemBase[hi]
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (A.itemBase[mid] <= item) lo = mid;
+        else hi = mid;
+    }
+    const BowKfCand C = A.cands[lo];
+    const int node = item - A.itemBase[lo];
+    const int *off1 = (const int *) (A.base + C.off1), *idx1 = (const int *) (A.base + C.idx1);
+    const int *off2 = (const int *) (A.base + C.off2), *idx2 = (const int *) (A.base + C.idx2);
+    const uint8_t *desc2 = A.base + C.desc2, *valid2 = A.base + C.valid2;
+    const ygzf_kp *keys2 = (const ygzf_kp *) (A.base + C.keys2);
+    int *match12 = A.match12 + (size_t) lo * A.n1;
+    unsigned char *binOf = A.binOf + (size_t) lo * A.n1;
+    int *tail = A.tail + (size_t) lo * kBowKfTail;
+    const int f0 = off2[node], nF = off2[node + 1] - f0;
+    const int rounds = (nF + 63) >> 6;
+    if (rounds > 64) return;        // (the entry point refuses such a node)
+    const float factor = 1.0f / HISTO_LENGTH;
+    const int TH_LOW = 50;
+    unsigned long long taken = 0;   // bit r: this lane's KF2 feature of round r (position r * 64 + lane) is in vbMatched2
+    unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
+    bool ok0 = false;               // round 0 held in registers
+    if (lane < nF) {
+        const int i2 = idx2[f0 + lane];
+        ok0 = valid2[i2] != 0;
+        if (ok0) {
+            const unsigned long long *d = (const unsigned long long *) (desc2 + (size_t) i2 * 32);
+            c0 = d[0]; c1 = d[1]; c2 = d[2]; c3 = d[3];
+        }
+    }
+    int count = 0;
+    for (int a = off1[node]; a < off1[node + 1]; a++) {
+        const int i1 = idx1[a];
+        if (!A.valid1[i1]) continue;                               // :512-516
+        const unsigned long long *qd = (const unsigned long long *) (A.desc1 + (size_t) i1 * 32);
+        const unsigned long long q0 = qd[0], q1 = qd[1], q2 = qd[2], q3 = qd[3];
+        unsigned best = (256u << 16) | 0xFFFFu, best2 = (256u << 16) | 0xFFFFu;
+        if (ok0 && !(taken & 1ull)) best = ((unsigned) (__popcll(q0 ^ c0) + __popcll(q1 ^ c1) + __popcll(q2 ^ c2) + __popcll(q3 ^ c3)) << 16) | (unsigned) lane;
+        for (int r = 1; r < rounds; r++) {
+            const int b = r * 64 + lane;
+            if (b >= nF || ((taken >> r) & 1ull)) continue;
+            const int i2 = idx2[f0 + b];
+            if (!valid2[i2]) continue;                             // :529-533
+            const unsigned long long *d = (const unsigned long long *) (desc2 + (size_t) i2 * 32);
+            const unsigned dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+            const unsigned key = (dist << 16) | (unsigned) b;
+            if (key < best) { best2 = best; best = key; }
+            else if (key < best2) best2 = key;
+        }
+        const unsigned wbest = wave_min_dpp(best);
+        const unsigned long long who = __ballot(best == wbest);
+        const int src = __ffsll((long long) who) - 1;
+        const unsigned second = wave_min_dpp(lane == src ? best2 : min(best, best2));
+        const int bestDist1 = (int) (wbest >> 16), bestDist2 = (int) (second >> 16);
+        if (!(bestDist1 < TH_LOW)) continue;                       // :548
+        if (!((float) bestDist1 < A.nnratio * (float) bestDist2)) continue;
+        const int b = (int) (wbest & 0xFFFFu);
+        if (lane == (b & 63)) taken |= 1ull << (b >> 6);           // vbMatched2[bestIdx2] = true  (:551)
+        if (lane == 0) {
+            const int i2 = idx2[f0 + b];
+            match12[i1] = i2;
+            if (A.checkOri) {
+                float rot = A.keys1[i1].angle - keys2[i2].angle;   // :554-559
+                if (rot < 0.0) rot += 360.0f;
+                int bin = (int) roundf(rot * factor);
+                if (bin == HISTO_LENGTH) bin = 0;
+                binOf[i1] = (unsigned char) bin;
+                atomicAdd(&tail[4 + bin], 1);
+            }
+        }
+        count++;
+    }
+    if (lane == 0 && count) atomicAdd(&tail[0], count);
+}
+
+__global__ __launch_bounds__(256) void k_bow_kf_finish(BowKfArgs A) {
+    if (!A.checkOri) return;
+    const size_t c = blockIdx.x;
+    int *tail = A.tail + c * kBowKfTail;
+    bow_finish(A.n1, A.match12 + c * A.n1, A.binOf + c * A.n1, tail + 4, tail);
+}
+
+void launch_bow_kf(hipStream_t st, const BowKfArgs &A) {
+    if (A.nItems > 0) hipLaunchKernelGGL(k_bow_kf_nodes, dim3((A.nItems + 3) / 4), dim3(256), 0, st, A);
+    if (A.nItems > 0 && A.checkOri) hipLaunchKernelGGL(k_bow_kf_finish, dim3(A.nCand), dim3(256), 0, st, A);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// ORBmatcher::SearchForTriangulation src/ORBmatcher.cc:596-741 with CheckDistEpipolarLine :136-153 (LocalMapping::CreateNewMapPoints).
 // The reference never sets vbMatched2 (:616 declares it, nothing writes it), so every KF1 feature is an independent problem: of the KF2
 // features of its vocabulary node that carry no MapPoint, pass the stereo filter, lie within TH_LOW, outside the epipole's exclusion disc
 // (both keypoints monocular, :668-673) and close enough to the epipolar line, it takes the least distance, the LAST of equals (the scan's

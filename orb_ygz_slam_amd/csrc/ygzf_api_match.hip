@@ -558,6 +558,85 @@ int ygzf_search_by_bow(ygzf_ctx *c, int n_nodes, const int *kf_off, const int *k
     return YGZF_OK;
 }
 
+// SearchByBoW(KF1, KF2) over n_cand KF2s (include/ygzf.h; match_kernels.hip: k_bow_kf_nodes).  Validation first; one packed copy in (KF1's
+// arrays once, every candidate's arrays, the candidate table, the item prefix), one out.  Nothing in c->held is touched: only the packed staging
+// area is written.
+int ygzf_search_by_bow_kf(ygzf_ctx *c, int n1, const ygzf_kp *keys1, const uint8_t *desc1, const uint8_t *valid1, int n_cand,
+                          const ygzf_bow_kf_candidate *cands, float nnratio, int check_orientation, int *match12, int *nmatches) {
+    if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
+    if (n1 < 0 || n_cand < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
+    if (n_cand > 0 && (!nmatches || !cands || (n1 > 0 && !match12))) return fail(c, YGZF_ERR_INVALID, "null argument");
+    const size_t K = (size_t) n_cand, N1 = (size_t) n1;
+    for (size_t k = 0; k < K; k++) nmatches[k] = 0;
+    for (size_t i = 0; i < K * N1; i++) match12[i] = -1;   // vpMatches12 = vector<MapPoint*>(vpMapPoints1.size(), NULL)  (:491)
+    if (n_cand == 0 || n1 == 0) return YGZF_OK;
+    if (!keys1 || !desc1 || !valid1) return fail(c, YGZF_ERR_INVALID, "null array");
+    std::vector<int> itemBase(K + 1, 0);
+    for (int k = 0; k < n_cand; k++) {
+        const ygzf_bow_kf_candidate &Q = cands[k];
+        if (Q.n < 0 || Q.n_nodes < 0) return fail(c, YGZF_ERR_INVALID, "candidate %d: negative count", k);
+        const bool empty = Q.n == 0 || Q.n_nodes == 0;
+        itemBase[k + 1] = itemBase[k] + (empty ? 0 : Q.n_nodes);
+        if (empty) continue;
+        if (!Q.keys || !Q.desc || !Q.valid || !Q.off1 || !Q.idx1 || !Q.off2 || !Q.idx2) return fail(c, YGZF_ERR_INVALID, "candidate %d: null array", k);
+        if (Q.off1[0] < 0 || Q.off2[0] < 0) return fail(c, YGZF_ERR_INVALID, "candidate %d: node offsets not ascending", k);
+        for (int j = 0; j < Q.n_nodes; j++) {
+            if (Q.off1[j] > Q.off1[j + 1] || Q.off2[j] > Q.off2[j + 1]) return fail(c, YGZF_ERR_INVALID, "candidate %d: node offsets not ascending", k);
+            if (Q.off2[j + 1] - Q.off2[j] > 4096)
+                return fail(c, YGZF_ERR_UNSUPPORTED, "candidate %d: more than 4096 features of the second KeyFrame in one vocabulary node", k);
+        }
+        for (int i = Q.off1[0]; i < Q.off1[Q.n_nodes]; i++)
+            if (Q.idx1[i] < 0 || Q.idx1[i] >= n1) return fail(c, YGZF_ERR_INVALID, "candidate %d: feature index of the first KeyFrame out of range", k);
+        for (int i = Q.off2[0]; i < Q.off2[Q.n_nodes]; i++)
+            if (Q.idx2[i] < 0 || Q.idx2[i] >= Q.n) return fail(c, YGZF_ERR_INVALID, "candidate %d: feature index of the second KeyFrame out of range", k);
+    }
+    if (itemBase[K] == 0) return YGZF_OK;
+    HIPCHECK(c, hipSetDevice(c->device));
+    int rc;
+    PackedTransfer P(c);
+    const size_t iK1 = P.add_in(keys1, sizeof(ygzf_kp) * N1), iD1 = P.add_in(desc1, 32 * N1), iV1 = P.add_in(valid1, N1);
+    std::vector<BowKfCand> recs(K);
+    memset(recs.data(), 0, sizeof(BowKfCand) * K);
+    for (size_t k = 0; k < K; k++) {
+        const ygzf_bow_kf_candidate &Q = cands[k];
+        if (itemBase[k + 1] == itemBase[k]) continue;
+        const size_t n = (size_t) Q.n, nn = (size_t) Q.n_nodes + 1;
+        BowKfCand &R = recs[k];
+        R.keys2 = (long long) P.add_in(Q.keys, sizeof(ygzf_kp) * n);
+        R.desc2 = (long long) P.add_in(Q.desc, 32 * n);
+        R.valid2 = (long long) P.add_in(Q.valid, n);
+        R.off1 = (long long) P.add_in(Q.off1, 4 * nn);
+        R.idx1 = (long long) P.add_in(Q.idx1, 4 * (size_t) Q.off1[Q.n_nodes]);
+        R.off2 = (long long) P.add_in(Q.off2, 4 * nn);
+        R.idx2 = (long long) P.add_in(Q.idx2, 4 * (size_t) Q.off2[Q.n_nodes]);
+    }
+    const size_t iR = P.add_in(recs.data(), sizeof(BowKfCand) * K), iB = P.add_in(itemBase.data(), 4 * (K + 1));
+    std::vector<int> tail(K * kBowKfTail);
+    const size_t oM = P.add_out(match12, 4 * K * N1), oT = P.add_out(tail.data(), 4 * tail.size()), oB = P.add_out(nullptr, K * N1);   // (binOf: scratch)
+    uint8_t *d;
+    if ((rc = P.upload(&d))) return rc;
+    HIPCHECK(c, hipMemsetAsync(P.d_out(oM), 0xFF, 4 * K * N1, c->stream));
+    HIPCHECK(c, hipMemsetAsync(P.d_out(oT), 0, 4 * tail.size(), c->stream));
+    BowKfArgs A;
+    A.nCand = n_cand; A.nItems = itemBase[K]; A.n1 = n1;
+    A.base = d;
+    A.cands = (const BowKfCand *) (d + iR);
+    A.itemBase = (const int *) (d + iB);
+    A.keys1 = (const ygzf_kp *) (d + iK1); A.desc1 = d + iD1; A.valid1 = d + iV1;
+    A.nnratio = nnratio; A.checkOri = check_orientation != 0;
+    A.match12 = (int *) P.d_out(oM);
+    A.binOf = (unsigned char *) P.d_out(oB);
+    A.tail = (int *) P.d_out(oT);
+    {
+        ProfScope ps(c, KK_BOWKF);
+        launch_bow_kf(c->stream, A);
+    }
+    HIPCHECK(c, hipGetLastError());
+    if ((rc = P.download())) return rc;
+    for (size_t k = 0; k < K; k++) nmatches[k] = tail[k * kBowKfTail];
+    return YGZF_OK;
+}
+
 int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, const int *idx1, const int *off2, const int *idx2,
                                   const ygzf_frame_view *kf1, const uint8_t *has_mp1, const ygzf_frame_view *kf2, const uint8_t *has_mp2,
                                   const float *level_sigma2_2, const float *F12, const float *Cw1, const float *R2w, const float *t2w,

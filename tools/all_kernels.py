@@ -93,6 +93,9 @@ def main():
             ki.extend(np.nonzero(na == node)[0]); fi.extend(np.nonzero(nb == node)[0])
             ko.append(len(ki)); fo.append(len(fi))
         ex.search_by_bow(ko, ki, fo, fi, np.ones(len(ka), np.uint8), ka, da, kb, db, 0.7, True)
+        # SearchByBoW(KeyFrame, KeyFrame) for three candidates on the same node list (LoopClosing::ComputeSim3): k_bow_kf_nodes
+        kf2 = dict(keys=kb, desc=db, valid=np.ones(len(kb), np.uint8), off1=ko, idx1=ki, off2=fo, idx2=fi)
+        ex.search_by_bow_kf(dict(keys=ka, desc=da, valid=np.ones(len(ka), np.uint8)), [kf2] * 3, 0.75, True)
         # SearchForTriangulation on the same node list (LocalMapping::CreateNewMapPoints): k_tri_nodes
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
         from tests.tri_cases import geometry
