@@ -660,46 +660,40 @@ __device__ __forceinline__ int fast9_test(const uint8_t *c, int tp, int t) {
 
 // cv::FAST cornerScore<16> for a pixel known to be a corner of polarity `pol`: max over the 16 arcs of 9 of the minimum
 // margin, minus 1 (== the largest threshold for which the pixel is still a corner).  Signed margins e[k] = +-(ring_k - centre)
-// live as 16-bit pairs (e[k] | e[k+8] << 16), so every packed min serves two arcs; "k+8" neighbours are the swapped halves.
-__device__ __forceinline__ unsigned pk_min16(unsigned a, unsigned b) {
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(v2s, a), __builtin_bit_cast(v2s, b)));
-}
-__device__ __forceinline__ unsigned pk_max16(unsigned a, unsigned b) {
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(v2s, a), __builtin_bit_cast(v2s, b)));
-}
-__device__ __forceinline__ unsigned pk_mul16(unsigned a, unsigned b) {
-    return __builtin_bit_cast(unsigned, __builtin_bit_cast(v2s, a) * __builtin_bit_cast(v2s, b));
-}
-__device__ __forceinline__ unsigned swap16(unsigned a) {   // a half swap feeding a packed min/max folds into its op_sel bits
-    const v2s x = __builtin_bit_cast(v2s, a);
-    return __builtin_bit_cast(unsigned, __builtin_shufflevector(x, x, 1, 0));
-}
+// live as f16 pairs (e[k] | e[k+8] << 16), so every packed operation serves two arcs; "k+8" neighbours are the swapped halves, which
+// fold into the instruction's op_sel bits.  A byte b becomes the f16 number 1024 + b by OR-ing 0x6400 into its half (a normal number:
+// nothing depends on the denormal mode); a margin is ONE v_pk_add_f16 of (+-ring) and (-+centre) -- the polarity is the sign bit OR-ed into
+// the ring pair and flipped in the centre pair, the sum is never negated, so no -0 appears.  Margins are integers in [-255, 255] and
+// minimum / maximum are exact, so the result is the integer the 16-bit integer form gave.  gfx950's three-input v_pk_minimum3_f16 /
+// v_pk_maximum3_f16 make "min over an arc of 9" two stages (arcs of 3, then three arcs of 3) and "max over 16 arcs" four instructions:
+// about 54 vector instructions per call instead of about 69 (issue rates: profiles/micro/r07_valu_issue_rates_f16.txt).
+typedef _Float16 v2h __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v2h swap_h(v2h x) { return __builtin_shufflevector(x, x, 1, 0); }
+__device__ __forceinline__ v2h pk_min3h(v2h a, v2h b, v2h c) { return __builtin_elementwise_minimum(__builtin_elementwise_minimum(a, b), c); }
+__device__ __forceinline__ v2h pk_max3h(v2h a, v2h b, v2h c) { return __builtin_elementwise_maximum(__builtin_elementwise_maximum(a, b), c); }
 __device__ __forceinline__ int fast9_arc_score(const uint8_t *c, int tp, int pol) {
     const int t2 = 2 * tp, t3 = 3 * tp;
-    const unsigned vv = (unsigned) c[0] * 0x10001u;
-    const unsigned sg = pol == 2 ? 0xFFFFFFFFu : 0x00010001u;   // -1 / +1 in both halves
-    unsigned P[8];
-#define MARGIN_PAIR(k, a, b) P[k] = pk_mul16(pk_sub16((unsigned) c[a] | ((unsigned) c[b] << 16), vv), sg);
+    const unsigned sgn = pol == 2 ? 0x80008000u : 0u;            // dark corner: centre - ring
+    const unsigned ringK = 0x64006400u | sgn;
+    const v2h vv = __builtin_bit_cast(v2h, (((unsigned) c[0] * 0x10001u) | 0x64006400u) ^ sgn ^ 0x80008000u);
+    v2h P[8];
+#define MARGIN_PAIR(k, a, b) P[k] = __builtin_bit_cast(v2h, (unsigned) c[a] | ((unsigned) c[b] << 16) | ringK) + vv;
     MARGIN_PAIR(0, t3, -t3) MARGIN_PAIR(1, t3 + 1, -t3 - 1) MARGIN_PAIR(2, t2 + 2, -t2 - 2) MARGIN_PAIR(3, tp + 3, -tp - 3)
     MARGIN_PAIR(4, 3, -3) MARGIN_PAIR(5, -tp + 3, tp - 3) MARGIN_PAIR(6, -t2 + 2, t2 - 2) MARGIN_PAIR(7, -t3 + 1, t3 - 1)
 #undef MARGIN_PAIR
-    unsigned M2[8], M4[8], M8[8];
+    v2h M3[8], M9[8];
 #pragma unroll
-    for (int k = 0; k < 7; k++) M2[k] = pk_min16(P[k], P[k + 1]);                 // (m2[k], m2[k+8])
-    M2[7] = pk_min16(P[7], swap16(P[0]));
+    for (int k = 0; k < 8; k++)   // (m3[k], m3[k+8]): minimum of ring k, k+1, k+2
+        M3[k] = pk_min3h(P[k], k + 1 < 8 ? P[k + 1] : swap_h(P[k - 7]), k + 2 < 8 ? P[k + 2] : swap_h(P[k - 6]));
 #pragma unroll
-    for (int k = 0; k < 6; k++) M4[k] = pk_min16(M2[k], M2[k + 2]);
-    M4[6] = pk_min16(M2[6], swap16(M2[0]));
-    M4[7] = pk_min16(M2[7], swap16(M2[1]));
-#pragma unroll
-    for (int k = 0; k < 4; k++) M8[k] = pk_min16(M4[k], M4[k + 4]);
-#pragma unroll
-    for (int k = 4; k < 8; k++) M8[k] = pk_min16(M4[k], swap16(M4[k - 4]));
-    unsigned best = 0;   // margins of a corner's winning arc are positive; max(0, ...) as the scalar form's `a = 0` start
-#pragma unroll
-    for (int k = 0; k < 8; k++) best = pk_max16(best, pk_min16(M8[k], swap16(P[k])));   // min(m8[k], e[k+8]) | min(m8[k+8], e[k])
-    const int lo = (short) (best & 0xFFFFu), hi = (short) (best >> 16);
-    return max(lo, hi) - 1;
+    for (int k = 0; k < 8; k++)   // (m9[k], m9[k+8]): an arc of 9 is three arcs of 3
+        M9[k] = pk_min3h(M3[k], k + 3 < 8 ? M3[k + 3] : swap_h(M3[k - 5]), k + 6 < 8 ? M3[k + 6] : swap_h(M3[k - 2]));
+    // margins of a corner's winning arc are positive; max(+0, ...) as the scalar form's `a = 0` start
+    v2h best = pk_max3h(__builtin_bit_cast(v2h, 0u), M9[0], M9[1]);
+    best = pk_max3h(best, M9[2], M9[3]);
+    best = pk_max3h(best, M9[4], M9[5]);
+    best = pk_max3h(best, M9[6], M9[7]);
+    return (int) __builtin_elementwise_maximum(best.x, best.y) - 1;
 }
 
 // LDS pitch of a cell's score map = the window pitch (wCell + 2 columns used, the window pitch is >= wCell + 7)

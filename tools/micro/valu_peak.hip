@@ -74,6 +74,10 @@ constexpr int kIter = 2000, kUnroll = 8, kChains = 8;   // 2000 x 8 x 8 = 128000
 #define OP_SDWA(x) asm volatile("v_add_u32_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:BYTE_0 src1_sel:DWORD" : "+v"(x) : "v"(b));
 #define OP_DPPROR(x) asm volatile("v_mov_b32_dpp %0, %1 row_ror:4 row_mask:0xf bank_mask:0xf" : "+v"(x) : "v"(b));
 #define OP_BITOP2(x) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0xfe" : "+v"(x) : "v"(b), "v"(c));
+// gfx950's three-input packed f16 minimum / maximum and the packed f16 add with negated operand halves (fast9_arc_score is built from them)
+#define OP_PKMIN3H(x) asm volatile("v_pk_minimum3_f16 %0, %0, %1, %2 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "+v"(x) : "v"(b), "v"(c));
+#define OP_PKMAX3H(x) asm volatile("v_pk_maximum3_f16 %0, %0, %1, %2 op_sel:[0,1,0] op_sel_hi:[1,0,1]" : "+v"(x) : "v"(b), "v"(c));
+#define OP_PKADDH(x) asm volatile("v_pk_add_f16 %0, %0, %1 neg_lo:[0,1] neg_hi:[0,1]" : "+v"(x) : "v"(b));
 
 #define KERNEL(NAME, OP)                                                                                         \
     __global__ __launch_bounds__(256) void NAME(unsigned *out, long long *clk, unsigned seed) {                  \
@@ -112,6 +116,7 @@ KERNEL(k_min3, OP_MIN3) KERNEL(k_med3, OP_MED3) KERNEL(k_pkmax, OP_PKMAX) KERNEL
 KERNEL(k_pkmul, OP_PKMUL) KERNEL(k_mulf, OP_MULF) KERNEL(k_addf, OP_ADDF) KERNEL(k_cvtf, OP_CVTF) KERNEL(k_cvtub, OP_CVTUB)
 KERNEL(k_mulhi, OP_MULHI) KERNEL(k_xad, OP_XAD) KERNEL(k_sad16, OP_SAD16) KERNEL(k_addlshl, OP_ADDLSHL) KERNEL(k_not, OP_NOT)
 KERNEL(k_bcnt, OP_BCNT) KERNEL(k_sdwa, OP_SDWA) KERNEL(k_dppror, OP_DPPROR) KERNEL(k_bitop2, OP_BITOP2)
+KERNEL(k_pkmin3h, OP_PKMIN3H) KERNEL(k_pkmax3h, OP_PKMAX3H) KERNEL(k_pkaddh, OP_PKADDH)
 
 __global__ __launch_bounds__(256) void k_pkfma(unsigned *out, long long *clk, unsigned seed) {
     typedef float v2 __attribute__((ext_vector_type(2)));
@@ -195,6 +200,7 @@ int main(int argc, char **argv) {   // optional arguments: substrings of the ins
                                                    {"v_cvt_f32_ubyte0", k_cvtub}, {"v_mul_hi_u32", k_mulhi}, {"v_xad_u32", k_xad}, {"v_sad_u16", k_sad16},
                                                    {"v_add_lshl_u32", k_addlshl}, {"v_not_b32", k_not}, {"v_bcnt_u32_b32", k_bcnt}, {"v_add_u32_sdwa", k_sdwa},
                                                    {"v_mov_b32_dpp ror", k_dppror}, {"v_bitop3 (or3)", k_bitop2},
+                                                   {"v_pk_minimum3_f16", k_pkmin3h}, {"v_pk_maximum3_f16", k_pkmax3h}, {"v_pk_add_f16 neg", k_pkaddh},
                                                    {"v_mul_f64", k_mulf64}, {"v_add_f64", k_addf64}, {"v_fma_f64", k_fmaf64},
                                                    {"v_add + 1 s_add", k_add_s1}, {"v_add + 2 salu", k_add_s2}, {"v_lerp + 1 s_add", k_lerp_s1}};
     const double instr = (double) kIter * kUnroll * kChains;

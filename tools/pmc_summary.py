@@ -91,8 +91,33 @@ def copy_stats(out, tag, sub, name):
             csv.writer(f, quoting=csv.QUOTE_ALL).writerows(rows)
 
 
+def valu_mix(ins, sub, source):
+    """VALU mix: instructions per frame from the counters, mean issue cost per instruction from the ISA classification (tools/valu_mix.py).  A kernel
+    launched several times per sub-batch (seven resize levels, the octree's two launches) counts all of them: launches are taken relative to the FAST kernel's."""
+    cost = {}
+    cf = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "valu_issue_cost.json")
+    if os.path.exists(cf):
+        cost = json.load(open(cf))
+    batches = max([len(ins[k].get("SQ_INSTS_VALU", [])) for k in ins if k.startswith("k_fast_")] or [0])
+    mix = {}
+    for k in ins:
+        n = len(ins[k].get("SQ_INSTS_VALU", []))
+        v = mean(ins[k].get("SQ_INSTS_VALU", []))
+        if v > 0 and k in cost:
+            per_batch = n / batches if batches else (7 if k == "k_pyr_resize" else 1)
+            mix[k] = {"valu_insts_per_frame": round(v * per_batch / sub, 1), "cycles_per_inst": cost[k]["cycles_per_inst"],
+                      "valu_insts_per_launch": round(v, 1), "waves_per_launch": round(mean(ins[k].get("SQ_WAVES", [])), 1), "launches_per_sub_batch": round(per_batch, 2)}
+    return {"_source": "SQ_INSTS_VALU of %s / %d frames per launch; cycles_per_inst from profiles/valu_issue_cost.json "
+                       "(tools/valu_mix.py: ISA of the kernel classified with the issue rates of profiles/micro/r02_valu_issue_rates.txt)" % (source, sub),
+            "euroc752x480_8lvl_1000feat": mix}
+
+
 def main():
     out, tag = sys.argv[1], sys.argv[2]
+    if tag == "--valu-mix":          # <dir with a *counter_collection.csv of an SQ_INSTS_VALU SQ_WAVES pass> --valu-mix <source label>: only profiles/valu_mix.json
+        json.dump(valu_mix(counters(out), int(os.environ.get("YGZF_PROFILE_SUB_BATCH", "256")), sys.argv[3]),
+                  open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "valu_mix.json"), "w"), indent=1)
+        return
     sub = int(os.environ.get("YGZF_PROFILE_SUB_BATCH", "256"))
     copy_stats(out, tag, "stats", tag + "_kernel_stats.csv")
     copy_stats(out, tag, "all_stats", tag + "_all_kernel_stats.csv")
@@ -113,21 +138,7 @@ def main():
     json.dump({"_source": "profiles/%s_pmc_hbm.csv (rocprofv3 PMC, HBM bytes per launch of one 256-frame sub-batch), CORRECTED: FETCH_SIZE x 1024 x %.3f + "
                           "WRITE_SIZE x 1024 x %.3f (%s)" % (tag, ff, wf, src), "fetch_factor": ff, "write_factor": wf,
                "euroc752x480_8lvl_1000feat": traffic}, open(os.path.join(out, "traffic.json"), "w"), indent=1)
-    # VALU mix: instructions per frame from the counters, mean issue cost per instruction from the ISA classification (tools/valu_mix.py)
-    cost = {}
-    cf = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "profiles", "valu_issue_cost.json")
-    if os.path.exists(cf):
-        cost = json.load(open(cf))
-    mix = {}
-    for k in ins:
-        v = mean(ins[k].get("SQ_INSTS_VALU", []))
-        if v > 0 and k in cost:
-            per_frame = v / sub * (7 if k == "k_pyr_resize" else 1)      # 7 resize launches per frame
-            mix[k] = {"valu_insts_per_frame": round(per_frame, 1), "cycles_per_inst": cost[k]["cycles_per_inst"],
-                      "valu_insts_per_launch": round(v, 1), "waves_per_launch": round(mean(ins[k].get("SQ_WAVES", [])), 1)}
-    json.dump({"_source": "SQ_INSTS_VALU of profiles/%s_pmc_insts.csv / %d frames per launch; cycles_per_inst from profiles/valu_issue_cost.json "
-                          "(tools/valu_mix.py: ISA of the kernel classified with the issue rates of profiles/micro/r02_valu_issue_rates.txt)" % (tag, sub),
-               "euroc752x480_8lvl_1000feat": mix}, open(os.path.join(out, "valu_mix.json"), "w"), indent=1)
+    json.dump(valu_mix(ins, sub, "profiles/%s_pmc_insts.csv" % tag), open(os.path.join(out, "valu_mix.json"), "w"), indent=1)
     print(open(os.path.join(out, tag + "_pmc_hbm.csv")).read())
     print(open(os.path.join(out, tag + "_pmc_insts.csv")).read())
 
