@@ -668,6 +668,44 @@ int ygzf_profile_reset(ygzf_ctx *ctx);
 /* Raw hipStream_t of the context (as void*), for callers that record their own events. */
 void *ygzf_stream(ygzf_ctx *ctx);
 
+/* ---- KeyFrameDatabase: the stored BowVectors and the place-recognition query
+ *      src/KeyFrameDatabase.cc:36-64 (add / erase / clear), :67-284 (DetectLoopCandidates / DetectRelocalizationCandidates),
+ *      DBoW2 L1Scoring::score Thirdparty/DBoW2/DBoW2/ScoringObject.cpp:23-68, the minimum-score loop src/LoopClosing.cc:125-136 -----------------
+ * The context keeps every added BowVector in device memory, one row of (word id, value) pairs per keyframe in a slot; a query streams the
+ * whole store once and returns, per query vector and slot, what the reference's walk over its inverted file and its score() call produce:
+ *   common : words present in both vectors (= mnLoopWords / mnRelocWords as the walk counts them: a keyframe is listed once per word it holds)
+ *   first  : the smallest common word id, -1 without one (the reference meets keyframes in the order (first, order of add): :76-91, :187-200)
+ *   score  : L1Scoring::score(query, stored) as the double it returns (-0.0 without a common word); the sum runs over the common words
+ *            ascending from 0.0 as the reference's merge does, so the float the callers derive (`float si = ...`, :119, :228) is the same bits.
+ * Which keyframes are connected, the word gates, the covisibility accumulation and the candidate lists stay with the caller
+ * (csrc/host/KeyFrameDatabase.cc holds the reference's bookkeeping over these three arrays).
+ *   ygzf_kfdb_add   : key (the caller's name of the keyframe, e.g. its address) with n >= 0 pairs, ids strictly ascending as BowVector iterates
+ *       and at most 2^31 - 1 (`first` is an int) (otherwise YGZF_ERR_INVALID); *slot (nullable) receives the slot, the lowest free one.  A key that is live: YGZF_ERR_STATE, nothing changes.
+ *   ygzf_kfdb_erase : frees the key's slot; an unknown key is no error (erase of a keyframe that was never added walks nothing, :43-59).
+ *   ygzf_kfdb_clear : no keys, no slots; the memory is kept.
+ *   ygzf_kfdb_size  : live keys and slots in use (the highest slot ever handed out since the last clear, plus one).
+ *   ygzf_kfdb_capacity : entries ((id, value) pairs) the store's arena holds and entries appended so far (holes of erased rows included).  The
+ *       arena starts at YGZF_KFDB_INITIAL_ENTRIES.  An erased row leaves a hole.  When an add does not fit behind the last row the live rows are
+ *       repacked on the device into a fresh arena: of twice the size (doubling until it fits), or of the same size when the live rows and the
+ *       new one fill at most half of it -- so under erasures and adds the memory follows the live entries (within a factor of four plus the
+ *       initial size), not everything ever appended.  During a repack both arenas exist.  The arena never shrinks; ygzf_destroy frees it.
+ *   ygzf_kfdb_query : n_q query vectors (ids strictly ascending and at most 2^31 - 1, at most 8192 words each: YGZF_ERR_UNSUPPORTED beyond); common / first / score are
+ *       dense n_q x n_slots arrays (n_slots as ygzf_kfdb_size reports), free slots 0 / -1 / 0.0, preset to that before any error return.
+ *       n_q = 0 or an empty store: YGZF_OK.  One launch for all queries.
+ * The store has buffers of its own: none of these calls changes what the context holds of an extraction batch or its results. */
+#define YGZF_KFDB_INITIAL_ENTRIES 65536
+typedef struct ygzf_kfdb_query_vec {
+    int n;
+    const uint32_t *ids;
+    const double *vals;
+} ygzf_kfdb_query_vec;
+int ygzf_kfdb_add(ygzf_ctx *ctx, uint64_t key, int n, const uint32_t *ids, const double *vals, int *slot);
+int ygzf_kfdb_erase(ygzf_ctx *ctx, uint64_t key);
+int ygzf_kfdb_clear(ygzf_ctx *ctx);
+int ygzf_kfdb_size(ygzf_ctx *ctx, int *n_live, int *n_slots);
+int ygzf_kfdb_capacity(ygzf_ctx *ctx, size_t *entries, size_t *used);
+int ygzf_kfdb_query(ygzf_ctx *ctx, int n_q, const ygzf_kfdb_query_vec *q, int *common, int *first, double *score);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,14 @@ class BowKfCandidate(C.Structure):
                 ("idx1", C.c_void_p), ("off2", C.c_void_p), ("idx2", C.c_void_p)]
 
 
+class KfdbQueryVec(C.Structure):
+    _fields_ = [("n", C.c_int), ("ids", C.c_void_p), ("vals", C.c_void_p)]
+
+
+KFDB_INITIAL_ENTRIES = 65536   # YGZF_KFDB_INITIAL_ENTRIES
+KFDB_MAX_QUERY_WORDS = 8192
+
+
 class Sim3Transforms(C.Structure):
     _fields_ = [("R1w", C.c_float * 9), ("t1w", C.c_float * 3), ("R2w", C.c_float * 9), ("t2w", C.c_float * 3), ("sR12", C.c_float * 9),
                 ("t12", C.c_float * 3), ("sR21", C.c_float * 9), ("t21", C.c_float * 3)]
@@ -158,6 +166,12 @@ def load_library(build_if_missing=True):
                                                  vp, ip]
     L.ygzf_search_by_bow.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.c_int, vp, vp, vp, C.c_int, vp, vp, C.c_float, C.c_int, vp, ip]
     L.ygzf_search_by_bow_kf.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(BowKfCandidate), C.c_float, C.c_int, vp, vp]
+    L.ygzf_kfdb_add.argtypes = [vp, C.c_uint64, C.c_int, vp, vp, ip]
+    L.ygzf_kfdb_erase.argtypes = [vp, C.c_uint64]
+    L.ygzf_kfdb_clear.argtypes = [vp]
+    L.ygzf_kfdb_size.argtypes = [vp, ip, ip]
+    L.ygzf_kfdb_capacity.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ygzf_kfdb_query.argtypes = [vp, C.c_int, C.POINTER(KfdbQueryVec), vp, vp, vp]
     L.ygzf_search_for_triangulation.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(FrameView), vp, C.POINTER(FrameView), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(Camera), C.c_int, C.c_int, vp, ip]
     L.ygzf_fuse_candidates.argtypes = [vp, C.c_int, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
@@ -635,6 +649,57 @@ class Extractor:
         self._ck(self.L.ygzf_search_by_bow_kf(self.h, n1, arr(kf1.get("keys"), KP_DTYPE), arr(kf1.get("desc"), np.uint8), arr(kf1.get("valid"), np.uint8),
                                               K, recs, nnratio, int(check_ori), _p(match12), _p(nm)))
         return match12[:K, :max(n1, 0)].copy(), nm[:K].copy()
+
+    def kfdb_add(self, key, ids, vals, n=None):
+        """ygzf_kfdb_add: the BowVector (ids ascending, vals) of keyframe `key` into the device store -> its slot.  None goes down as a null
+        pointer; n overrides the count taken from ids."""
+        i = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+        v = None if vals is None else np.ascontiguousarray(vals, np.float64)
+        slot = C.c_int(-1)
+        self._ck(self.L.ygzf_kfdb_add(self.h, int(key), (0 if i is None else len(i)) if n is None else int(n), None if i is None else _p(i),
+                                      None if v is None else _p(v), C.byref(slot)))
+        return slot.value
+
+    def kfdb_erase(self, key):
+        self._ck(self.L.ygzf_kfdb_erase(self.h, int(key)))
+
+    def kfdb_clear(self):
+        self._ck(self.L.ygzf_kfdb_clear(self.h))
+
+    def kfdb_size(self):
+        """-> (live keys, slots in use)"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._ck(self.L.ygzf_kfdb_size(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def kfdb_capacity(self):
+        """-> (entries the arena holds, entries appended so far)"""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.L.ygzf_kfdb_capacity(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def kfdb_query(self, queries):
+        """ygzf_kfdb_query: queries = [(ids, vals), ...] -> (common[Q, n_slots] int32, first[Q, n_slots] int32, score[Q, n_slots] float64): words in
+        common, smallest common word id (-1: none) and L1Scoring::score(query, stored) per slot; free slots 0 / -1 / 0.0.  On an error the
+        arrays the call had preset are attached to the exception as .outputs."""
+        Q, S = len(queries), self.kfdb_size()[1]
+        keep = []
+        recs = (KfdbQueryVec * max(Q, 1))()
+        for k, (ids, vals) in enumerate(queries):
+            i = None if ids is None else np.ascontiguousarray(ids, np.uint32)
+            v = None if vals is None else np.ascontiguousarray(vals, np.float64)
+            keep += [i, v]
+            recs[k] = KfdbQueryVec(len(i) if i is not None else len(v) if v is not None else 0, None if i is None else i.ctypes.data,
+                                   None if v is None else v.ctypes.data)
+        common = np.full((Q, S), 7, np.int32)
+        first = np.full((Q, S), 7, np.int32)
+        score = np.full((Q, S), 7.0, np.float64)
+        try:
+            self._ck(self.L.ygzf_kfdb_query(self.h, Q, recs, _p(common), _p(first), _p(score)))
+        except YgzfError as e:
+            e.outputs = (common, first, score)
+            raise
+        return common, first, score
 
     def search_for_triangulation(self, off1, idx1, off2, idx2, kf1, kf2, scale_factors2, level_sigma2_2, F12, Cw1, R2w, t2w, cam2,
                                  only_stereo=False, check_ori=True):

@@ -119,6 +119,7 @@ typedef const _OutputArray &OutputArray;
 
 namespace DBoW2 {
 typedef std::map<unsigned int, std::vector<unsigned int>> FeatureVector;   // node id -> feature indices (DBoW2/FeatureVector.h)
+class BowVector : public std::map<unsigned int, double> {};                // word id -> value (DBoW2/BowVector.h)
 }
 
 namespace ygz {
@@ -191,6 +192,7 @@ public:
     DBoW2::FeatureVector mFeatVec;
     long unsigned int mnId = 0;
     ORBextractor *mpORBextractorLeft = nullptr;   // the extractor whose ComputePyramid built mvImagePyramid (include/Frame.h:220)
+    DBoW2::BowVector mBowVec;                     // read by KeyFrameDatabase::DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:180-284)
 };
 inline int MapPoint::PredictScale(const float &currentDist, Frame *pF) {  // src/MapPoint.cc:359-373
     float ratio = mfMaxDistance / currentDist;
@@ -239,6 +241,22 @@ public:
     void AddMapPoint(MapPoint *pMP, const size_t &idx) { mvpMapPoints[idx] = pMP; }             // :428-431
     void EraseMapPointMatch(const size_t &idx) { mvpMapPoints[idx] = static_cast<MapPoint *>(nullptr); }   // :433-436
     void ReplaceMapPointMatch(const size_t &idx, MapPoint *pMP) { mvpMapPoints[idx] = pMP; }    // :445-447
+    // read and written by KeyFrameDatabase (src/KeyFrameDatabase.cc:36-284; include/KeyFrame.h:276-281) and LoopClosing::DetectLoop (src/LoopClosing.cc:123-136)
+    DBoW2::BowVector mBowVec;
+    long unsigned int mnLoopQuery = 0;
+    int mnLoopWords = 0;
+    float mLoopScore = 0;
+    long unsigned int mnRelocQuery = 0;
+    int mnRelocWords = 0;
+    float mRelocScore = 0;
+    std::set<KeyFrame *> mspConnected;                       // (the keys of mConnectedKeyFrameWeights)
+    std::vector<KeyFrame *> mvpOrderedConnectedKeyFrames;
+    std::set<KeyFrame *> GetConnectedKeyFrames() const { return mspConnected; }                               // src/KeyFrame.cc:381-388
+    std::vector<KeyFrame *> GetVectorCovisibleKeyFrames() const { return mvpOrderedConnectedKeyFrames; }      // :390-393
+    std::vector<KeyFrame *> GetBestCovisibilityKeyFrames(const int &N) const {                                // :395-402
+        if ((int) mvpOrderedConnectedKeyFrames.size() < N) return mvpOrderedConnectedKeyFrames;
+        return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
+    }
 };
 inline void MapPoint::AddObservation(KeyFrame *pKF, size_t idx) {  // src/MapPoint.cc:84-94
     if (mObservations.count(pKF)) return;

@@ -228,6 +228,31 @@ struct BowKfArgs {
 };
 void launch_bow_kf(hipStream_t st, const BowKfArgs &A);
 
+// The keyframe database (kfdb_kernels.hip).  Every stored BowVector is a row of (word id, value) pairs ascending by id in one arena (ids and
+// values in parallel arrays); KfdbSlot locates a row, in entries.  k_kfdb_query writes every (query, slot) cell of common / first / score
+// (nQueries x nSlots, free slots 0 / -1 / 0.0): nothing to pre-set.  A query's ids are qIds[qOff[q] .. qOff[q + 1]), ascending, at most
+// kKfdbMaxQueryWords of them (they are held in LDS).
+constexpr int kKfdbMaxQueryWords = 8192;
+constexpr unsigned kKfdbMaxWordId = 0x7fffffffu;   // `first` is an int with -1 for "none": the entry points refuse larger ids
+struct KfdbSlot {
+    long long off;
+    int len, live;
+};
+struct KfdbQueryArgs {
+    int nSlots;
+    const KfdbSlot *slots;
+    const unsigned *ids;
+    const double *vals;
+    const int *qOff;
+    const unsigned *qIds;
+    const double *qVals;
+    int *common, *first;
+    double *score;
+};
+void launch_kfdb_query(hipStream_t st, const KfdbQueryArgs &A, int nQueries, int maxQueryWords, int cuCount);
+void launch_kfdb_repack(hipStream_t st, int nSlots, const KfdbSlot *slots, const long long *newOff, const unsigned *ids, const double *vals,
+                        unsigned *idsNew, double *valsNew);
+
 // SearchForTriangulation per-node brute force with the epipolar tests (match_kernels.hip); match12 (n1 ints) pre-set to -1, hist (30 ints) and
 // nmatches to 0
 struct TriArgs {

@@ -1015,6 +1015,8 @@ void ygzf_destroy(ygzf_ctx *c) {
     if (c->dSplitCnt.p) (void) hipFree(c->dSplitCnt.p);
     if (c->dSplitX.p) (void) hipFree(c->dSplitX.p);
     if (c->dUpStage.p) (void) hipFree(c->dUpStage.p);
+    for (auto *b : {&c->kfdb.dIds, &c->kfdb.dVals, &c->kfdb.dTable})
+        if (b->p) (void) hipFree(b->p);
     if (c->hFastStats) (void) hipHostFree(c->hFastStats);
     if (c->hStage) (void) hipHostFree(c->hStage);
     if (c->hIn) (void) hipHostFree(c->hIn);

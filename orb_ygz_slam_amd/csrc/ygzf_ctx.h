@@ -6,6 +6,7 @@
 //   ygzf_api_align.hip   SparseImgAlign (one pair, cached, resident batch), the image cache, FindDirectProjection
 //   ygzf_api_detect.hip  Thirdparty/fast replacement, DSO / FAST_KEYPOINT detectors, descriptors of existing keys
 //   ygzf_api_stereo.hip  Frame::ComputeStereoMatches
+//   ygzf_api_kfdb.hip    KeyFrameDatabase: the BowVector store and its query
 #ifndef YGZF_CTX_H
 #define YGZF_CTX_H
 #include <cmath>
@@ -15,6 +16,8 @@
 #include <cstring>
 #include <limits>
 #include <mutex>
+#include <set>
+#include <unordered_map>
 
 #include "kernels.h"
 
@@ -22,10 +25,10 @@
 
 namespace ygzf {
 YGZF_HIDDEN int cv_round_host(double v);
-enum KernelKind { KK_PYR = 0, KK_FAST, KK_OCTREE, KK_DESCRIBE, KK_HAMMING, KK_BACKPROJ, KK_MATCH, KK_SIA, KK_FAST10, KK_DSO, KK_STEREO, KK_DIRECT, KK_BOW, KK_FRUSTUM, KK_DISTINCTIVE, KK_BOWNODES, KK_GRID, KK_FASTQ, KK_TRI, KK_FASTP, KK_FUSE, KK_PROJ, KK_BOWKF, KK_COUNT };
+enum KernelKind { KK_PYR = 0, KK_FAST, KK_OCTREE, KK_DESCRIBE, KK_HAMMING, KK_BACKPROJ, KK_MATCH, KK_SIA, KK_FAST10, KK_DSO, KK_STEREO, KK_DIRECT, KK_BOW, KK_FRUSTUM, KK_DISTINCTIVE, KK_BOWNODES, KK_GRID, KK_FASTQ, KK_TRI, KK_FASTP, KK_FUSE, KK_PROJ, KK_BOWKF, KK_KFDB, KK_COUNT };
 // (the KK_FUSE slot keeps the name ygzf_profile_read has always reported for it; it times k_proj_search<PM_FUSE>)
 static const char *kKernelNames[KK_COUNT] = {"k_pyr_resize", "k_fast_tab", "k_octree", "k_describe", "k_hamming_pairs",
-                                             "k_backproject_unit", "k_match_last", "k_sia_run", "k_f10_*", "k_dso_cells", "k_stereo_*", "k_direct_projection", "k_bow_descend", "k_frustum", "k_distinctive", "k_bow_nodes", "k_features_in_area", "k_fast_quads", "k_tri_nodes", "k_fast_tab_persist", "k_fuse", "k_proj_search", "k_bow_kf_nodes"};
+                                             "k_backproject_unit", "k_match_last", "k_sia_run", "k_f10_*", "k_dso_cells", "k_stereo_*", "k_direct_projection", "k_bow_descend", "k_frustum", "k_distinctive", "k_bow_nodes", "k_features_in_area", "k_fast_quads", "k_tri_nodes", "k_fast_tab_persist", "k_fuse", "k_proj_search", "k_bow_kf_nodes", "k_kfdb_query"};
 
 struct Geometry {
     int w = 0, h = 0;
@@ -153,6 +156,19 @@ struct ygzf_ctx {
     uint8_t *hStage = nullptr;             // page-locked staging for results that go back to pageable caller memory in many small pieces
     size_t hStageBytes = 0;
     void *hStageDev = nullptr;             // the same memory as the device addresses it (kernels write small results straight into it)
+    // The keyframe database (ygzf_api_kfdb.hip).  Buffers of its own: no other entry point reads or writes them, and it touches nothing of `held`.
+    //   arena: dIds / dVals hold `cap` entries, rows are appended at `top`; an erased row leaves a hole until the arena grows (then the live rows
+    //   are repacked).  slots: the host's copy of the slot table is the authority, dTable follows it -- records [dirtyLo, dirtyHi) have not been
+    //   sent yet (the next query sends them with its own upload).
+    struct Kfdb {
+        Buf dIds, dVals, dTable;
+        size_t cap = 0, top = 0, liveEntries = 0;
+        std::vector<KfdbSlot> slots;
+        std::vector<uint64_t> keys;                 // per slot (valid while live)
+        std::unordered_map<uint64_t, int> slotOf;   // live keys
+        std::set<int> freeSlots;                    // reused lowest first
+        int dirtyLo = 0, dirtyHi = 0;
+    } kfdb;
     Held held;                             // what the buffers hold between calls (the transitions below ygzf_ctx are its only writers)
     int img0Pitch = 0;
     // timing

@@ -96,6 +96,11 @@ def main():
         # SearchByBoW(KeyFrame, KeyFrame) for three candidates on the same node list (LoopClosing::ComputeSim3): k_bow_kf_nodes
         kf2 = dict(keys=kb, desc=db, valid=np.ones(len(kb), np.uint8), off1=ko, idx1=ki, off2=fo, idx2=fi)
         ex.search_by_bow_kf(dict(keys=ka, desc=da, valid=np.ones(len(ka), np.uint8)), [kf2] * 3, 0.75, True)
+        # the keyframe database: 200 stored BowVectors of 500 words, two query vectors in one launch: k_kfdb_query
+        for k in range(200):
+            ex.kfdb_add(k, np.sort(rng.choice(20000, 500, replace=False)), np.full(500, 1.0 / 500))
+        ex.kfdb_query([(np.sort(rng.choice(20000, 500, replace=False)), np.full(500, 1.0 / 500))] * 2)
+        ex.kfdb_clear()
         # SearchForTriangulation on the same node list (LocalMapping::CreateNewMapPoints): k_tri_nodes
         sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
         from tests.tri_cases import geometry
