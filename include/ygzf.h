@@ -706,6 +706,61 @@ int ygzf_kfdb_size(ygzf_ctx *ctx, int *n_live, int *n_slots);
 int ygzf_kfdb_capacity(ygzf_ctx *ctx, size_t *entries, size_t *used);
 int ygzf_kfdb_query(ygzf_ctx *ctx, int n_q, const ygzf_kfdb_query_vec *q, int *common, int *first, double *score);
 
+/* ---- Resident keyframes: what a KeyFrame never changes after its construction, kept on the device, and the two Fuse members run against it
+ *      ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th) src/ORBmatcher.cc:748-886 and Fuse(pKF, Scw, ...) :888-1004, as
+ *      ygzf_fuse_candidates / ygzf_fuse_sim3_candidates above ---------------------------------------------------------------------------------
+ * mvKeys, mDescriptors, mvuRight, the scale tables, the calibration, the image bounds and the 64 x 48 grid of a KeyFrame are fixed once it
+ * exists; only its pose moves.  ygzf_kf_put sends them up once and builds the grid once, on the device (k_kf_grid_build); the resident searches
+ * then take a key and a pose per row and send only the point arrays, the skip mask and the row table.  Every output is bit-identical to the
+ * non-resident call on the same keyframe: the same kernel body reads the same keys, descriptors, tables and grid order in both forms.
+ *   ygzf_kf_put     : key (the caller's name of the keyframe, e.g. its address) with kf->view (mvKeys, mDescriptors, mvuRight or NULL,
+ *       mvScaleFactors or NULL for the context's tables, nlevels), kf->cam, kf->inv_level_sigma2 (NULL allowed: then ygzf_fuse_candidates_resident
+ *       refuses the keyframe, ygzf_fuse_sim3_candidates_resident does not read it) and kf->log_scale_factor.  Every check of ygzf_fuse_candidates
+ *       runs here, once (octaves inside the tables, nlevels in range, non-empty bounds, the same key-count limit), so both forms accept the same
+ *       keyframes.  *slot (nullable) receives the slot, the lowest free one.  A key that is live: YGZF_ERR_STATE, nothing changes.  The host
+ *       arrays are consumed when the call returns.
+ *   ygzf_kf_erase   : frees the key's slot; an unknown key is no error.   ygzf_kf_clear : no keys, no slots; the memory is kept.
+ *   ygzf_kf_has     : *has = 1 while the key is live.   ygzf_kf_size : live keys and slots in use (highest slot handed out since the last clear, plus one).
+ *   ygzf_kf_capacity: bytes the store's arena holds and bytes appended so far (holes of erased rows included).  A keyframe of n keys takes
+ *       64 n bytes (68 n with mvuRight) for its arrays and 12 292 + 4 n for its grid, each of the five sections rounded up to 256 bytes: about
+ *       150 KB at 2 000 keys.  The arena starts at YGZF_KF_INITIAL_BYTES and grows as the keyframe database's does: an erased row leaves a hole;
+ *       when a put does not fit behind the last row the live rows are repacked, device to device, into a fresh arena of twice the size
+ *       (doubling until it fits), or of the same size when the live rows and the new one fill at most half of it.  During a repack both arenas
+ *       exist.  The arena never shrinks; ygzf_destroy frees it.
+ *   ygzf_kf_grid    : the stored grid of a live key, as the device built it: cell_start[3073] = the exclusive prefix of the cell counts, cells
+ *       column-major (PosInGrid's nGridPosX * 48 + nGridPosY), and list[n] = the key indices cell after cell, ascending inside a cell (the
+ *       reference's push_back order).  Keys outside the 64 x 48 cells are in no list: the entries from cell_start[3072] on are -1.  Either
+ *       array may be NULL.  An unknown key is YGZF_ERR_INVALID.
+ *   ygzf_fuse_candidates_resident / ygzf_fuse_sim3_candidates_resident: arguments, outputs, skip semantics and the n_kf = 0 / n_points = 0 case
+ *       exactly as ygzf_fuse_candidates / ygzf_fuse_sim3_candidates, with a ygzf_kf_ref (key + the pose of THIS call: Rcw / tcw / Ow as a
+ *       ygzf_fuse_kf holds them) in place of each ygzf_fuse_kf.  A key listed twice gives two equal rows (with equal poses).  A key that is not
+ *       resident is YGZF_ERR_INVALID, and so is the first form on a keyframe put without inv_level_sigma2.  best_idx / best_dist are preset to
+ *       -1 / 256 before any error return (given non-null arrays and positive counts).
+ * The store has buffers of its own and runs on the context's one stream: none of these calls changes what the context holds of an extraction
+ * batch, of the keyframe database or of the image cache, and a put, a repack and a search need no ordering from the caller. */
+#define YGZF_KF_INITIAL_BYTES (8u << 20)
+typedef struct ygzf_kf_static {
+    ygzf_frame_view view;
+    ygzf_camera cam;
+    const float *inv_level_sigma2;
+    float log_scale_factor;
+} ygzf_kf_static;
+typedef struct ygzf_kf_ref {
+    uint64_t key;
+    float Rcw[9], tcw[3], Ow[3];
+} ygzf_kf_ref;
+int ygzf_kf_put(ygzf_ctx *ctx, uint64_t key, const ygzf_kf_static *kf, int *slot);
+int ygzf_kf_erase(ygzf_ctx *ctx, uint64_t key);
+int ygzf_kf_clear(ygzf_ctx *ctx);
+int ygzf_kf_has(ygzf_ctx *ctx, uint64_t key, int *has);
+int ygzf_kf_size(ygzf_ctx *ctx, int *n_live, int *n_slots);
+int ygzf_kf_capacity(ygzf_ctx *ctx, size_t *bytes, size_t *used);
+int ygzf_kf_grid(ygzf_ctx *ctx, uint64_t key, int *cell_start, int *list);
+int ygzf_fuse_candidates_resident(ygzf_ctx *ctx, int n_kf, const ygzf_kf_ref *refs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip,
+                                  float th, int *best_idx, int *best_dist);
+int ygzf_fuse_sim3_candidates_resident(ygzf_ctx *ctx, int n_kf, const ygzf_kf_ref *refs, int n_points, const ygzf_fuse_points *pts,
+                                       const uint8_t *skip, float th, int *best_idx, int *best_dist);
+
 #ifdef __cplusplus
 }
 #endif

@@ -58,6 +58,16 @@ class KfdbQueryVec(C.Structure):
     _fields_ = [("n", C.c_int), ("ids", C.c_void_p), ("vals", C.c_void_p)]
 
 
+class KfStatic(C.Structure):
+    _fields_ = [("view", FrameView), ("cam", Camera), ("inv_level_sigma2", C.c_void_p), ("log_scale_factor", C.c_float)]
+
+
+class KfRef(C.Structure):
+    _fields_ = [("key", C.c_uint64), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3)]
+
+
+KF_INITIAL_BYTES = 8 << 20     # YGZF_KF_INITIAL_BYTES
+KF_GRID_CELLS = 64 * 48
 KFDB_INITIAL_ENTRIES = 65536   # YGZF_KFDB_INITIAL_ENTRIES
 KFDB_MAX_QUERY_WORDS = 8192
 
@@ -174,6 +184,15 @@ def load_library(build_if_missing=True):
     L.ygzf_kfdb_query.argtypes = [vp, C.c_int, C.POINTER(KfdbQueryVec), vp, vp, vp]
     L.ygzf_search_for_triangulation.argtypes = [vp, C.c_int, vp, vp, vp, vp, C.POINTER(FrameView), vp, C.POINTER(FrameView), vp, vp, vp, vp, vp, vp,
                                                 C.POINTER(Camera), C.c_int, C.c_int, vp, ip]
+    L.ygzf_kf_put.argtypes = [vp, C.c_uint64, C.POINTER(KfStatic), ip]
+    L.ygzf_kf_erase.argtypes = [vp, C.c_uint64]
+    L.ygzf_kf_clear.argtypes = [vp]
+    L.ygzf_kf_has.argtypes = [vp, C.c_uint64, ip]
+    L.ygzf_kf_size.argtypes = [vp, ip, ip]
+    L.ygzf_kf_capacity.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+    L.ygzf_kf_grid.argtypes = [vp, C.c_uint64, vp, vp]
+    L.ygzf_fuse_candidates_resident.argtypes = [vp, C.c_int, C.POINTER(KfRef), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
+    L.ygzf_fuse_sim3_candidates_resident.argtypes = [vp, C.c_int, C.POINTER(KfRef), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
     L.ygzf_fuse_candidates.argtypes = [vp, C.c_int, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
     L.ygzf_fuse_sim3_candidates.argtypes = [vp, C.c_int, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, C.c_float, vp, vp]
     L.ygzf_search_by_projection_sim3.argtypes = [vp, C.POINTER(FuseKf), C.c_int, C.POINTER(FusePoints), vp, vp, C.c_float, C.c_int, C.c_int, vp, vp]
@@ -787,6 +806,80 @@ class Extractor:
         bd = np.full((max(K, 1), max(P, 1)), 256, np.int32)
         self._ck(self.L.ygzf_fuse_sim3_candidates(self.h, K, arr, P, C.byref(pts), None if sk is None else _p(sk), th, _p(bi), _p(bd)))
         return bi[:K, :P].copy(), bd[:K, :P].copy()
+
+    def kf_put(self, key, kf):
+        """ygzf_kf_put: the keyframe dict of fuse_candidates (its Rcw / tcw / Ow are not read: the pose travels with each search) becomes
+        resident under `key` -> its slot.  The arrays are consumed when the call returns."""
+        keep = []
+        f = self._fuse_kfs([kf], keep)[0]
+        rec = KfStatic(f.view, f.cam, f.inv_level_sigma2, f.log_scale_factor)
+        slot = C.c_int(-1)
+        self._ck(self.L.ygzf_kf_put(self.h, int(key), C.byref(rec), C.byref(slot)))
+        return slot.value
+
+    def kf_erase(self, key):
+        self._ck(self.L.ygzf_kf_erase(self.h, int(key)))
+
+    def kf_clear(self):
+        self._ck(self.L.ygzf_kf_clear(self.h))
+
+    def kf_has(self, key):
+        a = C.c_int(0)
+        self._ck(self.L.ygzf_kf_has(self.h, int(key), C.byref(a)))
+        return bool(a.value)
+
+    def kf_size(self):
+        """-> (live keys, slots in use)"""
+        a, b = C.c_int(0), C.c_int(0)
+        self._ck(self.L.ygzf_kf_size(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def kf_capacity(self):
+        """-> (bytes the arena holds, bytes appended so far)"""
+        a, b = C.c_size_t(0), C.c_size_t(0)
+        self._ck(self.L.ygzf_kf_capacity(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def kf_grid(self, key, n):
+        """ygzf_kf_grid: the stored grid of resident keyframe `key` with n keys -> (cell_start[3073], list[n]) int32: the exclusive prefix of the
+        cell counts (cells column-major, px * 48 + py) and the key indices cell after cell, ascending inside a cell, -1 behind the last cell."""
+        cs = np.full(KF_GRID_CELLS + 1, -7, np.int32)
+        ls = np.full(max(int(n), 1), -7, np.int32)
+        self._ck(self.L.ygzf_kf_grid(self.h, int(key), _p(cs), _p(ls)))
+        return cs, ls[:int(n)].copy()
+
+    def _fuse_resident(self, fn, refs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th, skip):
+        keep = []
+        K = len(refs)
+        arr = (KfRef * max(K, 1))()
+        for k, (key, Rcw, tcw, Ow) in enumerate(refs):
+            r = arr[k]
+            r.key = int(key)
+            r.Rcw[:] = [float(x) for x in np.asarray(Rcw, np.float32).reshape(9)]
+            r.tcw[:] = [float(x) for x in np.asarray(tcw, np.float32).reshape(3)]
+            r.Ow[:] = [float(x) for x in np.asarray(Ow, np.float32).reshape(3)]
+        pts, P = self._fuse_points(world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, keep)
+        sk = None if skip is None else np.ascontiguousarray(skip, np.uint8).reshape(K, P)
+        bi = np.full((max(K, 1), max(P, 1)), 7, np.int32)
+        bd = np.full((max(K, 1), max(P, 1)), 7, np.int32)
+        try:
+            self._ck(fn(self.h, K, arr, P, C.byref(pts), None if sk is None else _p(sk), th, _p(bi), _p(bd)))
+        except YgzfError as e:
+            e.outputs = (bi[:K, :P].copy(), bd[:K, :P].copy())
+            raise
+        if K == 0 or P == 0:
+            return np.full((K, P), -1, np.int32), np.full((K, P), 256, np.int32)
+        return bi[:K, :P].copy(), bd[:K, :P].copy()
+
+    def fuse_candidates_resident(self, refs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=3.0, skip=None):
+        """fuse_candidates against resident keyframes (kf_put).  refs: (key, Rcw, tcw, Ow) per row, the pose of THIS call -> (best_idx, best_dist)
+        as fuse_candidates returns them, bit for bit.  On an error the outputs the call had preset are attached to the exception as .outputs."""
+        return self._fuse_resident(self.L.ygzf_fuse_candidates_resident, refs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th, skip)
+
+    def fuse_sim3_candidates_resident(self, refs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=4.0, skip=None):
+        """fuse_sim3_candidates against resident keyframes; refs as fuse_candidates_resident, Rcw / tcw / Ow the decomposed Scw."""
+        return self._fuse_resident(self.L.ygzf_fuse_sim3_candidates_resident, refs, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th,
+                                   skip)
 
     def search_by_projection_sim3(self, kf, world, normal, max_dist_inv, min_dist_inv, mf_max_distance, desc, th=10.0, skip=None, key_matched=None,
                                   n_best=1, max_dist=255):

@@ -57,6 +57,17 @@ inline bool pack_keyframe(KeyFrame *pKF, const KeyFrame *cam, ygzf_fuse_kf &f, s
     return true;
 }
 
+// ... the same without a pose, for the resident store (KeyFrameStore.h: ygzf_kf_put)
+inline bool pack_keyframe_static(KeyFrame *pKF, ygzf_kf_static &rec, std::vector<uint8_t> &hold, const char *who) {
+    ygzf_fuse_kf f;
+    if (!pack_keyframe(pKF, pKF, f, hold, who)) return false;
+    rec.view = f.view;
+    rec.cam = f.cam;
+    rec.inv_level_sigma2 = f.inv_level_sigma2;
+    rec.log_scale_factor = f.log_scale_factor;
+    return true;
+}
+
 // GetWorldPos, GetNormal, the distance limits, mfMaxDistance and GetDescriptor of pts[first ..]; entries that are null or have skip[i - first] != 0
 // are not read (they stay zero: the device skips them by the same mask)
 struct PointArrays {

@@ -13,6 +13,7 @@
 
 #include "../../../include/ygzf.h"
 #include "FuseApply.h"
+#include "KeyFrameStore.h"
 #include "MatcherPack.h"
 #include "ORBmatcherFuse.h"
 #include "ygzf_pool.h"
@@ -29,6 +30,7 @@ struct DeviceQuery {
                     std::vector<int> &bd) const {
         const size_t K = kfs.size(), P = pts.size();
         if (K == 0 || P == 0) return true;
+        if (KeyFrameDeviceStore::sResident) return resident(kfs, pts, skip, bi, bd);
         std::vector<ygzf_fuse_kf> kv(K);
         std::vector<std::vector<uint8_t>> hold(K);
         for (size_t k = 0; k < K; k++) {
@@ -48,6 +50,36 @@ struct DeviceQuery {
         const int rc = ygzf_fuse_candidates(c, (int) K, kv.data(), (int) P, &fp, skip.data(), th, bi.data(), bd.data());
         if (rc != YGZF_OK) {
             ygzf_host::report_failure(who, ygzf_last_error(c));
+            return false;
+        }
+        return true;
+    }
+    // the same query against the store's resident copies (KeyFrameStore.h): each keyframe is put when it is met first, the poses are read now
+    bool resident(const std::vector<KeyFrame *> &kfs, const std::vector<MapPoint *> &pts, const std::vector<uint8_t> &skip, std::vector<int> &bi,
+                  std::vector<int> &bd) const {
+        KeyFrameDeviceStore::Guard g(KeyFrameDeviceStore::instance(ORBextractor::sDevice));
+        ygzf_ctx *sc = g.ctx(who);
+        if (!sc) return false;
+        std::vector<ygzf_kf_ref> refs(kfs.size());
+        for (size_t k = 0; k < kfs.size(); k++) {
+            KeyFrame *pKF = kfs[k];
+            if (!g.resident(pKF, pKF->mnId, pKF->N, [&](ygzf_kf_static &rec, std::vector<uint8_t> &hold) { return pack_keyframe_static(pKF, rec, hold, who); }, who))
+                return false;
+            ygzf_kf_ref &f = refs[k];
+            f.key = KeyFrameDeviceStore::key(pKF);
+            const Matrix3f R = pKF->GetRotation();
+            const Vector3f t = pKF->GetTranslation(), O = pKF->GetCameraCenter();
+            for (int r = 0; r < 3; r++) {
+                for (int cc = 0; cc < 3; cc++) f.Rcw[3 * r + cc] = R(r, cc);
+                f.tcw[r] = t[r];
+                f.Ow[r] = O[r];
+            }
+        }
+        const PointArrays pa(pts, 0, nullptr);
+        g.count_query();
+        const int rc = ygzf_fuse_candidates_resident(sc, (int) refs.size(), refs.data(), (int) pts.size(), &pa.view, skip.data(), th, bi.data(), bd.data());
+        if (rc != YGZF_OK) {
+            ygzf_host::report_failure(who, ygzf_last_error(sc));
             return false;
         }
         return true;

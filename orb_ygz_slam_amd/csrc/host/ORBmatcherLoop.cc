@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "../../../include/ygzf.h"
+#include "KeyFrameStore.h"
 #include "LoopApply.h"
 #include "MatcherPack.h"
 #include "ORBmatcherLoop.h"
@@ -48,11 +49,33 @@ struct FuseScwQuery {
                     std::vector<int> &bd) const {
         const size_t K = rows.size(), P = pts.size();
         if (K == 0 || P == 0) return true;
+        const PointArrays pa(pts, 0, nullptr);
+        if (KeyFrameDeviceStore::sResident) {   // against the store's resident copies (KeyFrameStore.h); the decomposed Scw travels with the call
+            KeyFrameDeviceStore::Guard g(KeyFrameDeviceStore::instance(ORBextractor::sDevice));
+            ygzf_ctx *sc = g.ctx(who);
+            if (!sc) return false;
+            std::vector<ygzf_kf_ref> refs(K);
+            for (size_t k = 0; k < K; k++) {
+                KeyFrame *pKF = kfs[rows[k]];
+                if (!g.resident(pKF, pKF->mnId, pKF->N, [&](ygzf_kf_static &rec, std::vector<uint8_t> &hold) { return pack_keyframe_static(pKF, rec, hold, who); }, who))
+                    return false;
+                refs[k].key = KeyFrameDeviceStore::key(pKF);
+                std::memcpy(refs[k].Rcw, poses[rows[k]].R, 36);
+                std::memcpy(refs[k].tcw, poses[rows[k]].t, 12);
+                std::memcpy(refs[k].Ow, poses[rows[k]].Ow, 12);
+            }
+            g.count_query();
+            const int rc = ygzf_fuse_sim3_candidates_resident(sc, (int) K, refs.data(), (int) P, &pa.view, skip.data(), th, bi.data(), bd.data());
+            if (rc != YGZF_OK) {
+                ygzf_host::report_failure(who, ygzf_last_error(sc));
+                return false;
+            }
+            return true;
+        }
         std::vector<ygzf_fuse_kf> kv(K);
         std::vector<std::vector<uint8_t>> hold(K);
         for (size_t k = 0; k < K; k++)
             if (!pack_kf(kfs[rows[k]], kfs[rows[k]], &poses[rows[k]], kv[k], hold[k], who)) return false;
-        const PointArrays pa(pts, 0, nullptr);
         const int rc = ygzf_fuse_sim3_candidates(c, (int) K, kv.data(), (int) P, &pa.view, skip.data(), th, bi.data(), bd.data());
         if (rc != YGZF_OK) {
             ygzf_host::report_failure(who, ygzf_last_error(c));

@@ -394,7 +394,8 @@ hipError_t launch_features_in_area(hipStream_t st, const FiaArgs &A);
 // K keyframes x P points, per pair the bestIdx / bestDist of src/ORBmatcher.cc:764-868 before any map update (-1 / 256: none); and
 // LoopClosing's Fuse(pKF, Scw, ...), SearchByProjection(pKF, Scw, ...) and the two directions of SearchBySim3.  A row is one target keyframe
 // with its own point list.
-struct FuseKf {                     // one keyframe; keys / desc / uRight are byte offsets from ProjArgs::base (uRight -1: monocular)
+struct FuseKf {                     // one keyframe; keys / desc / uRight are byte offsets from ProjArgs::base (uRight -1: monocular),
+                                    // from ProjArgs::kfBase when the launch is a resident one
     long long keys, desc, uRight;
     int n, nLevels;
     float Rcw[9], tcw[3], Ow[3];
@@ -412,17 +413,31 @@ struct ProjRow {
     long long skip, keyMatched;     // byte offsets from ProjArgs::base, -1: none.  skip: nPoints bytes; keyMatched: kf.n bytes (PM_PROJ_SCW)
     int nPoints;
     long long out;                  // first point of this row in bestIdx / bestDist (in points; times nBest entries)
+    long long cellStart, list;      // resident launches: the keyframe's stored grid (k_kf_grid_build), byte offsets from ProjArgs::kfBase
 };
 struct ProjArgs {
     int mode;                       // any ProjMode
     int nRows, maxPoints, slice;    // slice = points per workgroup; grid = (ceil(maxPoints / slice), nRows)
-    const uint8_t *base;
+    const uint8_t *base;            // the call's packed staging area: the point arrays, masks and (non-resident) the keyframes' arrays
+    const uint8_t *kfBase;          // null, or the keyframe store's arena: every row's keyframe and its grid lie there (PM_FUSE, PM_FUSE_SCW)
     const ProjRow *rows;
     float th;
     int nBest, maxHamming;          // candidates kept per point (1 unless PM_PROJ_SCW) and the largest distance kept (<= 255)
     int *bestIdx, *bestDist;        // nBest entries per point, ascending (dist, list position), padded with -1 / 256
 };
 hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys);
+
+// The resident keyframes (kfstore_kernels.hip; entry points in ygzf_api_kfstore.hip): k_kf_grid_build writes the CSR build_grid_lds produces --
+// cellStart[GRID_CELLS + 1] (64 x 48 cells, column-major px * 48 + py) and list[n], key indices ascending inside a cell, the entries behind
+// cellStart[GRID_CELLS] (keys outside the cells are in no list) set to -1 -- once per keyframe.  n is bounded by fuse_lds_bytes(n) <= kMaxDynLds.
+constexpr int kKfGridCells = 64 * 48;
+struct KfGridArgs {
+    const ygzf_kp *keys;
+    int n;
+    float minX, minY, gridInvW, gridInvH;
+    int *cellStart, *list;
+};
+hipError_t launch_kf_grid_build(hipStream_t st, const KfGridArgs &A);
 
 struct SiaArgs {
     int ldsFeat;                    // feature slots of the dynamic LDS carve-up (float4 s_feat[ldsFeat] | float2 s_uv[ldsFeat] | float4 s_jac[2*ldsFeat])

@@ -15,10 +15,10 @@
 // is applied at the end.  Float expressions are evaluated in source order (library built with -ffp-contract=off).
 #include "kernels.h"
 #include "wave_ops.h"
+#include "grid_lds.h"   // GRID_COLS / GRID_ROWS / GRID_CELLS, kMatchBlock, build_grid_lds
 
 namespace ygzf {
 
-constexpr int GRID_COLS = 64, GRID_ROWS = 48, GRID_CELLS = GRID_COLS * GRID_ROWS;
 constexpr int TH_HIGH = 100;
 constexpr int HISTO_LENGTH = 30;
 
@@ -46,7 +46,6 @@ struct QueryParam {  // per Last keypoint, precomputed by all waves (32 bytes)
     unsigned pad;
 };
 
-constexpr int kMatchBlock = 1024;
 constexpr unsigned kNoKey = (256u << 16);
 constexpr int kExtSlots = 64;
 
@@ -1830,60 +1829,7 @@ static inline size_t al16(size_t b) { return (b + 15) & ~(size_t) 15; }
 // sort; the cells of one grid column are adjacent, so the cells [minCy, maxCy] of column ix are ONE contiguous run of the list) and
 // serves a slice of the queries, one wave per query: 64 list entries per step, ordered append by ballot rank.
 // ------------------------------------------------------------------------------------------------------------------
-// Frame::AssignFeaturesToGrid in LDS (one workgroup of kMatchBlock threads): cellStart[GRID_CELLS + 1] holds the exclusive prefix of the cell
-// counts, list[cellStart[c] ..) the keypoint indices of cell c in ascending order (the reference's push_back order); cellFill (GRID_CELLS)
-// and s_tmp (kMatchBlock / 64) are scratch.  Ends with a barrier.
-__device__ void build_grid_lds(const ygzf_kp *__restrict__ keys, int n, float minX, float minY, float gridInvW, float gridInvH, int *cellStart,
-                               int *cellFill, int *list, int *s_tmp) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    for (int i = tid; i < GRID_CELLS; i += kMatchBlock) cellFill[i] = 0;
-    __syncthreads();
-    for (int i = tid; i < n; i += kMatchBlock) {
-        const ygzf_kp k = keys[i];
-        const int px = (int) roundf((k.x - minX) * gridInvW);     // Frame::PosInGrid (round, as the reference)
-        const int py = (int) roundf((k.y - minY) * gridInvH);
-        if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) atomicAdd(&cellFill[px * GRID_ROWS + py], 1);
-    }
-    __syncthreads();
-    {   // exclusive scan of 3072 counts: 3 per thread
-        const int per = GRID_CELLS / kMatchBlock;
-        int sum = 0;
-        for (int k = 0; k < per; k++) sum += cellFill[tid * per + k];
-        const int incl = m_wave_incl_scan(sum);
-        if (lane == 63) s_tmp[wave] = incl;
-        __syncthreads();
-        int woff = 0;
-        for (int w2 = 0; w2 < wave; w2++) woff += s_tmp[w2];
-        int off = woff + incl - sum;
-        for (int k = 0; k < per; k++) {
-            const int c = cellFill[tid * per + k];
-            cellStart[tid * per + k] = off;
-            off += c;
-        }
-        if (tid == kMatchBlock - 1) cellStart[GRID_CELLS] = off;
-    }
-    __syncthreads();
-    for (int i = tid; i < GRID_CELLS; i += kMatchBlock) cellFill[i] = cellStart[i];
-    __syncthreads();
-    for (int i = tid; i < n; i += kMatchBlock) {
-        const ygzf_kp k = keys[i];
-        const int px = (int) roundf((k.x - minX) * gridInvW);
-        const int py = (int) roundf((k.y - minY) * gridInvH);
-        if (!(px < 0 || px >= GRID_COLS || py < 0 || py >= GRID_ROWS)) list[atomicAdd(&cellFill[px * GRID_ROWS + py], 1)] = i;
-    }
-    __syncthreads();
-    for (int c = tid; c < GRID_CELLS; c += kMatchBlock) {  // cells keep ascending keypoint index (push_back order)
-        const int s = cellStart[c], e = cellStart[c + 1];
-        for (int a = s + 1; a < e; a++) {
-            const int v = list[a];
-            int b = a - 1;
-            while (b >= s && list[b] > v) { list[b + 1] = list[b]; b--; }
-            list[b + 1] = v;
-        }
-    }
-    __syncthreads();
-}
-
+// (the grid itself: build_grid_lds, grid_lds.h)
 __global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ int s_tmp[kMatchBlock / 64];
@@ -2104,7 +2050,14 @@ size_t fuse_lds_bytes(int maxKeys) { return fia_lds_bytes(maxKeys); }
 // Every projection search: workgroup = one row (blockIdx.y: a target keyframe with its own point list) x a slice of that row's points.
 // Rows shorter than the longest leave their surplus workgroups idle (SearchBySim3's two directions have N1 and N2 points).  Fuse's K keyframes
 // x P points are K rows over one copy of the point arrays, row k's skip mask and results at k * P.
-template <int MODE>
+//
+// RES: the row's keyframe is resident (ygzf_api_kfstore.hip).  Its keys / descriptors / mvuRight are offsets from A.kfBase, the store's arena, and
+// so are R.cellStart / R.list, the grid k_kf_grid_build left there when the keyframe was put: nothing is rebuilt and no dynamic LDS is taken.  The
+// grid is read where it lies, in global memory.  A point reads two cellStart entries per grid column of its window and each list entry of those
+// columns once, 64 consecutive ones per step -- a few hundred bytes per point, against the 12 KB + 4 n bytes per workgroup a copy into the LDS
+// carve-up would move for the 64 points of a slice; and without the carve-up the workgroups of a CU are limited by their waves, not by LDS.
+// proj_search_point is the same code for both.
+template <int MODE, bool RES>
 __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ int s_tmp[kMatchBlock / 64];
@@ -2115,9 +2068,10 @@ __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
     const int p0 = blockIdx.x * A.slice, p1 = min(R.nPoints, p0 + A.slice);
     if (p0 >= p1) return;                            // the whole workgroup, before any barrier
     const FuseKf &K = R.kf;
-    const ygzf_kp *keys = (const ygzf_kp *) (A.base + K.keys);
-    const uint8_t *kdesc = A.base + K.desc;
-    const float *uRight = MODE == PM_FUSE && K.uRight >= 0 ? (const float *) (A.base + K.uRight) : nullptr;   // the other bodies have no mvuRight term
+    const uint8_t *kfBase = RES ? A.kfBase : A.base;
+    const ygzf_kp *keys = (const ygzf_kp *) (kfBase + K.keys);
+    const uint8_t *kdesc = kfBase + K.desc;
+    const float *uRight = MODE == PM_FUSE && K.uRight >= 0 ? (const float *) (kfBase + K.uRight) : nullptr;   // the other bodies have no mvuRight term
     const float *world = (const float *) (A.base + R.world);
     const float *normal = R.normal >= 0 ? (const float *) (A.base + R.normal) : nullptr;
     const float *maxInv = (const float *) (A.base + R.maxDistInv), *minInv = (const float *) (A.base + R.minDistInv);
@@ -2126,7 +2080,13 @@ __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
     const uint8_t *skip = R.skip >= 0 ? A.base + R.skip : nullptr;
     const uint8_t *keyMatched = R.keyMatched >= 0 ? A.base + R.keyMatched : nullptr;
     const int nBest = MODE == PM_PROJ_SCW ? A.nBest : 1;
-    build_grid_lds(keys, K.n, K.minX, K.minY, K.gridInvW, K.gridInvH, cellStart, cellFill, list, s_tmp);
+    const int *gStart = cellStart, *gList = list;
+    if (RES) {
+        gStart = (const int *) (A.kfBase + R.cellStart);
+        gList = (const int *) (A.kfBase + R.list);
+    } else {
+        build_grid_lds(keys, K.n, K.minX, K.minY, K.gridInvW, K.gridInvH, cellStart, cellFill, list, s_tmp);
+    }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int i = p0 + wave; i < p1; i += kMatchBlock / 64) {
         const size_t o = ((size_t) R.out + (size_t) i) * (size_t) nBest;
@@ -2135,7 +2095,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
                 for (int k = 0; k < nBest; k++) { A.bestIdx[o + k] = -1; A.bestDist[o + k] = 256; }
             continue;
         }
-        proj_search_point<MODE>(K, R.R2, R.t2, keys, kdesc, uRight, keyMatched, cellStart, list, world + 3 * (size_t) i,
+        proj_search_point<MODE>(K, R.R2, R.t2, keys, kdesc, uRight, keyMatched, gStart, gList, world + 3 * (size_t) i,
                                 normal ? normal + 3 * (size_t) i : nullptr, minInv[i], maxInv[i], mfMax[i],
                                 (const uint64_t *) (mpDesc + 32 * (size_t) i), A.th, nBest, A.maxHamming, lane, A.bestIdx + o, A.bestDist + o);
     }
@@ -2143,14 +2103,26 @@ __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
 
 template <int MODE>
 static hipError_t launch_proj_mode(hipStream_t st, const ProjArgs &A, int maxKeys) {
-    hipError_t e = hipFuncSetAttribute((const void *) k_proj_search<MODE>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    hipError_t e = hipFuncSetAttribute((const void *) k_proj_search<MODE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_proj_search<MODE>, dim3((A.maxPoints + A.slice - 1) / A.slice, A.nRows), dim3(kMatchBlock), fuse_lds_bytes(maxKeys), st, A);
+    hipLaunchKernelGGL((k_proj_search<MODE, false>), dim3((A.maxPoints + A.slice - 1) / A.slice, A.nRows), dim3(kMatchBlock), fuse_lds_bytes(maxKeys), st, A);
+    return hipSuccess;
+}
+template <int MODE>
+static hipError_t launch_proj_resident(hipStream_t st, const ProjArgs &A) {
+    hipLaunchKernelGGL((k_proj_search<MODE, true>), dim3((A.maxPoints + A.slice - 1) / A.slice, A.nRows), dim3(kMatchBlock), 0, st, A);
     return hipSuccess;
 }
 
 hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys) {
     if (A.nRows <= 0 || A.maxPoints <= 0) return hipSuccess;
+    if (A.kfBase) {   // every row's keyframe is resident: the two Fuse members have that form
+        switch (A.mode) {
+        case PM_FUSE: return launch_proj_resident<PM_FUSE>(st, A);
+        case PM_FUSE_SCW: return launch_proj_resident<PM_FUSE_SCW>(st, A);
+        }
+        return hipErrorInvalidValue;
+    }
     switch (A.mode) {
     case PM_FUSE: return launch_proj_mode<PM_FUSE>(st, A, maxKeys);
     case PM_FUSE_SCW: return launch_proj_mode<PM_FUSE_SCW>(st, A, maxKeys);

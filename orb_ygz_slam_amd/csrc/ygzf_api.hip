@@ -1017,6 +1017,7 @@ void ygzf_destroy(ygzf_ctx *c) {
     if (c->dUpStage.p) (void) hipFree(c->dUpStage.p);
     for (auto *b : {&c->kfdb.dIds, &c->kfdb.dVals, &c->kfdb.dTable})
         if (b->p) (void) hipFree(b->p);
+    if (c->kfs.dArena.p) (void) hipFree(c->kfs.dArena.p);
     if (c->hFastStats) (void) hipHostFree(c->hFastStats);
     if (c->hStage) (void) hipHostFree(c->hStage);
     if (c->hIn) (void) hipHostFree(c->hIn);

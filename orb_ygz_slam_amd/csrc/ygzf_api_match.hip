@@ -712,42 +712,50 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
     return YGZF_OK;
 }
 
+}  // extern "C" (the next two are the library's own, shared with ygzf_api_kfstore.hip: ygzf_ctx.h)
+
 // One keyframe of the Fuse / loop-closing searches: the argument checks (needSigma: mvInvLevelSigma2 is read, i.e. the first Fuse) ...
-static int fuse_kf_check(ygzf_ctx *c, const ygzf_fuse_kf &K, int k, bool needSigma) {
-    const int n = K.view.n;
+int kf_args_check(ygzf_ctx *c, const ygzf_frame_view &view, const ygzf_camera &cam, const float *inv_level_sigma2, int k, bool needSigma) {
+    const int n = view.n;
     if (n < 0) return fail(c, YGZF_ERR_INVALID, "keyframe %d: negative key count", k);
-    if (n > 0 && (!K.view.keys || !K.view.desc)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null key array", k);
-    if (needSigma && !K.inv_level_sigma2) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null mvInvLevelSigma2", k);
-    const int L = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
+    if (n > 0 && (!view.keys || !view.desc)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null key array", k);
+    if (needSigma && !inv_level_sigma2) return fail(c, YGZF_ERR_INVALID, "keyframe %d: null mvInvLevelSigma2", k);
+    const int L = view.scale_factors ? view.nlevels : c->tab.cfg.nlevels;
     if (L < 1 || L > kMaxLevels) return fail(c, YGZF_ERR_INVALID, "keyframe %d: nlevels out of range", k);
-    if (!(K.cam.max_x > K.cam.min_x) || !(K.cam.max_y > K.cam.min_y)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: empty image bounds", k);
+    if (!(cam.max_x > cam.min_x) || !(cam.max_y > cam.min_y)) return fail(c, YGZF_ERR_INVALID, "keyframe %d: empty image bounds", k);
     for (int i = 0; i < n; i++)
-        if (K.view.keys[i].octave < 0 || K.view.keys[i].octave >= L)
+        if (view.keys[i].octave < 0 || view.keys[i].octave >= L)
             return fail(c, YGZF_ERR_INVALID, "keyframe %d: keypoint octave outside the scale tables", k);
     if (fuse_lds_bytes(n) > (size_t) kMaxDynLds)
         return fail(c, YGZF_ERR_UNSUPPORTED, "keyframe %d: more than %d keypoints in one grid", k, (int) ((kMaxDynLds - 25000) / 4));
     return YGZF_OK;
 }
-// ... and its device record; the key arrays join the packed upload
-static void fuse_kf_fill(ygzf_ctx *c, PackedTransfer &P, const ygzf_fuse_kf &K, FuseKf &F) {
+// ... and its device record: what does not depend on the pose or on where the arrays lie (a resident keyframe keeps this part) ...
+void kf_record_static(ygzf_ctx *c, const ygzf_frame_view &view, const ygzf_camera &cam, const float *inv_level_sigma2, float log_scale_factor, FuseKf &F) {
     memset(&F, 0, sizeof F);
+    F.n = view.n;
+    F.nLevels = view.scale_factors ? view.nlevels : c->tab.cfg.nlevels;
+    F.fx = cam.fx; F.fy = cam.fy; F.cx = cam.cx; F.cy = cam.cy; F.mbf = cam.mbf;
+    F.minX = cam.min_x; F.minY = cam.min_y; F.maxX = cam.max_x; F.maxY = cam.max_y;
+    grid_inverses(cam, F.gridInvW, F.gridInvH);
+    predict_scale_steps(log_scale_factor, F.nLevels, F.levelStep);
+    for (int l = 0; l < kMaxLevels; l++) {
+        F.scale[l] = l < F.nLevels ? (view.scale_factors ? view.scale_factors[l] : c->tab.scale[l]) : 1.f;
+        F.invSigma2[l] = l < F.nLevels && inv_level_sigma2 ? inv_level_sigma2[l] : 1.f;
+    }
+}
+extern "C" {
+static int fuse_kf_check(ygzf_ctx *c, const ygzf_fuse_kf &K, int k, bool needSigma) { return kf_args_check(c, K.view, K.cam, K.inv_level_sigma2, k, needSigma); }
+// ... with the pose; the key arrays join the packed upload
+static void fuse_kf_fill(ygzf_ctx *c, PackedTransfer &P, const ygzf_fuse_kf &K, FuseKf &F) {
+    kf_record_static(c, K.view, K.cam, K.inv_level_sigma2, K.log_scale_factor, F);
     const size_t n = (size_t) K.view.n;
     F.keys = (long long) P.add_in(K.view.keys, sizeof(ygzf_kp) * n);
     F.desc = (long long) P.add_in(K.view.desc, 32 * n);
     F.uRight = K.view.u_right ? (long long) P.add_in(K.view.u_right, 4 * n) : -1;
-    F.n = (int) n;
-    F.nLevels = K.view.scale_factors ? K.view.nlevels : c->tab.cfg.nlevels;
     memcpy(F.Rcw, K.Rcw, 36);
     memcpy(F.tcw, K.tcw, 12);
     memcpy(F.Ow, K.Ow, 12);
-    F.fx = K.cam.fx; F.fy = K.cam.fy; F.cx = K.cam.cx; F.cy = K.cam.cy; F.mbf = K.cam.mbf;
-    F.minX = K.cam.min_x; F.minY = K.cam.min_y; F.maxX = K.cam.max_x; F.maxY = K.cam.max_y;
-    grid_inverses(K.cam, F.gridInvW, F.gridInvH);
-    predict_scale_steps(K.log_scale_factor, F.nLevels, F.levelStep);
-    for (int l = 0; l < kMaxLevels; l++) {
-        F.scale[l] = l < F.nLevels ? (K.view.scale_factors ? K.view.scale_factors[l] : c->tab.scale[l]) : 1.f;
-        F.invSigma2[l] = l < F.nLevels && K.inv_level_sigma2 ? K.inv_level_sigma2[l] : 1.f;
-    }
 }
 
 // ---- the projection searches of one snapshot (include/ygzf.h; match_kernels.hip: k_proj_search) -------------------------------------------
@@ -771,7 +779,7 @@ static void proj_row_points(PackedTransfer &P, ProjRow &R, const ygzf_fuse_point
     R.nPoints = n;
 }
 static int proj_run(ygzf_ctx *c, PackedTransfer &P, std::vector<ProjRow> &rows, int mode, int slot, int maxPoints, int maxKeys, float th, int nBest,
-                    int maxHamming, size_t oI, size_t oD) {
+                    int maxHamming, size_t oI, size_t oD, const uint8_t *kfBase = nullptr) {
     int rc;
     const size_t iR = P.add_in(rows.data(), sizeof(ProjRow) * rows.size());
     uint8_t *d;
@@ -781,6 +789,7 @@ static int proj_run(ygzf_ctx *c, PackedTransfer &P, std::vector<ProjRow> &rows, 
     A.nRows = (int) rows.size(); A.maxPoints = maxPoints;
     A.slice = 64;   // points per workgroup (four per wave): a forward Fuse of 20 keyframes x 1 500 points and a reverse one of 1 x 30 000 both give ~500 workgroups
     A.base = d;
+    A.kfBase = kfBase;
     A.rows = (const ProjRow *) (d + iR);
     A.th = th;
     A.nBest = nBest; A.maxHamming = maxHamming;
@@ -833,6 +842,62 @@ int ygzf_fuse_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_p
 int ygzf_fuse_sim3_candidates(ygzf_ctx *c, int n_kf, const ygzf_fuse_kf *kfs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
                               int *best_idx, int *best_dist) {
     return fuse_rows(c, PM_FUSE_SCW, false, KK_PROJ, n_kf, kfs, n_points, pts, skip, th, best_idx, best_dist);
+}
+
+// The two Fuse members over resident keyframes (ygzf_api_kfstore.hip): fuse_rows with every row's keyframe taken from the store.  Only the
+// point arrays, the skip mask and the row table cross the link; a row's record is the slot's own, moved to where the row lies in the arena, with
+// the call's pose.
+static int fuse_rows_resident(ygzf_ctx *c, int mode, bool needSigma, int slot, int n_kf, const ygzf_kf_ref *refs, int n_points, const ygzf_fuse_points *pts,
+                              const uint8_t *skip, float th, int *best_idx, int *best_dist) {
+    if (!c) return fail(c, YGZF_ERR_INVALID, "null argument");
+    if (n_kf < 0 || n_points < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
+    if (n_kf == 0 || n_points == 0) return YGZF_OK;
+    if (!best_idx || !best_dist) return fail(c, YGZF_ERR_INVALID, "null argument");
+    const size_t N = (size_t) n_points, E = N * (size_t) n_kf;
+    for (size_t i = 0; i < E; i++) { best_idx[i] = -1; best_dist[i] = 256; }
+    if (!refs || !pts) return fail(c, YGZF_ERR_INVALID, "null argument");
+    int rc;
+    if ((rc = proj_points_check(c, pts, true))) return rc;
+    const ygzf_ctx::KfStore &S = c->kfs;
+    for (int k = 0; k < n_kf; k++) {
+        const auto it = S.slotOf.find(refs[k].key);
+        if (it == S.slotOf.end()) return fail(c, YGZF_ERR_INVALID, "keyframe %d: key %llu is not resident", k, (unsigned long long) refs[k].key);
+        if (needSigma && !S.slots[it->second].hasSigma) return fail(c, YGZF_ERR_INVALID, "keyframe %d: put without mvInvLevelSigma2", k);
+    }
+    HIPCHECK(c, hipSetDevice(c->device));
+    PackedTransfer P(c);
+    std::vector<ProjRow> rows((size_t) n_kf);
+    memset(rows.data(), 0, sizeof(ProjRow) * rows.size());
+    proj_row_points(P, rows[0], pts, n_points, true, nullptr);   // one copy of the point arrays, shared by every row
+    const long long iS = skip ? (long long) P.add_in(skip, (size_t) n_kf * N) : -1;
+    for (int k = 0; k < n_kf; k++) {
+        if (k) rows[k] = rows[0];
+        const ygzf_ctx::KfStore::Slot &L = S.slots[S.slotOf.at(refs[k].key)];
+        FuseKf &F = rows[k].kf;
+        F = L.kf;
+        F.keys += L.off;
+        F.desc += L.off;
+        if (F.uRight >= 0) F.uRight += L.off;
+        memcpy(F.Rcw, refs[k].Rcw, 36);
+        memcpy(F.tcw, refs[k].tcw, 12);
+        memcpy(F.Ow, refs[k].Ow, 12);
+        rows[k].cellStart = L.off + L.cellStart;
+        rows[k].list = L.off + L.list;
+        rows[k].skip = skip ? iS + (long long) ((size_t) k * N) : -1;
+        rows[k].out = (long long) ((size_t) k * N);
+    }
+    const size_t oI = P.add_out(best_idx, 4 * E), oD = P.add_out(best_dist, 4 * E);
+    return proj_run(c, P, rows, mode, slot, n_points, 0, th, 1, 255, oI, oD, (const uint8_t *) S.dArena.p);
+}
+
+int ygzf_fuse_candidates_resident(ygzf_ctx *c, int n_kf, const ygzf_kf_ref *refs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip, float th,
+                                  int *best_idx, int *best_dist) {
+    return fuse_rows_resident(c, PM_FUSE, true, KK_FUSE, n_kf, refs, n_points, pts, skip, th, best_idx, best_dist);
+}
+
+int ygzf_fuse_sim3_candidates_resident(ygzf_ctx *c, int n_kf, const ygzf_kf_ref *refs, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip,
+                                       float th, int *best_idx, int *best_dist) {
+    return fuse_rows_resident(c, PM_FUSE_SCW, false, KK_PROJ, n_kf, refs, n_points, pts, skip, th, best_idx, best_dist);
 }
 
 int ygzf_search_by_projection_sim3(ygzf_ctx *c, const ygzf_fuse_kf *kf, int n_points, const ygzf_fuse_points *pts, const uint8_t *skip,

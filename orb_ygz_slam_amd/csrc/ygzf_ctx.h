@@ -7,6 +7,7 @@
 //   ygzf_api_detect.hip  Thirdparty/fast replacement, DSO / FAST_KEYPOINT detectors, descriptors of existing keys
 //   ygzf_api_stereo.hip  Frame::ComputeStereoMatches
 //   ygzf_api_kfdb.hip    KeyFrameDatabase: the BowVector store and its query
+//   ygzf_api_kfstore.hip the resident keyframes: put / erase / clear / grid (their searches are in ygzf_api_match.hip beside the non-resident ones)
 #ifndef YGZF_CTX_H
 #define YGZF_CTX_H
 #include <cmath>
@@ -25,10 +26,10 @@
 
 namespace ygzf {
 YGZF_HIDDEN int cv_round_host(double v);
-enum KernelKind { KK_PYR = 0, KK_FAST, KK_OCTREE, KK_DESCRIBE, KK_HAMMING, KK_BACKPROJ, KK_MATCH, KK_SIA, KK_FAST10, KK_DSO, KK_STEREO, KK_DIRECT, KK_BOW, KK_FRUSTUM, KK_DISTINCTIVE, KK_BOWNODES, KK_GRID, KK_FASTQ, KK_TRI, KK_FASTP, KK_FUSE, KK_PROJ, KK_BOWKF, KK_KFDB, KK_COUNT };
+enum KernelKind { KK_PYR = 0, KK_FAST, KK_OCTREE, KK_DESCRIBE, KK_HAMMING, KK_BACKPROJ, KK_MATCH, KK_SIA, KK_FAST10, KK_DSO, KK_STEREO, KK_DIRECT, KK_BOW, KK_FRUSTUM, KK_DISTINCTIVE, KK_BOWNODES, KK_GRID, KK_FASTQ, KK_TRI, KK_FASTP, KK_FUSE, KK_PROJ, KK_BOWKF, KK_KFDB, KK_KFGRID, KK_COUNT };
 // (the KK_FUSE slot keeps the name ygzf_profile_read has always reported for it; it times k_proj_search<PM_FUSE>)
 static const char *kKernelNames[KK_COUNT] = {"k_pyr_resize", "k_fast_tab", "k_octree", "k_describe", "k_hamming_pairs",
-                                             "k_backproject_unit", "k_match_last", "k_sia_run", "k_f10_*", "k_dso_cells", "k_stereo_*", "k_direct_projection", "k_bow_descend", "k_frustum", "k_distinctive", "k_bow_nodes", "k_features_in_area", "k_fast_quads", "k_tri_nodes", "k_fast_tab_persist", "k_fuse", "k_proj_search", "k_bow_kf_nodes", "k_kfdb_query"};
+                                             "k_backproject_unit", "k_match_last", "k_sia_run", "k_f10_*", "k_dso_cells", "k_stereo_*", "k_direct_projection", "k_bow_descend", "k_frustum", "k_distinctive", "k_bow_nodes", "k_features_in_area", "k_fast_quads", "k_tri_nodes", "k_fast_tab_persist", "k_fuse", "k_proj_search", "k_bow_kf_nodes", "k_kfdb_query", "k_kf_grid_build"};
 
 struct Geometry {
     int w = 0, h = 0;
@@ -169,6 +170,26 @@ struct ygzf_ctx {
         std::set<int> freeSlots;                    // reused lowest first
         int dirtyLo = 0, dirtyHi = 0;
     } kfdb;
+    // The resident keyframes (ygzf_api_kfstore.hip).  Buffers of its own, as the database above: no other entry point reads or writes them and
+    // it touches nothing of `held`.  One arena of bytes; a row holds what never changes after a keyframe's construction, in sections aligned
+    // as PackedTransfer aligns them: [keys | descriptors | mvuRight (stereo) | cellStart | list].  Rows are appended at `top`, an erased row
+    // leaves a hole until the arena grows (then the live rows are repacked).  The slot table lives on the host only: a search copies the
+    // slot's FuseKf -- camera, bounds, tables, section offsets relative to the row -- into its row table and adds `off` and the call's pose.
+    struct KfStore {
+        struct Slot {
+            long long off = 0;                      // the row's first byte in the arena
+            size_t bytes = 0;
+            bool live = false, hasSigma = false;    // hasSigma: put with mvInvLevelSigma2 (the first Fuse reads it)
+            FuseKf kf;                              // keys / desc / uRight relative to `off`; Rcw / tcw / Ow unset
+            long long cellStart = 0, list = 0;      // relative to `off`
+        };
+        Buf dArena;
+        size_t cap = 0, top = 0, liveBytes = 0;
+        std::vector<Slot> slots;
+        std::vector<uint64_t> keys;                 // per slot (valid while live)
+        std::unordered_map<uint64_t, int> slotOf;   // live keys
+        std::set<int> freeSlots;                    // reused lowest first
+    } kfs;
     Held held;                             // what the buffers hold between calls (the transitions below ygzf_ctx are its only writers)
     int img0Pitch = 0;
     // timing
@@ -461,5 +482,9 @@ YGZF_HIDDEN int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf);   
 YGZF_HIDDEN int mark_pyramid_done(ygzf_ctx *c);
 YGZF_HIDDEN int run_extract(ygzf_ctx *c, const ygzf::FrameSet &fs, int nFrames, bool pyramidReady = false);
 YGZF_HIDDEN int upload_rows(ygzf_ctx *c, void *dst, size_t dstPitch, const uint8_t *src, size_t srcPitch, int w, size_t rows);
+// ygzf_api_match.hip: a keyframe's argument checks (needSigma: mvInvLevelSigma2 is read) and the pose-free part of its device record
+YGZF_HIDDEN int kf_args_check(ygzf_ctx *c, const ygzf_frame_view &view, const ygzf_camera &cam, const float *inv_level_sigma2, int k, bool needSigma);
+YGZF_HIDDEN void kf_record_static(ygzf_ctx *c, const ygzf_frame_view &view, const ygzf_camera &cam, const float *inv_level_sigma2, float log_scale_factor,
+                                  ygzf::FuseKf &F);
 YGZF_HIDDEN int upload_frames(ygzf_ctx *c, const uint8_t *imgs, int nFrames, int w, int h, int row_pitch, size_t frame_stride, ygzf::FrameSet *fs);
 #endif
