@@ -15,6 +15,7 @@
 
 #include "kernels.h"
 #include "se3_device.h"
+#include "wave_ops.h"
 
 namespace ygzf {
 
@@ -688,9 +689,7 @@ __global__ __launch_bounds__(kSiaBlock) void k_sia_run(SiaArgs A) {
                     for (int w2 = 0; w2 < kSiaBlock / 64; w2++) v += s_red[w2 * kAcc + lane];
                     s_tot[lane] = v;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_handoff();
                 if (DBG) c2 = wall_clock64();
                 // lane 8 i + j: H[i][j] (accumulator of the upper-triangular entry), b[i] for j = 6
                 const int ei = lane >> 3, ej = lane & 7;

@@ -53,12 +53,6 @@ __device__ __forceinline__ float wave_sum_exact(float v) {
 }
 __device__ __forceinline__ float lane_bcast(float v, int lane) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), lane)); }
 
-__device__ __forceinline__ void dir_lds_sync() {   // orders this wave's LDS writes before its later reads by other lanes
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 __global__ __launch_bounds__(64 * kDirWaves) void k_direct_projection(DirectArgs A) {
     __shared__ uint8_t s_pwb[kDirWaves][112];          // _patch_with_border (10 x 10) of this wave's candidate
     __shared__ __attribute__((aligned(16))) float s_prod[kDirWaves][3][64];         // res*dx | res*dy | res per pixel, raster order
@@ -139,7 +133,7 @@ __global__ __launch_bounds__(64 * kDirWaves) void k_direct_projection(DirectArgs
             }
         }
     }
-    dir_lds_sync();
+    wave_lds_handoff();
     // ---- Align2D on cur level sl: lane = pixel (py, px) of the 8 x 8 patch
     const float u0 = A.pxCurr[2 * (size_t) i] * A.invScale[sl], v0 = A.pxCurr[2 * (size_t) i + 1] * A.invScale[sl];
     float u = u0, v = v0;
@@ -181,7 +175,7 @@ __global__ __launch_bounds__(64 * kDirWaves) void k_direct_projection(DirectArgs
             prod[lane] = res * dx;
             prod[64 + lane] = res * dy;
             prod[128 + lane] = res;
-            dir_lds_sync();
+            wave_lds_handoff();
             // lanes 0..2: Jres[lane] -= product[k] for k = 0..63 in raster order (the reference's accumulation order)
             float acc = 0.f;
             if (lane < 3) {
@@ -192,7 +186,7 @@ __global__ __launch_bounds__(64 * kDirWaves) void k_direct_projection(DirectArgs
                     acc -= q.x; acc -= q.y; acc -= q.z; acc -= q.w;
                 }
             }
-            dir_lds_sync();   // the products are consumed before the next iteration overwrites them
+            wave_lds_handoff();   // the products are consumed before the next iteration overwrites them
             const float Jres[3] = {lane_bcast(acc, 0), lane_bcast(acc, 1), lane_bcast(acc, 2)};
             float update[3];
 #pragma unroll

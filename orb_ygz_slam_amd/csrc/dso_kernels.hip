@@ -55,9 +55,7 @@ __global__ __launch_bounds__(64 * kDsoWaves) void k_dso_cells(const uint8_t *__r
         const int r = idx / TS, c = idx - r * TS;
         T[r * kDsoTileP + c] = img[(long long) (y_start - 5 + r) * pitch + x_start - 5 + c];
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
     // fast_corner_detect_10_sse2 domain: cells narrower than 22 px fall to the plain detector, which scans the whole cell
     const int dom0 = grid < 22 ? 0 : 3, D = grid < 22 ? grid : grid - 6, nPix = D * D;
     unsigned long long k0 = 0, k1 = 0, k2 = 0;   // this lane's three best (score rank << 32 | ~raster index); 0 = none

@@ -221,8 +221,6 @@ __device__ void block_radix_sort(unsigned *k0, unsigned *v0, unsigned *k1, unsig
     *rv = v0;
 }
 
-__device__ __forceinline__ void wave_lds_sync();
-
 // ------------------------------------------------------------------------------------------------------------------
 // K1  pyramid level from the previous level: cv::resize INTER_LINEAR, 8UC1, 11-bit fixed point coefficients that the
 // host precomputed exactly as OpenCV does (xofs/ialpha, yofs/ibeta).  One thread per output pixel.
@@ -844,7 +842,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
             }
         }
         if (sampled && lane == 0) { atomicAdd(&st[4], (unsigned) nQ); atomicAdd(&st[5], (unsigned) nquadsAll); atomicAdd(&st[7], 1u); }   // corner-bearing quads / quads / pass-1 runs
-        wave_lds_sync();
+        wave_lds_handoff();
         pc.mark(1);
         pc.bump();
         // ---- expansion: quad list -> corner list (y << 8 | x << 2 | polarity), still raster order ----
@@ -870,11 +868,11 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
             }
             ncorn += add;
         }
-        wave_lds_sync();
+        wave_lds_handoff();
         pc.mark(2);
         // the quad list is consumed: its bytes become the (zeroed) score map
         for (int idx = lane; idx < ((dh + 2) * kSP + 15) / 16; idx += 64) ((uint4 *) smap)[idx] = make_uint4(0, 0, 0, 0);
-        wave_lds_sync();
+        wave_lds_handoff();
         pc.mark(3);
         if (sampled && lane == 0 && !kIniFirst && ncorn > 64) atomicAdd(&st[2], (unsigned) ((min(ncorn, kCornerCap) - 1) >> 6));   // score rounds beyond the first
         int total = 0;          // keypoints this pass keeps
@@ -890,7 +888,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
                 sc = fast9_arc_score(&win[__mul24(y + 3, P) + x + 4], P, e & 3);
                 sp[0] = (uint8_t) sc;
             }
-            wave_lds_sync();
+            wave_lds_handoff();
             pc.mark(4);
             const int fl = have ? nms_flags(sp, iniTh, kSP) : 0;
             bool keep;
@@ -915,7 +913,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
                     smap[(y + 1) * kSP + x + 1] = (uint8_t) fast9_arc_score(&win[(y + 3) * P + x + 4], P, e & 3);
                 }
             }
-            wave_lds_sync();
+            wave_lds_handoff();
             pc.mark(4);
             // 3x3 NMS at both thresholds over the corner list
             int nIni = 0;
@@ -930,7 +928,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
                 }
                 nIni += __popcll(__ballot(fl & 1));
             }
-            wave_lds_sync();
+            wave_lds_handoff();
             // output: the list is in raster order
             const int want = kIniFirst ? 2 : (nIni > 0 ? 1 : 2);
             usedMin = !kIniFirst && nIni == 0;
@@ -963,7 +961,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
                     if (x >= dw) { x -= dw; y++; }
                 }
             }
-            wave_lds_sync();
+            wave_lds_handoff();
             // single-pass plan: sub-pass 0 keeps the iniTh survivors, sub-pass 1 (only if that is empty) the minTh survivors
             for (int sub = kIniFirst ? 1 : 0; sub < 2; sub++) {
                 total = 0;
@@ -996,7 +994,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
             }
             return;
         }
-        wave_lds_sync();   // the next pass reuses the quad list / score map / corner list bytes
+        wave_lds_handoff();   // the next pass reuses the quad list / score map / corner list bytes
     }
 }
 
@@ -1070,7 +1068,7 @@ __device__ __forceinline__ void fast_cell(const FrameSet &fs, const LevelGeom *_
             for (int u = 0; u < kU; u++) ((unsigned *) win)[dst[u]] = __builtin_amdgcn_alignbyte(hi[u], lo[u], sh);
         }
     }
-    wave_lds_sync();
+    wave_lds_handoff();
     PhaseClk pc;   // (the phase clock reports k_fast_tab; here it is only the argument)
     pc.start();
     fast_cell_process<kP, kIniFirst>(win, smap, clist, P, dw, dh, iniTh, minTh, cnt_out,
@@ -1102,7 +1100,7 @@ __global__ __launch_bounds__(kFastBlock) void k_fast_quads(FrameSet fs, const Le
         const int grp = sg * kFastRep + r;
         if (grp >= totalGroups) return;
         fast_cell<kP, kIniFirst>(fs, geom, nlevels, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, winPitch, winRows, smapRows, quadCap, fdyn, grp, f, wv, lane, gb, stats);
-        wave_lds_sync();   // the next cell reuses this wave's LDS region
+        wave_lds_handoff();   // the next cell reuses this wave's LDS region
     }
 }
 
@@ -1164,7 +1162,7 @@ __device__ __forceinline__ void fast_tab_cell(const FrameSet &fs, const FastCell
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
-    wave_lds_sync();
+    wave_lds_handoff();
     pc.mark(0);
     fast_cell_process<P, kIniFirst>(win, smap, clist, P, dw, dh, iniTh, minTh, cnt_out, slots + (long long) f * totalSlots + R.slot, grp, lane, stats, pc);
 }
@@ -1248,7 +1246,7 @@ __global__ __launch_bounds__(256) void k_fast_tab_persist(FrameSet fs, const Fas
         fast_tab_cell<kIniFirst>(fs, cells, (int) rec, (int) f, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, win, winBytes, smapBytes, lane, stats, pc);
         pc.flush(0, lane, item);
         pc.start();
-        wave_lds_sync();                                // the next cell reuses this wave's LDS region
+        wave_lds_handoff();                                // the next cell reuses this wave's LDS region
     }
 }
 
@@ -1694,7 +1692,7 @@ __device__ __forceinline__ void oct_head(const OctLevel &w) {
         }
         n = __builtin_amdgcn_readfirstlane(n);
     }
-    wave_lds_sync();
+    wave_lds_handoff();
     while (n <= 64) {
         const int prevSize = n, nxt = cur ^ 1;
         const OctNodes in = oct_nodes(S, cur);
@@ -1714,7 +1712,7 @@ __device__ __forceinline__ void oct_head(const OctLevel &w) {
                                        (unsigned) __builtin_amdgcn_readlane((int) incl, 63);
         const int sumK = (int) (tot & 0x1FFFFFu);
         if (act) oct_emit(S, oct_nodes(S, nxt), lo, cnt, dep, a1, a2, a3, (int) (ex & 0x1FFFFFu), (int) ((ex >> 21) & 0x1FFFFFu), (int) (ex >> 42), sumK);
-        wave_lds_sync();
+        wave_lds_handoff();
         cur = nxt;
         n = sumK + (int) (tot >> 42);
         nE = (int) ((tot >> 21) & 0x1FFFFFu);
@@ -2163,14 +2161,6 @@ __device__ __forceinline__ int reflect101(int i, int n) {
     return i;
 }
 
-// Orders this wave's LDS writes before its later LDS reads by other lanes (each wave owns a private LDS region, so
-// no block barrier is needed -- and none is allowed: waves of a block may exit early).
-__device__ __forceinline__ void wave_lds_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
 constexpr int kWin = 43, kWinP = 64;    // raw window: one 16-byte aligned 64-byte span per row (+ alignment slack)
 constexpr int kHb = 37, kHbP = 40;      // horizontally blurred: 43 rows x 37 cols (u16), pitch even for 32-bit stores
 constexpr int kBl = 37, kBlP = 40;      // blurred 37x37 (u8)
@@ -2259,7 +2249,7 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
         }
     }
 #define RAWP(r) (&L.rawp()[(r) * kWinP + ((rowOff0 + (r) * rowOffStep) & 15)])
-    wave_lds_sync();
+    wave_lds_handoff();
     pc.mark(0);
     // ---- intensity centroid on the 31x31 disc (centre = window (21,21)).  Work item = four pixels (row v, columns u = 4j-15 .. 4j-12):
     // two aligned dwords shifted into place, masked with the disc membership bytes, then m01 += v * (sum of the bytes) [v_sad_u8] and
@@ -2330,7 +2320,7 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
         unsigned *dst = (unsigned *) &L.hbp()[r * kHbP + 10 * sg];
         dst[0] = O[0]; dst[1] = O[1]; dst[2] = O[2]; dst[3] = O[3]; dst[4] = O[4];
     }
-    wave_lds_sync();
+    wave_lds_handoff();
     pc.mark(3);
     // vertical pass only where the rotated pattern samples (512 points instead of the 37 x 37 patch): 7 taps straight from hb
     float a, b;

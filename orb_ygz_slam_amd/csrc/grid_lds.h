@@ -1,6 +1,8 @@
 // grid_lds.h -- Frame::AssignFeaturesToGrid as one workgroup builds it in LDS (product code, device only).  Shared by the kernels that rebuild
 // a frame's grid on every launch (match_kernels.hip: k_features_in_area, k_proj_search) and the one that builds a resident keyframe's grid once
-// (kfstore_kernels.hip: k_kf_grid_build), so that both forms hold the same lists in the same order.
+// (kfstore_kernels.hip: k_kf_grid_build), so that both forms hold the same lists in the same order.  k_match_last builds the same grid
+// fused with its staging pass (one read of the keys fills the grid counts and the LDS copies of position, level and descriptor) and is
+// therefore not a caller.
 #ifndef YGZF_GRID_LDS_H
 #define YGZF_GRID_LDS_H
 #include "kernels.h"

@@ -3,24 +3,24 @@
 //   k_backproject_unit   bench/test helper: MapPoint world positions = unit-depth back-projection of the Last keypoints
 //   k_match_last         ORBmatcher::SearchByProjection(Frame &Cur, const Frame &Last, th, bMono, checkLevel)
 //                        reference src/ORBmatcher.cc:1218-1350, with Frame::AssignFeaturesToGrid / PosInGrid /
-//                        GetFeaturesInArea (src/Frame.cc:314-330, 483-493, 424-481) and DescriptorDistance (:1507-1523)
+//                        GetFeaturesInArea (src/Frame.cc:314-330, 483-493, 424-481)
 //
 // One workgroup per (Last, Cur) frame pair.  The 64x48 feature grid of Cur is rebuilt in LDS (counting sort, index order
 // inside a cell as the reference's push_back gives); all waves precompute the per-query projection, search radius and
 // level range; then ONE wave walks the Last keypoints in index order -- the reference's loop carries state through
 // Cur.mvpMapPoints ("already owned" test, :1292-1294), so acceptance must be resolved in order -- with its 64 lanes
-// spread over the grid cells of the search window, Hamming distances by __popcll on 4 x u64 from LDS-resident
-// descriptors, and a (distance, candidate order) key min-reduced across the wave so that ties break exactly like the
-// reference's strict `dist < bestDist` scan.  Rotation-histogram voting (:1315-1345, including the factor = 1/30 quirk)
-// is applied at the end.  Float expressions are evaluated in source order (library built with -ffp-contract=off).
+// spread over the grid cells of the search window, descriptors LDS-resident, and a (distance, candidate order) key
+// min-reduced across the wave so that ties break exactly like the reference's strict `dist < bestDist` scan.
+// Rotation-histogram voting (:1315-1345) is applied at the end.  Float expressions are evaluated in source order (library built with
+// -ffp-contract=off).
+// The reference's small rules -- descriptor distance, rotation bin, ComputeThreeMaxima, the GetFeaturesInArea cell window, the accept rule
+// of mode 1 -- are match_rules.h's, for every kernel of this file.
 #include "kernels.h"
 #include "wave_ops.h"
 #include "grid_lds.h"   // GRID_COLS / GRID_ROWS / GRID_CELLS, kMatchBlock, build_grid_lds
+#include "match_rules.h"
 
 namespace ygzf {
-
-constexpr int TH_HIGH = 100;
-constexpr int HISTO_LENGTH = 30;
 
 __device__ __forceinline__ int m_lane() { return threadIdx.x & 63; }
 
@@ -213,7 +213,7 @@ __device__ __forceinline__ void for_each_candidate(const MatchArgs &A, const Mat
             const unsigned long long *d = (const unsigned long long *) (curDesc + (size_t) i2 * 32);
             d0 = d[0]; d1 = d[1]; d2 = d[2]; d3 = d[3];
         }
-        const unsigned dist = __popcll(q0 ^ d0) + __popcll(q1 ^ d1) + __popcll(q2 ^ d2) + __popcll(q3 ^ d3);
+        const unsigned dist = hamming256(q0, q1, q2, q3, d0, d1, d2, d3);
         if (matchedDist && matchedDist[i2] <= (int) dist) continue;   // SearchForInitialization :414-415
         visit((dist << 16) | (unsigned) j, i2);
     }
@@ -554,16 +554,12 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
             if (lk.octave <= 0) {
                 const float u = pX, v = pY;
                 const float rad = A.th;
-                const int nMinCellX = max(0, (int) floorf((u - A.minX - rad) * A.gridInvW));
-                const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((u - A.minX + rad) * A.gridInvW));
-                const int nMinCellY = max(0, (int) floorf((v - A.minY - rad) * A.gridInvH));
-                const int nMaxCellY = min(GRID_ROWS - 1, (int) ceilf((v - A.minY + rad) * A.gridInvH));
-                if (!(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0) && nMaxCellX >= nMinCellX &&
-                    nMaxCellY >= nMinCellY) {
+                const CellWindow w = cell_window(u, v, rad, A.minX, A.minY, A.gridInvW, A.gridInvH);
+                if (!w.empty) {
                     q.valid = 1;
                     q.u = u; q.v = v; q.radius = rad; q.angle = lk.angle;
-                    q.minCx = (unsigned char) nMinCellX; q.maxCx = (unsigned char) nMaxCellX;
-                    q.minCy = (unsigned char) nMinCellY; q.maxCy = (unsigned char) nMaxCellY;
+                    q.minCx = (unsigned char) w.minCx; q.maxCx = (unsigned char) w.maxCx;
+                    q.minCy = (unsigned char) w.minCy; q.maxCy = (unsigned char) w.maxCy;
                     q.minLevel = (signed char) lk.octave; q.maxLevel = (signed char) lk.octave;
                 }
             }
@@ -581,17 +577,13 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 }
                 const float u = pX, v = pY;
                 const float rad = r * A.scaleFactors[lvl];
-                const int nMinCellX = max(0, (int) floorf((u - A.minX - rad) * A.gridInvW));
-                const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((u - A.minX + rad) * A.gridInvW));
-                const int nMinCellY = max(0, (int) floorf((v - A.minY - rad) * A.gridInvH));
-                const int nMaxCellY = min(GRID_ROWS - 1, (int) ceilf((v - A.minY + rad) * A.gridInvH));
-                if (!(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0) && nMaxCellX >= nMinCellX &&
-                    nMaxCellY >= nMinCellY) {
+                const CellWindow w = cell_window(u, v, rad, A.minX, A.minY, A.gridInvW, A.gridInvH);
+                if (!w.empty) {
                     q.valid = 1;
                     q.u = u; q.v = v; q.radius = rad;
                     q.ur = A.mpProjXR ? pXR : 0.f;
-                    q.minCx = (unsigned char) nMinCellX; q.maxCx = (unsigned char) nMaxCellX;
-                    q.minCy = (unsigned char) nMinCellY; q.maxCy = (unsigned char) nMaxCellY;
+                    q.minCx = (unsigned char) w.minCx; q.maxCx = (unsigned char) w.maxCx;
+                    q.minCy = (unsigned char) w.minCy; q.maxCy = (unsigned char) w.maxCy;
                     if (A.mode == 2) {
                         q.minLevel = (signed char) (lvl - 1); q.maxLevel = (signed char) (lvl + 1);
                         q.angle = pAng;
@@ -620,17 +612,12 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     else if (bForward) { minL = oct; maxL = -1; }
                     else if (bBackward) { minL = 0; maxL = oct; }
                     else { minL = oct - 1; maxL = oct + 1; }
-                    // GetFeaturesInArea cell window (src/Frame.cc:429-447)
-                    const int nMinCellX = max(0, (int) floorf((u - A.minX - r) * A.gridInvW));
-                    const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((u - A.minX + r) * A.gridInvW));
-                    const int nMinCellY = max(0, (int) floorf((v - A.minY - r) * A.gridInvH));
-                    const int nMaxCellY = min(GRID_ROWS - 1, (int) ceilf((v - A.minY + r) * A.gridInvH));
-                    if (!(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0) &&
-                        nMaxCellX >= nMinCellX && nMaxCellY >= nMinCellY) {
+                    const CellWindow w = cell_window(u, v, r, A.minX, A.minY, A.gridInvW, A.gridInvH);
+                    if (!w.empty) {
                         q.valid = 1;
                         q.u = u; q.v = v; q.radius = r; q.ur = u - A.mbf * invzc; q.angle = lk.angle;
-                        q.minCx = (unsigned char) nMinCellX; q.maxCx = (unsigned char) nMaxCellX;
-                        q.minCy = (unsigned char) nMinCellY; q.maxCy = (unsigned char) nMaxCellY;
+                        q.minCx = (unsigned char) w.minCx; q.maxCx = (unsigned char) w.maxCx;
+                        q.minCy = (unsigned char) w.minCy; q.maxCy = (unsigned char) w.maxCy;
                         q.minLevel = (signed char) minL; q.maxLevel = (signed char) maxL;
                     }
                 }
@@ -675,7 +662,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     const unsigned long long *d = (const unsigned long long *) (curDesc + (size_t) i2 * 32);
                     d0 = d[0]; d1 = d[1]; d2 = d[2]; d3 = d[3];
                 }
-                const unsigned dist = __popcll(q0 ^ d0) + __popcll(q1 ^ d1) + __popcll(q2 ^ d2) + __popcll(q3 ^ d3);
+                const unsigned dist = hamming256(q0, q1, q2, q3, d0, d1, d2, d3);
                 if ((A.mode == 0 || A.mode == 2) && dist > (unsigned) A.maxDist) ok = false;   // modes 1, 3 need the runner-up even when it is far
                 return ok ? ((dist << 16) | (ord & 0xFFFFu)) : 0xFFFFFFFFu;
             };
@@ -862,11 +849,10 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     pick = b1;                           // modes 0 / 2: every list entry is acceptable (dist <= maxDist)
                 } else {
                     pick = -1;
-                    const int bestDist = (int) (k1 >> 16);
-                    if (b1 >= 0 && bestDist <= TH_HIGH) {
+                    if (b1 >= 0) {
                         const int bestDist2 = (int) (k2 >> 16);      // 256 when there is no runner-up
-                        const int bestLevel = L.octave[b1], bestLevel2 = (b2 >= 0 && bestDist2 < 256) ? (int) L.octave[b2] : -1;
-                        if (!(bestLevel == bestLevel2 && (float) bestDist > A.nnratio * (float) bestDist2)) pick = b1;
+                        const int bestLevel2 = (b2 >= 0 && bestDist2 < 256) ? (int) L.octave[b2] : -1;
+                        if (accepts_best_of_two((int) (k1 >> 16), L.octave[b1], bestDist2, bestLevel2, A.nnratio)) pick = b1;
                     }
                 }
                 if (pick != choiceOf[i]) { choiceOf[i] = pick; changed = 1; }
@@ -929,7 +915,6 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
             if (tid == 0) { s_tmp[16] = 0; s_tmp[17] = 0; }
             __syncthreads();
             const bool doOri = A.checkOri != 0 && !two;
-            const float factor = 1.0f / HISTO_LENGTH;
             int mine = 0;
             for (int i = tid; i < nq; i += kMatchBlock) {
                 const int ch = choiceOf[i];
@@ -937,10 +922,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 atomicMax(&L.match[ch], i);
                 mine++;
                 if (doOri) {
-                    float rot = L.qang[i] - L.cang[ch];
-                    if (rot < 0.0) rot += 360.0f;
-                    int bin = (int) roundf(rot * factor);
-                    if (bin == HISTO_LENGTH) bin = 0;
+                    const int bin = rot_bin(L.qang[i], L.cang[ch]);
                     atomicAdd(&s_hist[bin], 1);
                     choiceOf[i] = (bin << 24) | ch;
                 }
@@ -956,22 +938,13 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
             }
             __syncthreads();
             if (doOri) {
-                int ind1 = -1, ind2 = -1, ind3 = -1;
-                int max1 = 0, max2 = 0, max3 = 0;
-                for (int b = 0; b < HISTO_LENGTH; b++) {
-                    const int sc = s_hist[b];
-                    if (sc > max1) { max3 = max2; max2 = max1; max1 = sc; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                    else if (sc > max2) { max3 = max2; max2 = sc; ind3 = ind2; ind2 = b; }
-                    else if (sc > max3) { max3 = sc; ind3 = b; }
-                }
-                if (max2 < 0.1f * (float) max1) { ind2 = -1; ind3 = -1; }
-                else if (max3 < 0.1f * (float) max1) { ind3 = -1; }
+                const ThreeMaxima top = three_maxima(s_hist);
                 int removed = 0;
                 for (int i = tid; i < nq; i += kMatchBlock) {
                     const int ev = choiceOf[i];
                     if (ev < 0) continue;
                     const int bin = ev >> 24, idx = ev & 0xFFFFFF;
-                    if (bin != ind1 && bin != ind2 && bin != ind3) {
+                    if (bin != top.ind1 && bin != top.ind2 && bin != top.ind3) {
                         L.owner[idx] = 0;
                         L.match[idx] = -2;
                         removed++;
@@ -993,7 +966,6 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
     // ---- in-order resolution by one wave.  Only LDS is touched inside the loop (a global store followed by the
     // ordering the next iteration needs would cost a full memory round trip per query).
     int nmatches = 0, nEvents = 0, nRescan = 0;
-    const float factor = 1.0f / HISTO_LENGTH;
     volatile unsigned char *vowner = L.owner;
     const bool doOri = A.checkOri && (A.mode == 0 || A.mode == 2);
     const unsigned long long lane_lt = (1ull << lane) - 1ull;
@@ -1008,9 +980,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
         volatile int *v12 = L.events;
         for (int i = lane; i < nt; i += 64) vdist[i] = 0x7FFFFFFF;
         for (int i = lane; i < nq; i += 64) v12[i] = -1;
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+        wave_lds_handoff();
         const int TH_LOW = 50;
         for (int i = 0; i < nq; i++) {
             const uint4 keys = L.specKey[i];
@@ -1041,10 +1011,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
             const int old = v21[b1];
             if (old >= 0) nmatches--;
             nmatches++;
-            float rot = L.qang[i] - L.cang[b1];
-            if (rot < 0.0) rot += 360.0f;
-            int bin = (int) roundf(rot * factor);
-            if (bin == HISTO_LENGTH) bin = 0;
+            const int bin = rot_bin(L.qang[i], L.cang[b1]);
             if (lane == 0) {
                 if (old >= 0) v12[old] = -1;
                 v12[i] = (bin << 24) | b1;
@@ -1052,22 +1019,10 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 vdist[b1] = bestDist;
                 if (A.checkOri) s_hist[bin]++;
             }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            wave_lds_handoff();
         }
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        if (A.checkOri) {
-            int max1 = 0, max2 = 0, max3 = 0;
-            for (int b = 0; b < HISTO_LENGTH; b++) {
-                const int s = s_hist[b];
-                if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-                else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-                else if (s > max3) { max3 = s; ind3 = b; }
-            }
-            if (max2 < 0.1f * (float) max1) { ind2 = -1; ind3 = -1; }
-            else if (max3 < 0.1f * (float) max1) { ind3 = -1; }
-        }
+        ThreeMaxima top = {-1, -1, -1};
+        if (A.checkOri) top = three_maxima(s_hist);
         int removed = 0;
         int *m12 = A.match12 + (long long) pair * A.kpStrideLast;
         for (int i = lane; i < nq; i += 64) {
@@ -1076,7 +1031,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
             if (ev >= 0) {
                 const int bin = ev >> 24;
                 m = ev & 0xFFFFFF;
-                if (A.checkOri && bin != ind1 && bin != ind2 && bin != ind3) { m = -1; removed++; }
+                if (A.checkOri && bin != top.ind1 && bin != top.ind2 && bin != top.ind3) { m = -1; removed++; }
             }
             m12[i] = m;
         }
@@ -1133,17 +1088,11 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 const bool rescan = pending && exhausted;
                 bool take = false;            // the query passes the accept rule with these picks
                 if (pending && !rescan && b1 >= 0) {
-                    const int bestDist = (int) (k1 >> 16);
-                    if (bestDist <= TH_HIGH) {
-                        const int bestDist2 = (int) (k2 >> 16);      // 256 when there is no runner-up
-                        const int bestLevel = l1, bestLevel2 = (b2 >= 0 && bestDist2 < 256) ? l2 : -1;
-                        take = !(bestLevel == bestLevel2 && (float) bestDist > A.nnratio * (float) bestDist2);
-                    }
+                    const int bestDist2 = (int) (k2 >> 16);      // 256 when there is no runner-up
+                    take = accepts_best_of_two((int) (k1 >> 16), l1, bestDist2, (b2 >= 0 && bestDist2 < 256) ? l2 : -1, A.nnratio);
                 }
                 if (take && obs) atomicMin((int *) &vclaim[b1], lane);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_handoff();
                 const bool conflict = pending && (rescan || (b1 >= 0 && vclaim[b1] < lane) || (b2 >= 0 && vclaim[b2] < lane));
                 __builtin_amdgcn_wave_barrier();
                 if (take && obs) vclaim[b1] = 64;
@@ -1173,9 +1122,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 // the first conflicting lane with an exhausted list: cooperative rescan against the current ownership
                 const bool firstRescan = first < 64 && __builtin_amdgcn_readlane((int) rescan, first) != 0;
                 if (firstRescan) {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_handoff();
                     const int qi = tile + first;
                     const QueryParam q = load_qp(&L.qp[qi]);
                     const unsigned long long *qd = (const unsigned long long *) (mpDesc + (size_t) qi * 32);
@@ -1183,11 +1130,10 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     unsigned s2 = kNoKey;
                     const unsigned s1 = scan_query(A, L, q, qd[0], qd[1], qd[2], qd[3], curDesc, uRight, lane, &c1, &s2, &c2);
                     nRescan++;
-                    const int bestDist = (int) (s1 >> 16);
-                    if (c1 >= 0 && bestDist <= TH_HIGH) {
+                    if (c1 >= 0) {
                         const int bestDist2 = (int) (s2 >> 16);
-                        const int bestLevel = L.octave[c1], bestLevel2 = (c2 >= 0 && bestDist2 < 256) ? L.octave[c2] : -1;
-                        if (!(bestLevel == bestLevel2 && (float) bestDist > A.nnratio * (float) bestDist2)) {
+                        const int bestLevel2 = (c2 >= 0 && bestDist2 < 256) ? L.octave[c2] : -1;
+                        if (accepts_best_of_two((int) (s1 >> 16), L.octave[c1], bestDist2, bestLevel2, A.nnratio)) {
                             const int qobs = L.qobs[qi];
                             if (lane == 0) { vowner[c1] = qobs ? 2 : 1; L.match[c1] = qi; }
                             nmatches++;
@@ -1195,9 +1141,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     }
                     if (lane == first) pending = false;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_handoff();
             }
         }
     } else {
@@ -1231,9 +1175,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     else rescan = true;
                 }
                 if (pending && choice >= 0 && obs) atomicMin((int *) &vclaim[choice], lane);
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_handoff();
                 const bool conflict = pending && (rescan || (choice >= 0 && vclaim[choice] < lane));
                 __builtin_amdgcn_wave_barrier();
                 if (pending && choice >= 0 && obs) vclaim[choice] = 64;
@@ -1257,10 +1199,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                         }
                     }
                     if (doOri && commit) {
-                        float rot = L.qang[i] - L.cang[choice];
-                        if (rot < 0.0) rot += 360.0f;
-                        int bin = (int) roundf(rot * factor);
-                        if (bin == HISTO_LENGTH) bin = 0;
+                        const int bin = rot_bin(L.qang[i], L.cang[choice]);
                         L.events[nEvents + __popcll(mcommit & lane_lt)] = (bin << 24) | choice;
                     }
                     const int nc = __popcll(mcommit);
@@ -1271,9 +1210,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 // the first conflicting lane with an exhausted list: cooperative rescan against the current ownership
                 const bool firstRescan = first < 64 && __builtin_amdgcn_readlane((int) rescan, first) != 0;
                 if (firstRescan) {
-                    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                    __builtin_amdgcn_wave_barrier();
-                    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                    wave_lds_handoff();
                     const int qi = tile + first;
                     const QueryParam q = load_qp(&L.qp[qi]);
                     const unsigned long long *qd = (const unsigned long long *) (mpDesc + (size_t) qi * 32);
@@ -1283,10 +1220,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     if ((int) (key >> 16) <= A.maxDist) {
                         if (lane == first) { vowner[b] = obs ? 2 : 1; L.match[b] = qi; }
                         if (doOri) {
-                            float rot = L.qang[qi] - L.cang[b];
-                            if (rot < 0.0) rot += 360.0f;
-                            int bin = (int) roundf(rot * factor);
-                            if (bin == HISTO_LENGTH) bin = 0;
+                            const int bin = rot_bin(L.qang[qi], L.cang[b]);
                             if (lane == 0) L.events[nEvents] = (bin << 24) | b;
                             nEvents++;
                         }
@@ -1294,37 +1228,22 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     }
                     if (lane == first) pending = false;
                 }
-                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-                __builtin_amdgcn_wave_barrier();
-                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+                wave_lds_handoff();
             }
         }
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
     STAMP(4);
     // ---- rotation consistency (:1327-1345) + ComputeThreeMaxima (:1471-1502) ----
     if (doOri) {
         for (int e = lane; e < nEvents; e += 64) atomicAdd(&s_hist[L.events[e] >> 24], 1);
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        int ind1 = -1, ind2 = -1, ind3 = -1;
-        int max1 = 0, max2 = 0, max3 = 0;
-        for (int b = 0; b < HISTO_LENGTH; b++) {
-            const int s = s_hist[b];
-            if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-            else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-            else if (s > max3) { max3 = s; ind3 = b; }
-        }
-        if (max2 < 0.1f * (float) max1) { ind2 = -1; ind3 = -1; }
-        else if (max3 < 0.1f * (float) max1) { ind3 = -1; }
+        wave_lds_handoff();
+        const ThreeMaxima top = three_maxima(s_hist);
         int removed = 0;
         for (int e = lane; e < nEvents; e += 64) {
             const int ev = L.events[e];
             const int bin = ev >> 24, idx = ev & 0xFFFFFF;
-            if (bin != ind1 && bin != ind2 && bin != ind3) {
+            if (bin != top.ind1 && bin != top.ind2 && bin != top.ind3) {
                 L.owner[idx] = 0;
                 L.match[idx] = -2;
                 removed++;
@@ -1333,9 +1252,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
         removed = wave_sum(removed);
         nmatches -= removed;
     }
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_handoff();
     for (int i = lane; i < nt; i += 64) { ownerOut[i] = L.owner[i]; matchOut[i] = L.match[i]; }
     if (lane == 0) A.nmatches[pair] = nmatches;
     if (lane == 0 && nRescan && A.matchStat) atomicAdd(A.matchStat + kMatchStatRescans, (unsigned) nRescan);
@@ -1362,7 +1279,6 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int nNodes, const int *__rest
     if (node >= nNodes) return;
     const int f0 = fOff[node], nF = fOff[node + 1] - f0;
     const int rounds = (nF + 63) >> 6;
-    const float factor = 1.0f / HISTO_LENGTH;
     const int TH_LOW = 50;
     unsigned long long taken = 0;   // bit r: this lane's candidate of round r (position r*64 + lane) already carries a match
     int count = 0;
@@ -1377,7 +1293,7 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int nNodes, const int *__rest
                 const int b = r * 64 + lane;
                 if (b >= nF || ((taken >> r) & 1ull)) continue;
                 const unsigned long long *d = (const unsigned long long *) (fDesc + (size_t) fIdx[f0 + b] * 32);
-                const unsigned dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+                const unsigned dist = hamming256(q0, q1, q2, q3, d);
                 const unsigned key = (dist << 16) | (unsigned) b;
                 if (key < best) { best2 = best; best = key; }
                 else if (key < best2) best2 = key;
@@ -1396,10 +1312,7 @@ __global__ __launch_bounds__(256) void k_bow_nodes(int nNodes, const int *__rest
             const int iF = fIdx[f0 + b];
             match[iF] = iKF;
             if (checkOri) {
-                float rot = kfKeys[iKF].angle - fKeys[iF].angle;
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int) roundf(rot * factor);
-                if (bin == HISTO_LENGTH) bin = 0;
+                const int bin = rot_bin(kfKeys[iKF].angle, fKeys[iF].angle);
                 binOf[iF] = (unsigned char) bin;
                 atomicAdd(&hist[bin], 1);
             }
@@ -1415,21 +1328,12 @@ __device__ __forceinline__ void bow_finish(int nF, int *__restrict__ match, cons
     __shared__ int s_removed;
     if (threadIdx.x == 0) s_removed = 0;
     __syncthreads();
-    int ind1 = -1, ind2 = -1, ind3 = -1;
-    int max1 = 0, max2 = 0, max3 = 0;
-    for (int b = 0; b < HISTO_LENGTH; b++) {   // ComputeThreeMaxima :1471-1502
-        const int s = hist[b];
-        if (s > max1) { max3 = max2; max2 = max1; max1 = s; ind3 = ind2; ind2 = ind1; ind1 = b; }
-        else if (s > max2) { max3 = max2; max2 = s; ind3 = ind2; ind2 = b; }
-        else if (s > max3) { max3 = s; ind3 = b; }
-    }
-    if (max2 < 0.1f * (float) max1) { ind2 = -1; ind3 = -1; }
-    else if (max3 < 0.1f * (float) max1) { ind3 = -1; }
+    const ThreeMaxima top = three_maxima(hist);
     int removed = 0;
     for (int i = threadIdx.x; i < nF; i += blockDim.x) {
         if (match[i] < 0) continue;
         const int bin = binOf[i];
-        if (bin != ind1 && bin != ind2 && bin != ind3) { match[i] = -2; removed++; }
+        if (bin != top.ind1 && bin != top.ind2 && bin != top.ind3) { match[i] = -2; removed++; }
     }
     if (removed) atomicAdd(&s_removed, removed);
     __syncthreads();
@@ -1482,7 +1386,6 @@ __global__ __launch_bounds__(256) void k_bow_kf_nodes(BowKfArgs A) {
     const int f0 = off2[node], nF = off2[node + 1] - f0;
     const int rounds = (nF + 63) >> 6;
     if (rounds > 64) return;        // (the entry point refuses such a node)
-    const float factor = 1.0f / HISTO_LENGTH;
     const int TH_LOW = 50;
     unsigned long long taken = 0;   // bit r: this lane's KF2 feature of round r (position r * 64 + lane) is in vbMatched2
     unsigned long long c0 = 0, c1 = 0, c2 = 0, c3 = 0;
@@ -1502,14 +1405,14 @@ __global__ __launch_bounds__(256) void k_bow_kf_nodes(BowKfArgs A) {
         const unsigned long long *qd = (const unsigned long long *) (A.desc1 + (size_t) i1 * 32);
         const unsigned long long q0 = qd[0], q1 = qd[1], q2 = qd[2], q3 = qd[3];
         unsigned best = (256u << 16) | 0xFFFFu, best2 = (256u << 16) | 0xFFFFu;
-        if (ok0 && !(taken & 1ull)) best = ((unsigned) (__popcll(q0 ^ c0) + __popcll(q1 ^ c1) + __popcll(q2 ^ c2) + __popcll(q3 ^ c3)) << 16) | (unsigned) lane;
+        if (ok0 && !(taken & 1ull)) best = (hamming256(q0, q1, q2, q3, c0, c1, c2, c3) << 16) | (unsigned) lane;
         for (int r = 1; r < rounds; r++) {
             const int b = r * 64 + lane;
             if (b >= nF || ((taken >> r) & 1ull)) continue;
             const int i2 = idx2[f0 + b];
             if (!valid2[i2]) continue;                             // :529-533
             const unsigned long long *d = (const unsigned long long *) (desc2 + (size_t) i2 * 32);
-            const unsigned dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+            const unsigned dist = hamming256(q0, q1, q2, q3, d);
             const unsigned key = (dist << 16) | (unsigned) b;
             if (key < best) { best2 = best; best = key; }
             else if (key < best2) best2 = key;
@@ -1527,10 +1430,7 @@ __global__ __launch_bounds__(256) void k_bow_kf_nodes(BowKfArgs A) {
             const int i2 = idx2[f0 + b];
             match12[i1] = i2;
             if (A.checkOri) {
-                float rot = A.keys1[i1].angle - keys2[i2].angle;   // :554-559
-                if (rot < 0.0) rot += 360.0f;
-                int bin = (int) roundf(rot * factor);
-                if (bin == HISTO_LENGTH) bin = 0;
+                const int bin = rot_bin(A.keys1[i1].angle, keys2[i2].angle);   // :554-559
                 binOf[i1] = (unsigned char) bin;
                 atomicAdd(&tail[4 + bin], 1);
             }
@@ -1593,7 +1493,7 @@ __global__ __launch_bounds__(256) void k_tri_nodes(TriArgs A) {
             const bool stereo2 = A.uR2 && A.uR2[i2] >= 0;
             if (A.onlyStereo && !stereo2) continue;
             const unsigned long long *d = (const unsigned long long *) (A.desc2 + (size_t) i2 * 32);
-            const int dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+            const int dist = hamming256(q0, q1, q2, q3, d);
             if (dist > TH_LOW) continue;
             const ygzf_kp kp2 = A.keys2[i2];
             if (!stereo1 && !stereo2) {
@@ -1615,10 +1515,7 @@ __global__ __launch_bounds__(256) void k_tri_nodes(TriArgs A) {
     A.match12[i1] = i2;
     atomicAdd(A.nmatches, 1);
     if (A.checkOri) {
-        float rot = kp1.angle - A.keys2[i2].angle;
-        if (rot < 0.0) rot += 360.0f;
-        int bin = (int) roundf(rot * (1.0f / HISTO_LENGTH));
-        if (bin == HISTO_LENGTH) bin = 0;
+        const int bin = rot_bin(kp1.angle, A.keys2[i2].angle);
         A.binOf[i1] = (unsigned char) bin;
         atomicAdd(&A.hist[bin], 1);
     }
@@ -1706,7 +1603,7 @@ __global__ __launch_bounds__(256) void k_distinctive(int nPoints, const int *__r
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             const int j = r * 64 + lane;
-            dist[r] = (r < per && j < N) ? (int) (__popcll(q0 ^ d[r][0]) + __popcll(q1 ^ d[r][1]) + __popcll(q2 ^ d[r][2]) + __popcll(q3 ^ d[r][3])) : 1 << 20;
+            dist[r] = (r < per && j < N) ? (int) hamming256(q0, q1, q2, q3, d[r]) : 1 << 20;
         }
         // smallest value m with #{dist <= m} > k
         int lo = 0, hi = 256;
@@ -1743,7 +1640,7 @@ __global__ __launch_bounds__(256) void k_distinctive_large(int nLarge, const int
         const unsigned long long q0 = qi[0], q1 = qi[1], q2 = qi[2], q3 = qi[3];
         for (int j = lane; j < N; j += 64) {
             const unsigned long long *d = (const unsigned long long *) (desc + (size_t) (o0 + j) * 32);
-            atomicAdd(&hist[__popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3])], 1);
+            atomicAdd(&hist[hamming256(q0, q1, q2, q3, d)], 1);
         }
         __builtin_amdgcn_wave_barrier();
         // smallest value m with #{dist <= m} > k: lane l sums bins 5 l .. 5 l + 4 (257 bins over 52 lanes), wave prefix, then the lane whose run crosses k
@@ -1801,7 +1698,7 @@ __global__ __launch_bounds__(256) void k_bow_descend(int n, const uint8_t *__res
             if (base + lane < nc) {
                 const int id = childIdx[c0 + base + lane];
                 const unsigned long long *d = (const unsigned long long *) (nodeDesc + (size_t) id * 32);
-                const unsigned dist = (unsigned) (__popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]));
+                const unsigned dist = hamming256(q0, q1, q2, q3, d);
                 key = ((unsigned long long) dist << 32) | (unsigned) (base + lane);
             }
             const unsigned long long m = ~wave_max_u64(~key);   // minimum
@@ -1845,15 +1742,13 @@ __global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
         const int minLevel = A.levels ? A.levels[2 * q] : -1, maxLevel = A.levels ? A.levels[2 * q + 1] : -1;
         int *out = A.outIdx + (long long) q * A.cap;
         int total = 0;
-        const int nMinCellX = max(0, (int) floorf((x - A.minX - r) * A.gridInvW));
-        const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((x - A.minX + r) * A.gridInvW));
-        const int nMinCellY = max(0, (int) floorf((y - A.minY - r) * A.gridInvH));
-        const int nMaxCellY = min(GRID_ROWS - 1, (int) ceilf((y - A.minY + r) * A.gridInvH));
-        if (!(nMinCellX >= GRID_COLS || nMaxCellX < 0 || nMinCellY >= GRID_ROWS || nMaxCellY < 0)) {
+        // the bounds are cell_window's; not its `empty`: differs because the row test sits inside the column loop (the loops of src/Frame.cc:451-452 visit no cell then)
+        const CellWindow w = cell_window(x, y, r, A.minX, A.minY, A.gridInvW, A.gridInvH);
+        if (!(w.minCx >= GRID_COLS || w.maxCx < 0 || w.minCy >= GRID_ROWS || w.maxCy < 0)) {
             const bool bCheckLevels = (minLevel > 0) || (maxLevel >= 0);
-            for (int ix = nMinCellX; ix <= nMaxCellX; ix++) {
-                if (nMinCellY > nMaxCellY) break;
-                const int s = cellStart[ix * GRID_ROWS + nMinCellY], e = cellStart[ix * GRID_ROWS + nMaxCellY + 1];
+            for (int ix = w.minCx; ix <= w.maxCx; ix++) {
+                if (w.minCy > w.maxCy) break;
+                const int s = cellStart[ix * GRID_ROWS + w.minCy], e = cellStart[ix * GRID_ROWS + w.maxCy + 1];
                 for (int base = s; base < e; base += 64) {
                     const int j = base + lane;
                     bool ok = false;
@@ -1984,6 +1879,7 @@ __device__ __forceinline__ void proj_search_point(const FuseKf &K, const float *
         int pred = 0;
         for (int k = 1; k < K.nLevels; k++) pred += (ratio >= K.levelStep[k]) ? 1 : 0;
         const float r = th * K.scale[pred];
+        // not cell_window: differs because each bound is tested as soon as it is known, as src/KeyFrame.cc:778-792 returns between them
         const int nMinCellX = max(0, (int) floorf((u - K.minX - r) * K.gridInvW));
         if (nMinCellX >= GRID_COLS) break;
         const int nMaxCellX = min(GRID_COLS - 1, (int) ceilf((u - K.minX + r) * K.gridInvW));
@@ -2022,7 +1918,7 @@ __device__ __forceinline__ void proj_search_point(const FuseKf &K, const float *
                         }
                     }
                     const uint64_t *d = (const uint64_t *) (kdesc + 32 * (size_t) idx);
-                    const unsigned dist = __popcll(d[0] ^ m0) + __popcll(d[1] ^ m1) + __popcll(d[2] ^ m2) + __popcll(d[3] ^ m3);
+                    const unsigned dist = hamming256(d[0], d[1], d[2], d[3], m0, m1, m2, m3);
                     if ((int) dist > maxHamming) continue;   // maxHamming <= 255: never below the initial bestDist = 256
                     const unsigned key = (dist << 16) | (unsigned) (ord + lane);
                     if (MODE == PM_PROJ_SCW && pass > 0 && key <= prev) continue;

@@ -14,6 +14,7 @@
 // exactly (|sum| <= 121 * 510), evaluated here in int32.  Float expressions keep source order (library built -ffp-contract=off).
 #include "kernels.h"
 #include "wave_ops.h"
+#include "match_rules.h"   // hamming256
 
 namespace ygzf {
 
@@ -121,7 +122,7 @@ __global__ __launch_bounds__(256) void k_stereo_match(StereoArgs A) {
             if (oct < levelL - 1 || oct > levelL + 1) continue;
             if (!(rc.x >= minU && rc.x <= maxU)) continue;
             const unsigned long long *d = (const unsigned long long *) (descR + (long long) iR * 32);
-            const unsigned dist = __popcll(q0 ^ d[0]) + __popcll(q1 ^ d[1]) + __popcll(q2 ^ d[2]) + __popcll(q3 ^ d[3]);
+            const unsigned dist = hamming256(q0, q1, q2, q3, d);
             const unsigned key = (dist << 16) | (unsigned) iR;
             best = key < best ? key : best;
         }

@@ -80,5 +80,13 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     return r;
 }
 
+// LDS hand-off inside one wave: orders this wave's LDS writes before its later LDS reads by other lanes.  Where each wave works on LDS of its
+// own no block barrier is needed -- and none is allowed where waves of a block may exit early.
+__device__ __forceinline__ void wave_lds_handoff() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 }  // namespace ygzf
 #endif
