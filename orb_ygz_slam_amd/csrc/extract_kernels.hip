@@ -1389,7 +1389,7 @@ template <int kBlock> __device__ __forceinline__ void oct_empty_level(const OctA
     for (int i = w.tid; i < w.g.kpCap; i += kBlock) a.procRec[(long long) w.f * a.kpStride + w.g.kpBase + i] = make_uint2(0u, kNoKeypoint);
 }
 
-// ---- LDS carve-up ----
+// ---- LDS carve-up (the sizes it must match: octree_lds_bytes / octree_lds_cand / octree_hist_lds_bytes, ygzf_plan.hip) ----
 template <bool kGlobalNodes, bool kHist> __device__ __forceinline__ void oct_carve(const OctArgs &a, OctLevel &w, int *dyn) {
     OctShared &S = w.S;
     const int cap = a.cap;
@@ -2749,23 +2749,7 @@ void launch_fast_tab_persist(hipStream_t st, const FrameSet &fs, const FastCellR
                            totalItems, perXcd, winRows, smapRows, quadCap, stats, counters);
 }
 
-size_t octree_lds_bytes(int maxCellsPerLevel, int cap, int ldsCand, bool globalNodes) {
-    if (globalNodes) return sizeof(int) * ((size_t) maxCellsPerLevel + 1 + 3 + 4 * (size_t) ldsCand);
-    // (k_octree: the candidates' second sort buffer lies over the cell table and the node arrays, the first one behind them)
-    const size_t region = (((size_t) maxCellsPerLevel + 1 + 3) & ~(size_t) 3) + 19 * (size_t) cap;
-    return sizeof(int) * (std::max(region, 2 * (size_t) ldsCand) + 2 * (size_t) ldsCand);
-}
-
-int octree_lds_cand(int maxCellsPerLevel, int cap, size_t budget) {
-    const long long region = (((long long) maxCellsPerLevel + 1 + 3) & ~3ll) + 19ll * cap, ints = (long long) (budget / sizeof(int));
-    long long c = ints / 4;                              // the second buffer wider than the region it lies over
-    if (2 * c < region) c = (ints - region) / 2;         // ... or inside it
-    c &= ~3ll;
-    return c < 256 ? 0 : (int) std::min(c, 8192ll);
-}
-
-size_t octree_hist_lds_bytes(int regionInts, int histBins) { return sizeof(int) * ((size_t) regionInts + (size_t) histBins + 1); }
-
+// (octree_lds_bytes / octree_lds_cand / octree_hist_lds_bytes, the sizes of k_octree's dynamic LDS, are host arithmetic: ygzf_plan.hip)
 hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist) {
     constexpr int kOctMaxDyn = 160 * 1024 - 10 * 1024;   // the kernel's static LDS (radix histogram, scan scratch) is ~8.5 KB at 1024 threads
     if (hist) return hipFuncSetAttribute((const void *) k_octree<false, true, kOctBlock>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);

@@ -1,6 +1,7 @@
 // ygzf_ctx.h -- the context of libygzf and the small helpers every translation unit of the C ABI shares (product code, internal: nothing here
 // is part of include/ygzf.h).  The entry points live in
-//   ygzf_api.hip         context, geometry tables, buffers, the extractor's launch sequence, batch fetches, timers / profile
+//   ygzf_plan.hip        the extractor's launch plans per geometry: host arithmetic only, no kernel and no runtime call (ygzf_plan.h)
+//   ygzf_api.hip         context, device tables, buffers, the extractor's launch sequence, batch fetches, timers / profile
 //   ygzf_api_match.hip   ORBmatcher: SearchByProjection / SearchByBoW / SearchForInitialization / SearchForTriangulation, the Frame grid, isInFrustum,
 //                        distinctive descriptors, the vocabulary
 //   ygzf_api_align.hip   SparseImgAlign (one pair, cached, resident batch), the image cache, FindDirectProjection
@@ -20,45 +21,13 @@
 #include <set>
 #include <unordered_map>
 
-#include "kernels.h"
-
-#define YGZF_HIDDEN __attribute__((visibility("hidden")))
+#include "ygzf_plan.h"
 
 namespace ygzf {
-YGZF_HIDDEN int cv_round_host(double v);
 enum KernelKind { KK_PYR = 0, KK_FAST, KK_OCTREE, KK_DESCRIBE, KK_HAMMING, KK_BACKPROJ, KK_MATCH, KK_SIA, KK_FAST10, KK_DSO, KK_STEREO, KK_DIRECT, KK_BOW, KK_FRUSTUM, KK_DISTINCTIVE, KK_BOWNODES, KK_GRID, KK_FASTQ, KK_TRI, KK_FASTP, KK_FUSE, KK_PROJ, KK_BOWKF, KK_KFDB, KK_KFGRID, KK_COUNT };
 // (the KK_FUSE slot keeps the name ygzf_profile_read has always reported for it; it times k_proj_search<PM_FUSE>)
 static const char *kKernelNames[KK_COUNT] = {"k_pyr_resize", "k_fast_tab", "k_octree", "k_describe", "k_hamming_pairs",
                                              "k_backproject_unit", "k_match_last", "k_sia_run", "k_f10_*", "k_dso_cells", "k_stereo_*", "k_direct_projection", "k_bow_descend", "k_frustum", "k_distinctive", "k_bow_nodes", "k_features_in_area", "k_fast_quads", "k_tri_nodes", "k_fast_tab_persist", "k_fuse", "k_proj_search", "k_bow_kf_nodes", "k_kfdb_query", "k_kf_grid_build"};
-
-struct Geometry {
-    int w = 0, h = 0;
-    std::vector<LevelGeom> lv;
-    std::vector<int> xofs, yofs;
-    std::vector<short> xalpha, ybeta;
-    std::vector<PyrColRec> pyrCols;      // k_pyr_resize_tiled's tables (levels >= 1, LevelGeom::pyrCol / pyrRow / pyrTile index them)
-    std::vector<PyrRowRec> pyrRows;
-    std::vector<PyrTileRec> pyrTiles;
-    long long pyrBytes = 0;   // per frame, levels >= 1
-    std::vector<PyrStripPlan> pyrPlan;   // k_pyr_strips: one entry per strip (empty: this geometry takes one launch per level)
-    int pyrStripOffA = 0, pyrStripOffB = 0;
-    int pyrBase = 0;                     // the strips start from this level (0: the image; > 0: levels 1 .. pyrBase come from k_pyr_resize_tiled first)
-    PyrStripLevel pyrLevels[kMaxLevels];
-    size_t pyrStripLds = 0;
-    int totalCells = 0, maxCellsPerLevel = 0;
-    int totalGroups = 0, fastSmapRows = 3, fastWinPitch = 16, fastWinRows = 7, fastQuadCap = 4;   // 2x2 cell groups of k_fast_quads
-    int fastWCellMax = 1;
-    std::vector<FastCellRec> fastCells;   // [group * 4 + position]: k_fast_tab's per-cell records
-    long long totalSlots = 0;
-    long long candStride = 0;
-    int kpStride = 0, kpCapMax = 0;
-};
-
-// One launch of k_octree's sort plan (node arrays in LDS): levels [l0, l0 + n), `block` threads per workgroup, list capacity `cap`, candidate
-// budget `ldsCand` (more candidates sort through global memory), `lds` bytes of dynamic LDS.
-struct OctSortGroup { int l0 = 0, n = 0, block = kOctBlock, cap = 0, ldsCand = 0; size_t lds = 0; };
-// oneGroup: all levels in one launch of kOctBlock threads (YGZF_FORCE=oct_groups=1); block > 0 / ldsBytes > 0 pin every launch's workgroup / LDS
-YGZF_HIDDEN std::vector<OctSortGroup> plan_oct_sort(const Geometry &G, int L, bool oneGroup, int block, size_t ldsBytes);
 
 }  // namespace ygzf
 
@@ -109,15 +78,8 @@ struct ygzf_ctx {
     std::vector<unsigned char> alKey;   // cache key of the uploaded SiaLevel tables
     int identityPoses = 0;
     void *identityPosesPtr = nullptr;
-    size_t octLds = 0;         // one launch of all levels (the global-arena sort plan); the plan choice (oct_sort_budget) -- not the budgets of octSortGroups
-    int octLdsCand = 0;
-    bool octGlobalNodes = false;
-    // histogram plan of the octree (levels with tens of thousands of candidates): launches of consecutive levels, each with its own LDS allotment
-    struct OctGroup { int l0 = 0, n = 0, cap = 0, regionInts = 0, histBins = 0; size_t lds = 0; };
-    std::vector<OctGroup> octGroups;
-    OctGroup octSmall;                     // all levels in ONE histogram-plan launch: launches of a few frames (see run_extract)
-    std::vector<OctSortGroup> octSortGroups;   // sort plan with LDS node arrays: its launches (plan_oct_sort)
-    bool haveOctSmall = false;
+    PlanPins pins = PlanPins::from_env();   // the YGZF_FORCE plan pins as they stood when this context was constructed (ygzf_plan.h)
+    OctPlan oct;               // what the geometry's octree launches with (plan_octree)
     bool carryOff = false;     // ygzf_set_carry_previous(0): extractions do not carry the previous batch's last frame into slot 0
     struct OctHistLayout {     // what dOctHist's hand-over counters were last cleared for (k_octree's helper workgroups)
         int frames = 0, helpers = 0, histBins = 0;
@@ -125,7 +87,7 @@ struct ygzf_ctx {
         bool operator==(const OctHistLayout &o) const { return frames == o.frames && helpers == o.helpers && histBins == o.histBins && bytes == o.bytes; }
     } octHistLayout;
     int octDoneTarget = 0;     // what the launches since that clear have brought every (level, frame) counter of the layout to
-    static constexpr int octSmallWgs = 128;   // launches of up to this many workgroups take it (752x480: 16 frames 0.211 against 0.221 ms, 64 frames 0.439 against 0.430)
+    static constexpr int octSmallWgs = 128;   // launches of up to this many workgroups take oct.small (752x480: 16 frames 0.211 against 0.221 ms, 64 frames 0.439 against 0.430)
     Buf dOctNodes;
     // FAST threshold plan (extract_kernels.hip, fast_cell): 0 = chosen per batch from the statistics the kernel leaves behind, 1 = one pass at
     // minTh, 2 = iniTh first.  Identical results either way.
@@ -197,7 +159,6 @@ struct ygzf_ctx {
     // ygzf_set_extract_ahead: ygzf_compute_pyramid queues the extraction behind the pyramid and reads the levels back on a second stream
     // one-frame pyramid chain as a captured graph: seven dependent launches cost the host more than the kernels take (pyramid_chain)
     bool useGraphs = !debug_flag("nograph");
-    int pyrStripFrames = (int) forced("pyr_strip_frames", 16);   // k_pyr_strips up to this many frames per launch (0: never)
     PyrChainGraph pyrGraph = {};
     const void *pyrGraphKey[6] = {nullptr};   // geometry tables + size the graph was built for
     bool extractAhead = false;
@@ -212,8 +173,6 @@ struct ygzf_ctx {
     bool linkKernels = forced("fetch_kernel", 1) != 0, pyrLink = forced("pyr_link", 1) != 0;
     int uploadKernelFrames = (int) forced("upload_kernel_frames", 2);
     size_t uploadKernelBytes = (size_t) forced("upload_kernel_bytes", 16l << 20);
-    int octHelpersForced = (int) forced("oct_helpers", -1), octHelperSpin = (int) forced("oct_helper_spin", 1 << 16);
-    int fastPersistMode = (int) forced("fast_persist", -1), fastPersistWgs = (int) forced("fast_persist_wgs", 8);
     int matchSplit = (int) forced("match_split", 0);   // 0 automatic, 1 off, n workgroups per pair
     int matchFixedLanes = forced_is("match_lanes", "fixed");   // eight lanes per query whatever the launch
     int matchFence = (int) forced("match_fence", 0);   // 1: full fences around the matcher's hand-over
@@ -265,8 +224,6 @@ static int ensure(ygzf_ctx *c, ygzf_ctx::Buf &b, size_t bytes) {
     b.bytes = bytes;
     return YGZF_OK;
 }
-
-static inline int align_up(int v, int a) { return (v + a - 1) / a * a; }
 
 // ---- the transitions of ygzf_ctx::held (its only writers) ----------------------------------------------------------------------------
 static void forget_outputs(ygzf_ctx *c) { c->held.frames = 0; c->held.carry = 0; }
@@ -475,7 +432,6 @@ static inline ygzf::PyrTabs pyr_tabs(const ygzf_ctx *c) {
 }
 
 // ---- defined in ygzf_api.hip, used by the other translation units ---------------------------------------------------------------------
-YGZF_HIDDEN int build_geometry(ygzf_ctx *c, int w, int h, ygzf::Geometry &G);
 YGZF_HIDDEN int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames);
 YGZF_HIDDEN int pyramid_chain(ygzf_ctx *c, const ygzf::FrameSet &fs, int nFrames);
 YGZF_HIDDEN int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf);   // ygzf_api_stereo.hip

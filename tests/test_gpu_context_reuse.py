@@ -368,3 +368,29 @@ def test_mgpu_tail_chunks_on_one_slot(orc):
         got = mg.extract_match(frames, unit=2, cam=cam, th=TH)
         _mgpu_check(orc, frames, got, 2, ("short units", i))
     mg.close()
+
+
+_OCT_PLAN = re.compile(r"\[ygzf octree (small plan|histogram plan|sort plan|single launch)")
+
+
+def test_plan_pins_outlive_a_geometry_change(oracle, capfd):
+    """YGZF_FORCE is read when the context is created (csrc/ygzf_plan.h, PlanPins) and holds for every geometry the context meets afterwards: a
+    context created with oct_plan=sort -- the environment restored right after, as every helper here does -- extracts two 320x240 frames, then two
+    200x150 frames.  Launches of so few workgroups are the small histogram plan's unless the sort plan is pinned: both extractions must report
+    the sort plan's launches and no small plan, and give the oracle's keypoints and descriptors."""
+    from orb_ygz_slam_amd import Extractor
+    nf, nl = 300, 3
+    with _env(debug="oct", oct_plan="sort"):
+        ex = Extractor(nf, 1.2, nl, 20, 7, max_width=320, max_height=240, max_batch=2)
+    oex = oracle.Extractor(nf, 1.2, nl, 20, 7)
+    for w, h in ((320, 240), (200, 150)):
+        imgs = _images(w, h, n=2)
+        capfd.readouterr()
+        ex.extract_batch_host(np.stack(imgs))
+        ran = _OCT_PLAN.findall(capfd.readouterr().err)
+        assert ran and all(p in ("sort plan", "single launch") for p in ran), ((w, h), ran)
+        for f in range(2):
+            k, d = ex.batch_fetch(f)
+            ok, od = oex.extract(imgs[f])
+            assert len(k) == len(ok) and (k == ok).all() and (d == od).all(), ((w, h), f)
+    ex.close()

@@ -40,6 +40,11 @@ def main():
     rows = []
     rows.append(("extract (image)", med(lambda: ex.extract(A))))
     rows.append(("compute_pyramid", med(lambda: ex.compute_pyramid(A))))
+    rows.append(("compute_pyramid + extract_resident", med(lambda: (ex.compute_pyramid(A), ex.extract_resident(w, h)))))
+    ex16 = Extractor(1000, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=16)
+    batch = np.stack([A, B] * 8)
+    rows.append(("extract_batch_host + sync (16 frames)", med(lambda: (ex16.extract_batch_host(batch), ex16.sync()))))
+    ex16.close()
     rows.append(("extract_dso (150 existing keys)", med(lambda: ex.extract_dso(A, ka[:150]))))
     ex.extract(A)
     rows.append(("describe_keys (150 keys, after an extract)", med(lambda: ex.describe_keys(ka[:150]))))
