@@ -166,9 +166,19 @@ int ygzf_extract(ygzf_ctx *ctx, const uint8_t *img, int w, int h, int stride, yg
  * row_pitch bytes apart (base pointer, row_pitch and frame_stride must be multiples of 4: the kernels use aligned 32-bit loads).
  * Results stay on the device (chain into ygzf_match_*) until fetched.  Asynchronous on the
  * context stream; ygzf_sync / ygzf_batch_counts / ygzf_batch_fetch synchronise.
- * Lifetime: the context keeps d_imgs as level 0 of the batch -- ygzf_describe_keys, ygzf_stereo_batch, ygzf_align_batch_prev and
+ * Lifetime: the context keeps d_imgs as level 0 of the batch -- ygzf_describe_keys, ygzf_stereo_batch and
  * ygzf_batch_fetch_level(…, 0, …) read it later -- so the frames must stay valid and unchanged until the next ygzf_extract* call on this
- * context (or its destruction). */
+ * context (or its destruction).  (ygzf_align_batch_prev aligns on levels >= 1, which the context owns: it never reads d_imgs.)
+ * What is read: of frame f, at F = d_imgs + f*frame_stride, any byte of [F & ~15, F + h*row_pitch) -- the h*row_pitch bytes of the frame, the
+ * padding of its rows and of its LAST row included, and the 16-byte block that holds its first byte, i.e. up to 12 bytes in front of a frame
+ * that is only 4-aligned.  All of that must be readable device memory; only the w pixels of each row influence a result.  Who reads beyond the
+ * pixels (established by reading the kernels, csrc/extract_kernels.hip -- a test cannot observe an out-of-range read safely; the tests lay the
+ * frames out between garbage and compare results, tests/test_gpu_device_frames.py): the descriptor window is staged as 64 bytes per row from the
+ * 16-byte boundary below its first byte (describe_window: rows ky-21 .. ky+21 <= h-2, so never past F + h*row_pitch); the tiled pyramid step
+ * loads 16-byte chunks of a row from 4-aligned columns and bounds itself by h*row_pitch, not by (h-1)*row_pitch + w (pyr_tile; the chunk that
+ * would cross that bound is read byte by byte); the FAST cell table stages 48 bytes per window row, the last row at least 16 rows above the
+ * bottom (fast_tab_cell).  k_pyr_strips (aligned dwords below w rounded up to 4 <= row_pitch), fast_cell, k_pyr_resize, the stereo kernels and
+ * ygzf_batch_fetch_level read pixels only. */
 int ygzf_extract_batch_device(ygzf_ctx *ctx, const uint8_t *d_imgs, int n_frames, int w, int h, int row_pitch, size_t frame_stride);
 /* Same, host frames (H2D copy of each frame included).  The copy is asynchronous too: `imgs` must stay valid and unchanged until the next
  * synchronising call on this context (ygzf_sync, ygzf_batch_counts, ygzf_batch_fetch*, ...); page-locked memory gives the full PCIe rate. */

@@ -124,8 +124,9 @@ def test_baseline_large_configs(oracle, w, h, nl, nf):
 
 
 def test_bench_clip_parity(oracle):
-    """The exact clip bench.py times: every frame of a 64-frame run (extract + match against the predecessor, carried across two
-    batches) equals the oracle -- the number `value` is quoted on is a number about correct results."""
+    """The clip bench.py times, through the HOST entry (ygzf_extract_batch_host: level 0 in the context's own buffer): every frame of a 64-frame
+    run (extract + match against the predecessor, carried across two batches) equals the oracle.  The device entry bench.py itself launches
+    (ygzf_extract_batch_device on the caller's frames) is covered by tests/test_gpu_device_frames.py."""
     from bench import make_frames
     from orb_ygz_slam_amd import Extractor, make_camera, EUROC
     w, h = 752, 480
