@@ -17,6 +17,7 @@
 #include <mutex>
 #include "kernels.h"
 #include "wave_ops.h"
+#include "describe_lds.h"
 #include "orb_pattern_table.h"
 
 namespace ygzf {
@@ -2161,8 +2162,7 @@ __device__ __forceinline__ int reflect101(int i, int n) {
     return i;
 }
 
-constexpr int kWin = 43, kWinP = 64;    // raw window: one 16-byte aligned 64-byte span per row (+ alignment slack)
-constexpr int kHb = 37, kHbP = 40;      // horizontally blurred: 43 rows x 37 cols (u16), pitch even for 32-bit stores
+// kWin, kWinSpan (raw window: one 16-byte aligned 64-byte span per row), kHb, kHbP (row-blurred window) and the window's LDS layout: describe_lds.h
 constexpr int kBl = 37, kBlP = 40;      // blurred 37x37 (u8)
 // waves (= keypoints) per workgroup of k_describe / k_describe_list.  A workgroup's LDS and wave slots stay allocated until its slowest wave
 // is done (interior windows and border windows differ by a factor of several): measured per 256 frames, same box, 1 / 2 / 4 / 8 waves per
@@ -2172,29 +2172,37 @@ constexpr int kBl = 37, kBlP = 40;      // blurred 37x37 (u8)
 #endif
 constexpr int kDescWaves = YGZF_DESC_WAVES;
 
-// Per-wave LDS: the row-blurred window hb (43 rows x 40 u16 = 3440 B) and the raw window (43 rows x 64 B) share memory: hb rows 0..25
-// sit in front of raw, hb rows 26..42 overlay raw rows 0..21, which are dead by the time they are written (the orientation moments
-// are taken first, the horizontal pass consumes raw rows in ascending order and a wave's LDS operations execute in order).
-// 4.9 KB per wave -> the CU's 32 wave slots fill before its LDS does.
-constexpr int kHbFront = 26 * kHbP * 2;   // bytes of hb in front of raw (rows 0..25)
+typedef __attribute__((address_space(3))) unsigned lds_u32_t;
+// p + bytes as an LDS address the compiler takes as given: what is read or written through it are offsets of the instructions
+template <typename T>
+__device__ __forceinline__ T *lds_at(T *p, unsigned bytes) {
+    unsigned a = (unsigned) (uintptr_t) p + bytes;
+    asm("" : "+v"(a));
+    return (T *) (uintptr_t) a;
+}
+
+// Per-wave LDS: the row-blurred window hb (43 rows x 40 u16 = 3440 B) and the raw window (43 spans of 64 B and 20 pad slots, 3088 B) share
+// memory: hb's first kHbFront bytes sit in front of raw, the rest overlays raw rows that are dead by the time it is written.  describe_lds.h
+// states the condition and asserts it.  4.4 KB per wave -> the CU's 32 wave slots fill before its LDS does.
 struct DescLds {
-    __attribute__((aligned(16))) uint8_t mem[kHbFront + kWin * kWinP + 16];
+    __attribute__((aligned(16))) uint8_t mem[kDescLdsBytes];
     __device__ __forceinline__ uint8_t *rawp() { return mem + kHbFront; }
     __device__ __forceinline__ unsigned short *hbp() { return (unsigned short *) mem; }
 };
 
 // umax of the 31-px circular patch (src/ORBextractor.cc:455-469 for HALF_PATCH_SIZE = 15); ygzf_create checks the context's table against it
 constexpr int kUmax15[16] = {15, 15, 15, 15, 14, 14, 14, 13, 13, 12, 11, 10, 9, 8, 6, 3};
-// Disc membership as byte masks: item = (row v + 15) * 8 + j covers columns u + 15 = 4j .. 4j + 3 of row v; byte k of m[item] is 0xFF
-// when (u, v) lies inside the patch (|u| <= umax[|v|]).  Items 248..255 (past the last row) are empty.
-struct DiscBytes { unsigned m[256]; };
+// Disc membership as byte masks, in the centroid's own item order (describe_lds.h): item = 64 * step + lane covers columns u + 15 = 4j .. 4j + 3
+// (j = desc_centroid_dword(lane)) of window row desc_centroid_row(step, lane) = 21 + v; byte k of m[item] is 0xFF when (u, v) lies inside
+// the patch (|u| <= umax[|v|]).  The eight items of row 37 (past the last row of the disc) are empty.
+struct DiscBytes { unsigned m[64 * kDescCenSteps]; };
 constexpr DiscBytes make_disc_bytes() {
     DiscBytes d{};
-    for (int item = 0; item < 248; item++) {
-        const int v = (item >> 3) - 15, j = item & 7;
+    for (int item = 0; item < 64 * kDescCenSteps; item++) {
+        const int v = desc_centroid_row(item >> 6, item & 63) - 21, j = desc_centroid_dword(item & 63);
         const int av = v < 0 ? -v : v;
         unsigned m = 0;
-        for (int k = 0; k < 4; k++) {
+        for (int k = 0; k < 4 && av <= 15; k++) {
             const int u = 4 * j + k - 15;
             const int au = u < 0 ? -u : u;
             if (u <= 15 && au <= kUmax15[av]) m |= 0xFFu << (8 * k);
@@ -2221,49 +2229,57 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
     // ---- stage the 43x43 window (rows ky-21..ky+21).  Interior keypoints: the 43 bytes of a row lie inside one 16-byte
     // aligned 64-byte span -> 4 lanes x dwordx4 per row, 3 wave-level loads for the whole window, all in flight at once.
     // Keypoints within 21 px of the image border need BORDER_REFLECT_101 (what the blur of the border-less level clone
-    // sees) and take the byte path.  Window column c of row r lives at raw[r*64 + ((rowOff0 + r*rowOffStep) & 15) + c].
-    unsigned discM[4];   // disc membership bytes of this lane's four centroid work items: loaded first, used after the window is staged
+    // sees) and take the byte path.  Window column c of row r lives at raw[desc_row_byte(r) + ((rowOff0 + r*rowOffStep) & 15) + c]; the rows'
+    // spans are padded apart against LDS bank conflicts (describe_lds.h).
+    unsigned discM[kDescCenSteps];   // disc membership bytes of this lane's four centroid work items: loaded first, used after the window is staged
 #pragma unroll
-    for (int it = 0; it < 4; it++) discM[it] = c_disc.m[it * 64 + lane];
+    for (int it = 0; it < kDescCenSteps; it++) discM[it] = c_disc.m[it * 64 + lane];
     const bool interior = kx >= 21 && kx + 21 < gw && ky >= 21 && ky + 22 < gh && ((pitch & 3) == 0);
     int rowOff0 = 0, rowOffStep = 0;
     if (interior) {
         const unsigned long long a00 = (unsigned long long) img + (unsigned) (ky - 21) * (unsigned) pitch + (unsigned) (kx - 21);
         rowOff0 = (int) (a00 & 15);
         rowOffStep = pitch & 15;
-        // LDS-DMA: lane idx & 63 of piece idx >> 6 delivers LDS bytes 16 idx .. 16 idx + 15 = row idx >> 2, quarter idx & 3 -- the window's own
-        // layout, so the 43 x 64 bytes go global memory -> LDS in three instructions without a register round trip or a ds_write
+        // LDS-DMA: lane s & 63 of piece s >> 6 delivers LDS bytes 16 s .. 16 s + 15.  Which quarter of which row's span that slot holds is
+        // the layout's choice (desc_slot_item); the lanes of the pad slots load nothing.  So the 43 x 64 bytes go global memory -> LDS in
+        // three instructions without a register round trip or a ds_write
 #pragma unroll
-        for (int i0 = 0; i0 < kWin * 4; i0 += 64) {
-            const int idx = i0 + lane, r = idx >> 2, q = idx & 3;
-            const unsigned long long a = a00 + __umul24((unsigned) r, (unsigned) pitch);
-            if (idx < kWin * 4)
-                __builtin_amdgcn_global_load_lds((const unsigned *) ((a & ~15ull) + 16 * q), (lds_void_t *) (L.rawp() + 16 * i0), 16, 0, 0);
+        for (int i0 = 0; i0 < kDescRawSlots; i0 += 64) {
+            const int item = desc_slot_item(i0 + lane), r = item >> 2, q = item & 3;
+            // the 16-byte boundary below the row's first byte, as a 32-bit offset from the one below the window's first byte
+            const unsigned off = ((unsigned) rowOff0 + __umul24((unsigned) r, (unsigned) pitch)) & ~15u;
+            if (!desc_slot_is_pad(i0 + lane))
+                __builtin_amdgcn_global_load_lds((const unsigned *) ((a00 & ~15ull) + (off + 16u * (unsigned) q)), (lds_void_t *) (L.rawp() + 16 * i0), 16, 0, 0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     } else {
         for (int idx = lane; idx < kWin * kWin; idx += 64) {
             const int r = idx / kWin, c = idx - r * kWin;
             const int yy = reflect101(ky - 21 + r, gh), xx = reflect101(kx - 21 + c, gw);
-            L.rawp()[r * kWinP + c] = img[(long long) yy * pitch + xx];
+            L.rawp()[desc_row_byte(r) + c] = img[(long long) yy * pitch + xx];
         }
     }
-#define RAWP(r) (&L.rawp()[(r) * kWinP + ((rowOff0 + (r) * rowOffStep) & 15)])
+    // byte offset of window row r's column 0 in the raw region
+    auto rawByte = [&](int r) { return (unsigned) (desc_row_byte(r) + ((rowOff0 + r * rowOffStep) & 15)); };
     wave_lds_handoff();
     pc.mark(0);
     // ---- intensity centroid on the 31x31 disc (centre = window (21,21)).  Work item = four pixels (row v, columns u = 4j-15 .. 4j-12):
     // two aligned dwords shifted into place, masked with the disc membership bytes, then m01 += v * (sum of the bytes) [v_sad_u8] and
-    // m10 += <bytes, (4j .. 4j+3)> - 15 * sum [v_dot4_u32_u8].  248 items = 4 steps of the wave; integer sums, any order is exact.
+    // m10 += <bytes, (4j .. 4j+3)> - 15 * sum [v_dot4_u32_u8].  248 items = 4 steps of the wave; integer sums, any order is exact, and the
+    // order is the one whose reads meet no bank twice (desc_centroid_row).  A lane's four rows are 8 apart: same offset inside the span, a
+    // constant number of bytes further.
     int m10, m01;
     {
         unsigned wsum = 0, ssum = 0;
         int vsum = 0;
-        const unsigned ucol = 0x03020100u + 0x04040404u * (unsigned) (lane & 7);
+        const int j = desc_centroid_dword(lane), r0 = desc_centroid_row(0, lane);
+        const unsigned ucol = 0x03020100u + 0x04040404u * (unsigned) j;
+        const unsigned A = rawByte(r0) + 6u + 4u * (unsigned) j;
+        const unsigned *dw0 = (const unsigned *) L.rawp() + (A >> 2);
 #pragma unroll
-        for (int it = 0; it < 4; it++) {
-            const int r = 6 + it * 8 + (lane >> 3);                      // window row 21 + v
-            const unsigned A = (unsigned) (RAWP(r) - L.rawp()) + 6u + 4u * (unsigned) (lane & 7);
-            const unsigned *dw = (const unsigned *) L.rawp() + (A >> 2);
+        for (int it = 0; it < kDescCenSteps; it++) {
+            const int r = r0 + kDescCenStepRows * it;                    // window row 21 + v
+            const unsigned *dw = dw0 + it * (kDescCenStepBytes / 4);
             const unsigned px = __builtin_amdgcn_alignbyte(dw[1], dw[0], A & 3u) & discM[it];
             const unsigned sm = __builtin_amdgcn_sad_u8(px, 0u, 0u);
             wsum = __builtin_amdgcn_udot4(px, ucol, wsum, false);
@@ -2287,14 +2303,22 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
     constexpr unsigned kTapHi = 0x00122200u | (unsigned) k2;                                  // bytes (k2, 34, 18, 0)
     // horizontal: 43 rows x 4 segments of 10 columns (the last one's columns 37..39 land in the row's slack and are never read): 172 items =
     // three steps of the wave (eight-column segments made 215 items: a fourth step for 23 of the 64 lanes)
-    for (int t = lane; t < kWin * 4; t += 64) {
-        const int r = t >> 2, sg = t & 3;
+    // A lane's steps are 16 rows apart: same offset inside the span (16 x rowOffStep), same hb column, and a distance in bytes that only the
+    // layout decides (desc_blur_step_byte) -- one address computation for the three steps.
+    const int rb0 = desc_blur_row(lane), sg = desc_blur_seg(lane);
+    const unsigned Ab0 = rawByte(rb0) + 10u * (unsigned) sg;
+    // Each step's source and destination address is ONE register, the five dwords are instruction offsets from it (lds_at: left to itself
+    // the compiler forms a base register per ds_read2 / ds_write2 pair, two more vector instructions per step and side).
+    const lds_u32_t *const dw0 = (const lds_u32_t *) ((const unsigned *) L.rawp() + (Ab0 >> 2));
+    const unsigned sh = Ab0 & 3u;
+    lds_u32_t *const hb0 = (lds_u32_t *) &L.hbp()[rb0 * kHbP + 10 * sg];
+#pragma unroll
+    for (int s = 0; s < kDescBlurSteps; s++) {
+        if (64 * (s + 1) > kDescBlurItems && lane >= kDescBlurItems - 64 * s) break;   // (the last step has 44 items)
         // 16 source bytes from an arbitrary byte address: five aligned dwords, shifted into place once (e[k] = bytes 4k..4k+3 of the
         // run); output j = <bytes j..j+3, (18,34,k2,k3)> + <bytes j+4..j+7, (k2,34,18,0)> -- two v_dot4_u32_u8 per output, exact
         // (the sum is at most 65535); byte j+7 meets the zero tap, so output 9 never needs a sixth dword.
-        const unsigned A = (unsigned) (RAWP(r) - L.rawp()) + 10u * (unsigned) sg;
-        const unsigned *dw = (const unsigned *) L.rawp() + (A >> 2);
-        const unsigned sh = A & 3u;
+        const lds_u32_t *dw = lds_at(dw0, (unsigned) desc_blur_step_byte(s, rb0));
         const unsigned d0 = dw[0], d1 = dw[1], d2 = dw[2], d3 = dw[3], d4 = dw[4];
         // e[m] = bytes 4m .. 4m + 3 of the run.  Output j = 4m + r sums bytes j .. j + 6 against (18, 34, k2, k3, k2, 34, 18): instead of shifting the
         // bytes into place for every j (three more v_alignbyte per dword) the TAPS are shifted -- eight constant words -- and the aligned dwords meet
@@ -2317,7 +2341,7 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
         const unsigned o8 = __builtin_amdgcn_udot4(e[2], T0a, __builtin_amdgcn_udot4(e[3], T0b, 0u, false), false);
         const unsigned o9 = __builtin_amdgcn_udot4(e[2], T1a, __builtin_amdgcn_udot4(e[3], T1b, 0u, false), false);
         const unsigned O[5] = {oa[0] | (oa[1] << 16), oa[2] | (oa[3] << 16), ob[0] | (ob[1] << 16), ob[2] | (ob[3] << 16), o8 | (o9 << 16)};
-        unsigned *dst = (unsigned *) &L.hbp()[r * kHbP + 10 * sg];
+        lds_u32_t *dst = lds_at(hb0, (unsigned) s * (kDescBlurStepRows * kHbP * 2));
         dst[0] = O[0]; dst[1] = O[1]; dst[2] = O[2]; dst[3] = O[3]; dst[4] = O[4];
     }
     wave_lds_handoff();
@@ -2358,7 +2382,6 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
     }
     pc.mark(5);
     *angleOut = angle;
-#undef RAWP
 }
 
 // Output bookkeeping between the octree and k_describe: first output index of every level of every frame (the levels' keypoints are
