@@ -352,8 +352,8 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
         if ((rc = launch_fast(c, fs, nFrames, fast, iniFirst, collect))) return rc;
         long long *odbg = nullptr;
         if (c->octDebug) {
-            if ((rc = ensure(c, c->dTmpA, kOctDbgWords * sizeof(long long)))) return rc;
-            odbg = (long long *) c->dTmpA.p;
+            if ((rc = ensure(c, c->tmp.a, kOctDbgWords * sizeof(long long)))) return rc;
+            odbg = (long long *) c->tmp.a.p;
             HIPCHECK(c, hipMemsetAsync(odbg, 0, kOctDbgWords * sizeof(long long), c->stream));
         }
         // launches of a few frames take the small plan (all levels in one histogram-plan launch, with helper workgroups), every other one the geometry's launches
@@ -526,46 +526,6 @@ void ygzf_destroy(ygzf_ctx *c) {
     if (!c) return;
     (void) hipSetDevice(c->device);
     if (c->stream) (void) hipStreamSynchronize(c->stream);
-    ygzf_ctx::Buf *bufs[] = {&c->dGeom, &c->dXofs, &c->dXalpha, &c->dYofs, &c->dYbeta, &c->dImg0, &c->dPyr, &c->dCellCnt, &c->dSlots,
-                             &c->dK0, &c->dV0, &c->dK1, &c->dV1, &c->dXY, &c->dLvlXY, &c->dLvlScore, &c->dLvlCnt, &c->dLvlBase, &c->dLvlCand,
-                             &c->dOutKp, &c->dOutDesc, &c->dOutCnt, &c->dTmpA, &c->dTmpB, &c->dTmpC, &c->dWorld, &c->dOwner, &c->dMatch,
-                             &c->dNMatch, &c->dPoses, &c->dQp, &c->dProcOrder, &c->dSpill, &c->dCarryPyr, &c->dOctNodes, &c->dResPack, &c->dFastCtr,
-                             &c->dPyrPlan, &c->dPyrCols, &c->dPyrRows, &c->dPyrTiles, &c->dOctHist};
-    for (auto *b : bufs)
-        if (b->p) (void) hipFree(b->p);
-    for (auto &b : c->dGen)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dSia)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dVoc)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dBow)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dF10)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dAl)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dDso)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dSt)
-        if (b.p) (void) hipFree(b.p);
-    if (c->dStBins.p) (void) hipFree(c->dStBins.p);
-    for (auto &b : c->dDir)
-        if (b.p) (void) hipFree(b.p);
-    for (auto &b : c->dFr)
-        if (b.p) (void) hipFree(b.p);
-    if (c->dCacheImg.p) (void) hipFree(c->dCacheImg.p);
-    if (c->dCachePyr.p) (void) hipFree(c->dCachePyr.p);
-    if (c->dFastStats.p) (void) hipFree(c->dFastStats.p);
-    if (c->dFastCells.p) (void) hipFree(c->dFastCells.p);
-    if (c->dPack.p) (void) hipFree(c->dPack.p);
-    if (c->dMatchStat.p) (void) hipFree(c->dMatchStat.p);
-    if (c->dSplitCnt.p) (void) hipFree(c->dSplitCnt.p);
-    if (c->dSplitX.p) (void) hipFree(c->dSplitX.p);
-    if (c->dUpStage.p) (void) hipFree(c->dUpStage.p);
-    for (auto *b : {&c->kfdb.dIds, &c->kfdb.dVals, &c->kfdb.dTable})
-        if (b->p) (void) hipFree(b->p);
-    if (c->kfs.dArena.p) (void) hipFree(c->kfs.dArena.p);
     if (c->hFastStats) (void) hipHostFree(c->hFastStats);
     if (c->hStage) (void) hipHostFree(c->hStage);
     if (c->hIn) (void) hipHostFree(c->hIn);
@@ -580,7 +540,7 @@ void ygzf_destroy(ygzf_ctx *c) {
     if (c->tStart) (void) hipEventDestroy(c->tStart);
     if (c->tStop) (void) hipEventDestroy(c->tStop);
     if (c->stream) (void) hipStreamDestroy(c->stream);
-    delete c;
+    delete c;   // every Buf frees itself here: on the device selected above, with the stream drained
 }
 
 const char *ygzf_last_error(const ygzf_ctx *c) {
@@ -715,12 +675,12 @@ int ygzf_compute_pyramid(ygzf_ctx *c, const uint8_t *img, int w, int h, int stri
     offs[0] = offs[1] = 0;
     for (int l = 1; l < L; l++) offs[l + 1] = offs[l] + (unsigned) G.lv[l].w * (unsigned) G.lv[l].h;
     const size_t total = offs[L];
-    if ((rc = ensure_stage(c, total + 64)) || (rc = ensure(c, c->dTmpC, total + 64))) return rc;
+    if ((rc = ensure_stage(c, total + 64)) || (rc = ensure(c, c->tmp.c, total + 64))) return rc;
     // (the page-locked staging area as the device addresses it: the packing kernel -- 16-byte stores -- writes the levels over the link itself, on the
     // stream the copy would have taken; a byte-per-thread packing kernel doing so was slower than the copy engine: ComputePyramid 94 -> 97 us)
     const bool linkPack = c->hStageDev != nullptr && c->linkKernels && c->pyrLink;
     if (!linkPack) {
-        launch_pack_levels(c->stream, fs, (const LevelGeom *) c->dGeom.p, 1, L, offs, (uint8_t *) c->dTmpC.p);
+        launch_pack_levels(c->stream, fs, (const LevelGeom *) c->dGeom.p, 1, L, offs, (uint8_t *) c->tmp.c.p);
         HIPCHECK(c, hipGetLastError());
     }
     // extract-ahead: FAST / octree / descriptors of this image are queued behind the pyramid now and run while the levels travel back on
@@ -738,7 +698,7 @@ int ygzf_compute_pyramid(ygzf_ctx *c, const uint8_t *img, int w, int h, int stri
     if (total && linkPack) {
         launch_pack_levels(rd, fs, (const LevelGeom *) c->dGeom.p, 1, L, offs, (uint8_t *) c->hStageDev);
         HIPCHECK(c, hipGetLastError());
-    } else if (total) HIPCHECK(c, hipMemcpyAsync(c->hStage, c->dTmpC.p, total, hipMemcpyDeviceToHost, rd));
+    } else if (total) HIPCHECK(c, hipMemcpyAsync(c->hStage, c->tmp.c.p, total, hipMemcpyDeviceToHost, rd));
     if (ahead && (rc = run_extract(c, fs, 1, true))) return rc;   // (queued after the copy so that the copy starts while these launches are issued)
     if (levels_out[0] != img || stride != w)
         for (int y = 0; y < h; y++) memcpy(levels_out[0] + (size_t) y * w, img + (size_t) y * stride, (size_t) w);
@@ -970,8 +930,8 @@ int ygzf_stereo_pair_host(ygzf_ctx *l, ygzf_ctx *r, const uint8_t *left, const u
     HIPCHECK(l, hipStreamWaitEvent(l->stream, r->evShare, 0));
     if ((rc = stereo_across(l, r, mb, mbf))) return rc;
     const size_t ks = (size_t) l->geo.kpStride;
-    HIPCHECK(l, hipMemcpyAsync(u_right, l->dSt[1].p, 4 * ks, hipMemcpyDeviceToHost, l->stream));
-    HIPCHECK(l, hipMemcpyAsync(depth, l->dSt[2].p, 4 * ks, hipMemcpyDeviceToHost, l->stream));
+    HIPCHECK(l, hipMemcpyAsync(u_right, l->st.uRight.p, 4 * ks, hipMemcpyDeviceToHost, l->stream));
+    HIPCHECK(l, hipMemcpyAsync(depth, l->st.depth.p, 4 * ks, hipMemcpyDeviceToHost, l->stream));
     HIPCHECK(l, hipStreamSynchronize(r->stream));
     HIPCHECK(l, hipStreamSynchronize(l->stream));
     return YGZF_OK;
@@ -1038,11 +998,11 @@ int ygzf_batch_fetch_level(ygzf_ctx *c, int frame, int level, uint8_t *out) {
     const uint8_t *p = level_ptr(c->held.fs, g, level, frame, &pitch);
     // packed on the device, then one linear copy (a pitched copy of an odd-width level is executed row by row)
     const size_t bytes = (size_t) g.w * g.h;
-    int rc = ensure(c, c->dTmpC, bytes + 64);
+    int rc = ensure(c, c->tmp.c, bytes + 64);
     if (rc) return rc;
-    launch_repitch_rows(c->stream, p, (size_t) pitch, (uint8_t *) c->dTmpC.p, (size_t) g.w, g.w, (size_t) g.h);
+    launch_repitch_rows(c->stream, p, (size_t) pitch, (uint8_t *) c->tmp.c.p, (size_t) g.w, g.w, (size_t) g.h);
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(out, c->dTmpC.p, bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(out, c->tmp.c.p, bytes, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
@@ -1123,17 +1083,17 @@ int ygzf_descriptor_distance(ygzf_ctx *c, const uint8_t *a, const uint8_t *b, in
         HIPCHECK(c, hipGetLastError());
         return P.download();
     }
-    if ((rc = ensure(c, c->dTmpA, (size_t) n * 32)) || (rc = ensure(c, c->dTmpB, (size_t) n * 32)) ||
-        (rc = ensure(c, c->dTmpC, (size_t) n * sizeof(int))))
+    if ((rc = ensure(c, c->tmp.a, (size_t) n * 32)) || (rc = ensure(c, c->tmp.b, (size_t) n * 32)) ||
+        (rc = ensure(c, c->tmp.c, (size_t) n * sizeof(int))))
         return rc;
-    HIPCHECK(c, hipMemcpyAsync(c->dTmpA.p, a, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(c->dTmpB.p, b, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(c->tmp.a.p, a, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(c->tmp.b.p, b, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, KK_HAMMING);
-        launch_hamming_pairs(c->stream, c->dTmpA.p, c->dTmpB.p, n, (int *) c->dTmpC.p);
+        launch_hamming_pairs(c->stream, c->tmp.a.p, c->tmp.b.p, n, (int *) c->tmp.c.p);
     }
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(dist, c->dTmpC.p, (size_t) n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(dist, c->tmp.c.p, (size_t) n * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }

@@ -42,7 +42,7 @@ static int sia_run_impl(ygzf_ctx *c, const ygzf_sia_frame *ref, const ygzf_sia_f
     HIPCHECK(c, hipSetDevice(c->device));
     const size_t N = ref->n;
     int rc;
-    ygzf_ctx::Buf *S = c->dSia;   // 4 images, 6 caches; the small arrays cross the link as one packed copy each way (PackedTransfer)
+    ygzf_ctx::Sia &S = c->sia;   // the levels' images and the patch cache; the small arrays cross the link as one packed copy each way (PackedTransfer)
     std::vector<SiaLevel> lv(2 * kMaxLevels);
     memset(lv.data(), 0, lv.size() * sizeof(SiaLevel));
     size_t largestCur = 0;   // the largest current-frame level that may be staged in LDS beside the feature tables
@@ -69,13 +69,13 @@ static int sia_run_impl(ygzf_ctx *c, const ygzf_sia_frame *ref, const ygzf_sia_f
                 return fail(c, YGZF_ERR_INVALID, "bad pyramid level %d", l);
             imgBytes += (size_t) ref->level_w[l] * ref->level_h[l] + (size_t) cur->level_w[l] * cur->level_h[l] + 128;
         }
-        if ((rc = ensure(c, S[4], imgBytes))) return rc;
+        if ((rc = ensure(c, S.images, imgBytes))) return rc;
         size_t off = 0;
         for (int l = min_level; l <= max_level; l++) {
             for (int side = 0; side < 2; side++) {
                 const ygzf_sia_frame *f = side ? cur : ref;
                 const size_t b = (size_t) f->level_w[l] * f->level_h[l];
-                uint8_t *d = (uint8_t *) S[4].p + off;
+                uint8_t *d = (uint8_t *) S.images.p + off;
                 HIPCHECK(c, hipMemcpyAsync(d, f->levels[l], b, hipMemcpyHostToDevice, c->stream));   // Frame clones are tight (step == cols)
                 SiaLevel &L = lv[side * kMaxLevels + l];
                 L.img = d; L.w = f->level_w[l]; L.h = f->level_h[l]; L.pitch = f->level_w[l];
@@ -95,7 +95,7 @@ static int sia_run_impl(ygzf_ctx *c, const ygzf_sia_frame *ref, const ygzf_sia_f
     uint8_t *dIn;
     const size_t nLv = (size_t) (max_level - min_level + 1);
     const bool perLevel = c->siaPerLevel;
-    if ((rc = ensure(c, S[6], perLevel ? nLv * N * (52 * sizeof(float) + 1) + N + 64 : N * (16 + 96) * sizeof(float) + N + 64)) || (rc = P.upload(&dIn))) return rc;
+    if ((rc = ensure(c, S.patchCache, perLevel ? nLv * N * (52 * sizeof(float) + 1) + N + 64 : N * (16 + 96) * sizeof(float) + N + 64)) || (rc = P.upload(&dIn))) return rc;
     const SiaLevel *dLv = (const SiaLevel *) (dIn + oLv);
     SiaArgs A;
     memset(&A, 0, sizeof A);
@@ -114,7 +114,7 @@ static int sia_run_impl(ygzf_ctx *c, const ygzf_sia_frame *ref, const ygzf_sia_f
     A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy;
     A.maxLevel = max_level; A.minLevel = min_level; A.nIter = n_iter;
     A.eps = 0.000001f;   // src/SparseImageAlign.cc:17
-    A.patchCache = (float *) S[6].p;
+    A.patchCache = (float *) S.patchCache.p;
     A.jacCache = nullptr;
     A.visible = (uint8_t *) (A.patchCache + N * 48);
     A.momCache = A.patchCache + N * 64;   // (the buffer holds 112 floats per feature)
@@ -130,9 +130,9 @@ static int sia_run_impl(ygzf_ctx *c, const ygzf_sia_frame *ref, const ygzf_sia_f
     A.out = (float *) P.d_out(rOut);
     {
         if (c->siaDebug) {
-            if ((rc = ensure(c, c->dTmpB, 256))) return rc;
-            HIPCHECK(c, hipMemsetAsync(c->dTmpB.p, 0, 256, c->stream));
-            A.dbg = (long long *) c->dTmpB.p;
+            if ((rc = ensure(c, c->tmp.b, 256))) return rc;
+            HIPCHECK(c, hipMemsetAsync(c->tmp.b.p, 0, 256, c->stream));
+            A.dbg = (long long *) c->tmp.b.p;
         }
         size_t sl = sia_lds_bytes((int) N);
         A.ldsFeat = (int) N;
@@ -281,16 +281,16 @@ int ygzf_find_direct_projection_batch(ygzf_ctx *c, const ygzf_camera *cam, int c
         if (ref_kp[i].octave < 0 || ref_kp[i].octave >= L) return fail(c, YGZF_ERR_INVALID, "candidate %d: octave out of range", i);
     }
     HIPCHECK(c, hipSetDevice(c->device));
-    ygzf_ctx::Buf *D = c->dDir;
+    ygzf_ctx::Direct &D = c->dir;
     struct Up { ygzf_ctx::Buf *b; const void *src; size_t bytes; };
-    Up ups[] = {{&D[0], ref_slot, 4 * (size_t) n}, {&D[1], ref_Tcw7, 28 * (size_t) n}, {&D[2], ref_kp, sizeof(ygzf_kp) * (size_t) n},
-                {&D[3], mp_world, 12 * (size_t) n}, {&D[4], px_curr, 8 * (size_t) n}};
+    Up ups[] = {{&D.refSlot, ref_slot, 4 * (size_t) n}, {&D.refTcw7, ref_Tcw7, 28 * (size_t) n}, {&D.refKp, ref_kp, sizeof(ygzf_kp) * (size_t) n},
+                {&D.mpWorld, mp_world, 12 * (size_t) n}, {&D.pxCurr, px_curr, 8 * (size_t) n}};
     int rc;
     for (auto &u : ups) {
         if ((rc = ensure(c, *u.b, u.bytes))) return rc;
         HIPCHECK(c, hipMemcpyAsync(u.b->p, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
     }
-    if ((rc = ensure(c, D[5], 4 * (size_t) n)) || (rc = ensure(c, D[6], (size_t) n)) || (patches_with_border && (rc = ensure(c, D[7], 100 * (size_t) n)))) return rc;
+    if ((rc = ensure(c, D.searchLevel, 4 * (size_t) n)) || (rc = ensure(c, D.success, (size_t) n)) || (patches_with_border && (rc = ensure(c, D.patches, 100 * (size_t) n)))) return rc;
     DirectArgs A;
     memset(&A, 0, sizeof A);
     A.cache = cache_frameset_impl(c);
@@ -305,23 +305,23 @@ int ygzf_find_direct_projection_batch(ygzf_ctx *c, const ygzf_camera *cam, int c
     }
     A.invLevelSigma2_1 = c->tab.invSigma2[L > 1 ? 1 : 0];
     A.n = n;
-    A.refSlot = (const int *) D[0].p;
-    A.refTcw7 = (const float *) D[1].p;
-    A.refKp = (const ygzf_kp *) D[2].p;
-    A.mpWorld = (const float *) D[3].p;
-    A.pxCurr = (float *) D[4].p;
-    A.searchLevel = (int *) D[5].p;
-    A.success = (uint8_t *) D[6].p;
-    A.patches = patches_with_border ? (uint8_t *) D[7].p : nullptr;
+    A.refSlot = (const int *) D.refSlot.p;
+    A.refTcw7 = (const float *) D.refTcw7.p;
+    A.refKp = (const ygzf_kp *) D.refKp.p;
+    A.mpWorld = (const float *) D.mpWorld.p;
+    A.pxCurr = (float *) D.pxCurr.p;
+    A.searchLevel = (int *) D.searchLevel.p;
+    A.success = (uint8_t *) D.success.p;
+    A.patches = patches_with_border ? (uint8_t *) D.patches.p : nullptr;
     {
         ProfScope ps(c, KK_DIRECT);
         launch_direct_projection(c->stream, A);
     }
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(px_curr, D[4].p, 8 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(search_level, D[5].p, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(success, D[6].p, (size_t) n, hipMemcpyDeviceToHost, c->stream));
-    if (patches_with_border) HIPCHECK(c, hipMemcpyAsync(patches_with_border, D[7].p, 100 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(px_curr, D.pxCurr.p, 8 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(search_level, D.searchLevel.p, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(success, D.success.p, (size_t) n, hipMemcpyDeviceToHost, c->stream));
+    if (patches_with_border) HIPCHECK(c, hipMemcpyAsync(patches_with_border, D.patches.p, 100 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
@@ -339,17 +339,17 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
     const int B = c->held.frames;
     if (G.kpStride == 0) return fail(c, YGZF_ERR_STATE, "configuration yields no keypoints");
     c->alignCarry = true;
-    ygzf_ctx::Buf *S = c->dAl;   // 0 level tables, 1 poses, 2 caches, 3 out, (world = dWorld)
+    ygzf_ctx::Align &S = c->al;   // (world = dWorld)
     if ((rc = ensure(c, c->dWorld, (size_t) (B + 1) * G.kpStride * 3 * sizeof(float))) ||
-        (rc = ensure(c, S[0], (size_t) B * 2 * kMaxLevels * sizeof(SiaLevel))) || (rc = ensure(c, S[1], (size_t) B * 14 * sizeof(float))) ||
-        (rc = ensure(c, S[2], c->siaPerLevel && B <= kSiaPerLevelPairs ? (size_t) (max_level - min_level + 1) * B * G.kpStride * (52 * sizeof(float) + 1) + (size_t) B * G.kpStride + 64
+        (rc = ensure(c, S.levels, (size_t) B * 2 * kMaxLevels * sizeof(SiaLevel))) || (rc = ensure(c, S.poses, (size_t) B * 14 * sizeof(float))) ||
+        (rc = ensure(c, S.patchCache, c->siaPerLevel && B <= kSiaPerLevelPairs ? (size_t) (max_level - min_level + 1) * B * G.kpStride * (52 * sizeof(float) + 1) + (size_t) B * G.kpStride + 64
                                               : (size_t) B * G.kpStride * ((16 + 96) * sizeof(float) + 1) + 64)) ||
-        (rc = ensure(c, S[3], (size_t) B * 48 * sizeof(float))) || (rc = ensure(c, c->dCarryPyr, (size_t) G.pyrBytes + 256)))
+        (rc = ensure(c, S.out, (size_t) B * 48 * sizeof(float))) || (rc = ensure(c, c->dCarryPyr, (size_t) G.pyrBytes + 256)))
         return rc;
     // level tables + identity poses: uploaded when anything they depend on changed
     std::vector<unsigned char> key;
     {
-        const void *parts[] = {c->dPyr.p, c->dCarryPyr.p, S[0].p, S[1].p};
+        const void *parts[] = {c->dPyr.p, c->dCarryPyr.p, S.levels.p, S.poses.p};
         key.insert(key.end(), (const unsigned char *) parts, (const unsigned char *) parts + sizeof parts);
         const int ints[] = {B, G.w, G.h, c->held.carryPyr ? 1 : 0};
         key.insert(key.end(), (const unsigned char *) ints, (const unsigned char *) ints + sizeof ints);
@@ -367,8 +367,8 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
             }
         std::vector<float> poses((size_t) B * 14, 0.f);
         for (int p = 0; p < B; p++) poses[(size_t) p * 14 + 3] = poses[(size_t) p * 14 + 10] = 1.f;   // identity quaternions
-        HIPCHECK(c, hipMemcpyAsync(S[0].p, lv.data(), lv.size() * sizeof(SiaLevel), hipMemcpyHostToDevice, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(S[1].p, poses.data(), poses.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(S.levels.p, lv.data(), lv.size() * sizeof(SiaLevel), hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(S.poses.p, poses.data(), poses.size() * sizeof(float), hipMemcpyHostToDevice, c->stream));
         HIPCHECK(c, hipStreamSynchronize(c->stream));
         c->alKey = key;
     }
@@ -381,15 +381,15 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
     A.unitWorld = 1;             // MapPoints at unit depth along the keypoints' rays, computed where they are used
     A.kpStride = G.kpStride;
     A.nRef = cnt;
-    A.poses = (const float *) S[1].p;
-    A.refLv = (const SiaLevel *) S[0].p;
+    A.poses = (const float *) S.poses.p;
+    A.refLv = (const SiaLevel *) S.levels.p;
     A.curLv = A.refLv + kMaxLevels;
     A.lvStride = 2 * kMaxLevels;
     for (int l = 0; l < kMaxLevels; l++) A.invScale[l] = l < L ? c->tab.invScale[l] : 1.f;
     A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy;
     A.maxLevel = max_level; A.minLevel = min_level; A.nIter = n_iter;
     A.eps = 0.000001f;
-    A.patchCache = (float *) S[2].p;
+    A.patchCache = (float *) S.patchCache.p;
     A.jacCache = nullptr;
     A.visible = (uint8_t *) (A.patchCache + (size_t) B * G.kpStride * 48);
     A.momCache = A.patchCache + (size_t) B * G.kpStride * 64;   // (the buffer holds 112 floats per keypoint slot)
@@ -403,9 +403,9 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
         A.levelFlags = (uint8_t *) (A.momCache + nLv * slots * 4);
         A.visible = A.levelFlags + nLv * slots;
     }
-    A.out = (float *) S[3].p;
+    A.out = (float *) S.out.p;
     const int first = c->held.carryPyr ? 0 : 1;   // without a carried pyramid frame 0 has no reference image
-    if (!c->held.carryPyr) HIPCHECK(c, hipMemsetAsync(S[3].p, 0, 48 * sizeof(float), c->stream));
+    if (!c->held.carryPyr) HIPCHECK(c, hipMemsetAsync(S.out.p, 0, 48 * sizeof(float), c->stream));
     if (B - first > 0) {
         SiaArgs A2 = A;
         A2.keys += (size_t) first * G.kpStride;
@@ -453,7 +453,7 @@ int ygzf_align_fetch(ygzf_ctx *c, int frame, float *TCR_out, size_t *ret, float 
     if (c->held.alignPairs < 1) return fail(c, YGZF_ERR_STATE, "no aligned batch");
     if (frame < 0 || frame >= c->held.alignPairs) return fail(c, YGZF_ERR_INVALID, "frame %d out of range", frame);
     float out[48];
-    HIPCHECK(c, hipMemcpyAsync(out, (float *) c->dAl[3].p + (size_t) frame * 48, sizeof out, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(out, (float *) c->al.out.p + (size_t) frame * 48, sizeof out, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     memcpy(TCR_out, out, 28);
     *ret = (size_t) out[7];

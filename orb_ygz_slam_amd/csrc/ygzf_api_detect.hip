@@ -20,19 +20,19 @@ int ygzf_fast10(ygzf_ctx *c, const uint8_t *img, int img_w, int img_h, int strid
     } else if (h < 7)
         return YGZF_OK;
     HIPCHECK(c, hipSetDevice(c->device));
-    ygzf_ctx::Buf *B = c->dF10;
+    ygzf_ctx::Fast10 &B = c->f10;
     const int pitch = align_up(img_w, 64);
     int rc;
-    if ((rc = ensure(c, B[0], (size_t) pitch * img_h)) || (rc = ensure(c, B[1], (size_t) w * h * sizeof(short))) ||
-        (rc = ensure(c, B[2], (size_t) (2 * h + 2) * sizeof(int))) || (rc = ensure(c, B[3], (size_t) std::max(cap, 1) * 2 * sizeof(short))) ||
-        (rc = ensure(c, B[4], (size_t) std::max(cap, 1) * sizeof(int))) || (rc = ensure(c, B[5], (size_t) std::max(cap, 1) * sizeof(int))))
+    if ((rc = ensure(c, B.img, (size_t) pitch * img_h)) || (rc = ensure(c, B.scores, (size_t) w * h * sizeof(short))) ||
+        (rc = ensure(c, B.rowCnt, (size_t) (2 * h + 2) * sizeof(int))) || (rc = ensure(c, B.xy, (size_t) std::max(cap, 1) * 2 * sizeof(short))) ||
+        (rc = ensure(c, B.scoreList, (size_t) std::max(cap, 1) * sizeof(int))) || (rc = ensure(c, B.nonmax, (size_t) std::max(cap, 1) * sizeof(int))))
         return rc;
-    if ((rc = upload_rows(c, B[0].p, (size_t) pitch, img, (size_t) stride, img_w, (size_t) img_h))) return rc;
-    int *rowCnt = (int *) B[2].p, *rowKept = rowCnt + h, *totals = rowKept + h;
+    if ((rc = upload_rows(c, B.img.p, (size_t) pitch, img, (size_t) stride, img_w, (size_t) img_h))) return rc;
+    int *rowCnt = (int *) B.rowCnt.p, *rowKept = rowCnt + h, *totals = rowKept + h;
     {
         ProfScope ps(c, KK_FAST10);
-        launch_fast10(c->stream, (const uint8_t *) B[0].p, pitch, x0, y0, w, h, dx0, dx1, dy0, dy1, barrier, (short *) B[1].p, rowCnt, rowKept,
-                      totals, (short *) B[3].p, (int *) B[4].p, (int *) B[5].p, cap);
+        launch_fast10(c->stream, (const uint8_t *) B.img.p, pitch, x0, y0, w, h, dx0, dx1, dy0, dy1, barrier, (short *) B.scores.p, rowCnt, rowKept,
+                      totals, (short *) B.xy.p, (int *) B.scoreList.p, (int *) B.nonmax.p, cap);
     }
     HIPCHECK(c, hipGetLastError());
     int tot[2];
@@ -41,9 +41,9 @@ int ygzf_fast10(ygzf_ctx *c, const uint8_t *img, int img_w, int img_h, int strid
     *n_corners = tot[0];
     if (n_nonmax) *n_nonmax = tot[1];
     if (tot[0] > cap) return fail(c, YGZF_ERR_INVALID, "capacity %d < %d corners", cap, tot[0]);
-    if (tot[0] && xy) HIPCHECK(c, hipMemcpyAsync(xy, B[3].p, (size_t) tot[0] * 2 * sizeof(short), hipMemcpyDeviceToHost, c->stream));
-    if (tot[0] && scores) HIPCHECK(c, hipMemcpyAsync(scores, B[4].p, (size_t) tot[0] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    if (tot[1] && nonmax_idx) HIPCHECK(c, hipMemcpyAsync(nonmax_idx, B[5].p, (size_t) tot[1] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (tot[0] && xy) HIPCHECK(c, hipMemcpyAsync(xy, B.xy.p, (size_t) tot[0] * 2 * sizeof(short), hipMemcpyDeviceToHost, c->stream));
+    if (tot[0] && scores) HIPCHECK(c, hipMemcpyAsync(scores, B.scoreList.p, (size_t) tot[0] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    if (tot[1] && nonmax_idx) HIPCHECK(c, hipMemcpyAsync(nonmax_idx, B.nonmax.p, (size_t) tot[1] * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
@@ -64,6 +64,22 @@ static int key_level_position(ygzf_ctx *c, const ygzf_kp &k, int i, int *px, int
     return YGZF_OK;
 }
 
+// describe the first `total` entries of grid.list on `frame` of fs and read angles (ang may be null) + descriptors back; synchronises
+static int describe_list(ygzf_ctx *c, const FrameSet &fs, int frame, int total, float *ang, uint8_t *desc) {
+    ygzf_ctx::Grid &D = c->grid;
+    int rc;
+    if ((rc = ensure(c, D.angles, 4 * (size_t) total)) || (rc = ensure(c, c->tmp.c, 32 * (size_t) total))) return rc;
+    {
+        ProfScope ps(c, KK_DESCRIBE);
+        launch_describe_list(c->stream, fs, (const LevelGeom *) c->dGeom.p, D.list.p, total, frame, (float *) D.angles.p, (uint8_t *) c->tmp.c.p, c->tab.cfg.cv_mode);
+    }
+    HIPCHECK(c, hipGetLastError());
+    if (ang) HIPCHECK(c, hipMemcpyAsync(ang, D.angles.p, 4 * (size_t) total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(desc, c->tmp.c.p, 32 * (size_t) total, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    return YGZF_OK;
+}
+
 int ygzf_describe_keys(ygzf_ctx *c, int frame, const ygzf_kp *keys, int n, int recompute_angle, float *angles_out, uint8_t *desc) {
     if (!c || (n > 0 && (!keys || !desc))) return fail(c, YGZF_ERR_INVALID, "null argument");
     if (c->held.frames < 1) return fail(c, YGZF_ERR_STATE, "no extracted batch");
@@ -81,17 +97,9 @@ int ygzf_describe_keys(ygzf_ctx *c, int frame, const ygzf_kp *keys, int n, int r
         memcpy(&list4[4 * i + 3], &keys[i].angle, 4);
     }
     int rc;
-    if ((rc = ensure(c, c->dDso[5], 16 * (size_t) n)) || (rc = ensure(c, c->dDso[7], 4 * (size_t) n)) || (rc = ensure(c, c->dTmpC, 32 * (size_t) n))) return rc;
-    HIPCHECK(c, hipMemcpyAsync(c->dDso[5].p, list4.data(), 16 * (size_t) n, hipMemcpyHostToDevice, c->stream));
-    {
-        ProfScope ps(c, KK_DESCRIBE);
-        launch_describe_list(c->stream, c->held.fs, (const LevelGeom *) c->dGeom.p, c->dDso[5].p, n, frame, (float *) c->dDso[7].p, (uint8_t *) c->dTmpC.p, c->tab.cfg.cv_mode);
-    }
-    HIPCHECK(c, hipGetLastError());
-    if (angles_out) HIPCHECK(c, hipMemcpyAsync(angles_out, c->dDso[7].p, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(desc, c->dTmpC.p, 32 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return YGZF_OK;
+    if ((rc = ensure(c, c->grid.list, 16 * (size_t) n))) return rc;
+    HIPCHECK(c, hipMemcpyAsync(c->grid.list.p, list4.data(), 16 * (size_t) n, hipMemcpyHostToDevice, c->stream));
+    return describe_list(c, c->held.fs, frame, n, angles_out, desc);
 }
 
 int ygzf_extract_dso(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, ygzf_kp *keys, int n_existing, int cap, uint8_t *desc,
@@ -132,18 +140,17 @@ int ygzf_extract_dso(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, 
     const int gmin = std::min(grid, minGrid);   // a start below 7 (many features on a small image) is used as it is; it only never shrinks further
     const int maxCells = (w / gmin) * (h / gmin) + 1;
     const size_t occWords = ((size_t) w * h + 31) / 32;
-    ygzf_ctx::Buf &dOcc = c->dDso[0], &dOccXY = c->dDso[1], &dCellCnt = c->dDso[2], &dCellXY = c->dDso[3], &dTotal = c->dDso[4], &dList = c->dDso[5],
-                  &dNewXY = c->dDso[6], &dAng = c->dDso[7];
+    ygzf_ctx::Grid &D = c->grid;
     const size_t maxEntries = (size_t) n_existing + 3 * (size_t) maxCells;
-    if ((rc = ensure(c, dOcc, occWords * 4)) || (rc = ensure(c, dOccXY, 4 * (size_t) (n_existing + 1))) || (rc = ensure(c, dCellCnt, 4 * (size_t) maxCells)) ||
-        (rc = ensure(c, dCellXY, 12 * (size_t) maxCells)) || (rc = ensure(c, dTotal, 64)) || (rc = ensure(c, dList, 16 * maxEntries)) ||
-        (rc = ensure(c, dNewXY, 4 * 3 * (size_t) maxCells)) || (rc = ensure(c, dAng, 4 * maxEntries)) || (rc = ensure(c, c->dTmpC, 32 * maxEntries)))
+    if ((rc = ensure(c, D.occ, occWords * 4)) || (rc = ensure(c, D.occXY_voteKey, 4 * (size_t) (n_existing + 1))) || (rc = ensure(c, D.cellCnt_lvlTotals, 4 * (size_t) maxCells)) ||
+        (rc = ensure(c, D.cellXY, 12 * (size_t) maxCells)) || (rc = ensure(c, D.total_lvlOff, 64)) || (rc = ensure(c, D.list, 16 * maxEntries)) ||
+        (rc = ensure(c, D.newXY, 4 * 3 * (size_t) maxCells)) || (rc = ensure(c, D.angles, 4 * maxEntries)) || (rc = ensure(c, c->tmp.c, 32 * maxEntries)))
         return rc;
-    HIPCHECK(c, hipMemsetAsync(dOcc.p, 0, occWords * 4, c->stream));
+    HIPCHECK(c, hipMemsetAsync(D.occ.p, 0, occWords * 4, c->stream));
     if (n_existing > 0) {
-        HIPCHECK(c, hipMemcpyAsync(dOccXY.p, occXY.data(), 4 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(dList.p, list4.data(), 16 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
-        launch_dso_occ(c->stream, (const unsigned *) dOccXY.p, n_existing, w, h, (unsigned *) dOcc.p);
+        HIPCHECK(c, hipMemcpyAsync(D.occXY_voteKey.p, occXY.data(), 4 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(D.list.p, list4.data(), 16 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
+        launch_dso_occ(c->stream, (const unsigned *) D.occXY_voteKey.p, n_existing, w, h, (unsigned *) D.occ.p);
     }
     // the grid-size retry loop of :1301-1377; mnGridSize persists across frames through *grid_size
     int cnt = 0, nInner = 0;
@@ -160,15 +167,15 @@ int ygzf_extract_dso(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, 
         const int nRows = h / grid, nCols = w / grid;
         nInner = (nRows > 2 && nCols > 2) ? (nRows - 2) * (nCols - 2) : 0;
         if (nInner > maxCells) return fail(c, YGZF_ERR_INVALID, "grid size %d: more cells than planned", grid);
-        HIPCHECK(c, hipMemsetAsync(dTotal.p, 0, 4, c->stream));
+        HIPCHECK(c, hipMemsetAsync(D.total_lvlOff.p, 0, 4, c->stream));
         {
             ProfScope ps(c, KK_DSO);
-            launch_dso_cells(c->stream, fs.img0, fs.img0_pitch, w, h, grid, nCols, nRows, (unsigned *) dOcc.p, (int *) dCellCnt.p, (unsigned *) dCellXY.p,
-                             (int *) dTotal.p, 20, 5, 3, w, false);   // :1330 / :1337: both barriers hard-coded in the single-level detector
+            launch_dso_cells(c->stream, fs.img0, fs.img0_pitch, w, h, grid, nCols, nRows, (unsigned *) D.occ.p, (int *) D.cellCnt_lvlTotals.p, (unsigned *) D.cellXY.p,
+                             (int *) D.total_lvlOff.p, 20, 5, 3, w, false);   // :1330 / :1337: both barriers hard-coded in the single-level detector
         }
         cnt = 0;
         if (nInner > 0) {
-            HIPCHECK(c, hipMemcpyAsync(&cnt, dTotal.p, 4, hipMemcpyDeviceToHost, c->stream));
+            HIPCHECK(c, hipMemcpyAsync(&cnt, D.total_lvlOff.p, 4, hipMemcpyDeviceToHost, c->stream));
             HIPCHECK(c, hipStreamSynchronize(c->stream));
         }
         if (cnt == 0) break;   // the reference loops forever on a frame without a single corner; defined: no new keypoints
@@ -180,18 +187,11 @@ int ygzf_extract_dso(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, 
     if (total > cap) return fail(c, YGZF_ERR_INVALID, "capacity %d < %d keypoints", cap, total);
     if (total == 0) return YGZF_OK;
     if (!desc || !keys) return fail(c, YGZF_ERR_INVALID, "null output");
-    if (cnt > 0) launch_dso_compact(c->stream, (const int *) dCellCnt.p, (const unsigned *) dCellXY.p, nInner, n_existing, dList.p, (unsigned *) dNewXY.p, 0);
-    {
-        ProfScope ps(c, KK_DESCRIBE);
-        launch_describe_list(c->stream, fs, dGeom, dList.p, total, 0, (float *) dAng.p, (uint8_t *) c->dTmpC.p, c->tab.cfg.cv_mode);
-    }
-    HIPCHECK(c, hipGetLastError());
+    if (cnt > 0) launch_dso_compact(c->stream, (const int *) D.cellCnt_lvlTotals.p, (const unsigned *) D.cellXY.p, nInner, n_existing, D.list.p, (unsigned *) D.newXY.p, 0);
     std::vector<float> ang(total);
     std::vector<unsigned> nxy(cnt);
-    HIPCHECK(c, hipMemcpyAsync(ang.data(), dAng.p, 4 * (size_t) total, hipMemcpyDeviceToHost, c->stream));
-    if (cnt > 0) HIPCHECK(c, hipMemcpyAsync(nxy.data(), dNewXY.p, 4 * (size_t) cnt, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(desc, c->dTmpC.p, 32 * (size_t) total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
+    if (cnt > 0) HIPCHECK(c, hipMemcpyAsync(nxy.data(), D.newXY.p, 4 * (size_t) cnt, hipMemcpyDeviceToHost, c->stream));
+    if ((rc = describe_list(c, fs, 0, total, ang.data(), desc))) return rc;
     for (int i = 0; i < n_existing; i++) keys[i].angle = ang[i];
     for (int i = 0; i < cnt; i++) {   // :1356-1366
         ygzf_kp &k = keys[n_existing + i];
@@ -232,22 +232,6 @@ static int grid_extract_begin(ygzf_ctx *c, const uint8_t *img, int w, int h, int
     return YGZF_OK;
 }
 
-// describe `total` list entries (the first n_existing are the frame's own keys) and read angles + descriptors back
-static int grid_extract_describe(ygzf_ctx *c, const FrameSet &fs, void *dList, int total, std::vector<float> *ang, uint8_t *desc) {
-    int rc;
-    if ((rc = ensure(c, c->dDso[7], 4 * (size_t) total)) || (rc = ensure(c, c->dTmpC, 32 * (size_t) total))) return rc;
-    {
-        ProfScope ps(c, KK_DESCRIBE);
-        launch_describe_list(c->stream, fs, (const LevelGeom *) c->dGeom.p, dList, total, 0, (float *) c->dDso[7].p, (uint8_t *) c->dTmpC.p, c->tab.cfg.cv_mode);
-    }
-    HIPCHECK(c, hipGetLastError());
-    ang->resize(total);
-    HIPCHECK(c, hipMemcpyAsync(ang->data(), c->dDso[7].p, 4 * (size_t) total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(desc, c->dTmpC.p, 32 * (size_t) total, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipStreamSynchronize(c->stream));
-    return YGZF_OK;
-}
-
 int ygzf_extract_fast_keypoint(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, ygzf_kp *keys, int n_existing, int cap, uint8_t *desc, int *n_total) {
     if (!c || !img || !n_total || (n_existing > 0 && !keys)) return fail(c, YGZF_ERR_INVALID, "null argument");
     if (n_existing < 0 || n_existing > cap) return fail(c, YGZF_ERR_INVALID, "n_existing %d outside 0..cap", n_existing);
@@ -282,17 +266,17 @@ int ygzf_extract_fast_keypoint(ygzf_ctx *c, const uint8_t *img, int w, int h, in
         maxH = std::max(maxH, g.h);
     }
     const size_t nAll = (size_t) std::max<long long>(lvlOff[L], 1);
-    ygzf_ctx::Buf *B = c->dF10;
-    ygzf_ctx::Buf &dOcc = c->dDso[0], &dKey = c->dDso[1], &dCellXY = c->dDso[3], &dOff = c->dDso[4], &dList = c->dDso[5], &dTot = c->dDso[2];
-    if ((rc = ensure(c, B[1], maxWin * sizeof(short))) || (rc = ensure(c, B[2], (size_t) (2 * maxH + 2) * sizeof(int))) || (rc = ensure(c, B[3], nAll * 2 * sizeof(short))) ||
-        (rc = ensure(c, B[4], nAll * sizeof(int))) || (rc = ensure(c, B[5], nAll * sizeof(int))) || (rc = ensure(c, dOcc, (size_t) nCells)) ||
-        (rc = ensure(c, dKey, 8 * (size_t) nCells)) || (rc = ensure(c, dCellXY, 4 * (size_t) nCells)) || (rc = ensure(c, dOff, 8 * (size_t) (L + 1))) ||
-        (rc = ensure(c, dTot, 8 * (size_t) L + 8)))
+    ygzf_ctx::Fast10 &B = c->f10;
+    ygzf_ctx::Grid &D = c->grid;
+    if ((rc = ensure(c, B.scores, maxWin * sizeof(short))) || (rc = ensure(c, B.rowCnt, (size_t) (2 * maxH + 2) * sizeof(int))) || (rc = ensure(c, B.xy, nAll * 2 * sizeof(short))) ||
+        (rc = ensure(c, B.scoreList, nAll * sizeof(int))) || (rc = ensure(c, B.nonmax, nAll * sizeof(int))) || (rc = ensure(c, D.occ, (size_t) nCells)) ||
+        (rc = ensure(c, D.occXY_voteKey, 8 * (size_t) nCells)) || (rc = ensure(c, D.cellXY, 4 * (size_t) nCells)) || (rc = ensure(c, D.total_lvlOff, 8 * (size_t) (L + 1))) ||
+        (rc = ensure(c, D.cellCnt_lvlTotals, 8 * (size_t) L + 8)))
         return rc;
-    HIPCHECK(c, hipMemcpyAsync(dOcc.p, occ.data(), (size_t) nCells, hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(dOff.p, lvlOff.data(), 8 * (size_t) (L + 1), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemsetAsync(dKey.p, 0, 8 * (size_t) nCells, c->stream));
-    HIPCHECK(c, hipMemsetAsync(dTot.p, 0, 8 * (size_t) L + 8, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(D.occ.p, occ.data(), (size_t) nCells, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(D.total_lvlOff.p, lvlOff.data(), 8 * (size_t) (L + 1), hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemsetAsync(D.occXY_voteKey.p, 0, 8 * (size_t) nCells, c->stream));
+    HIPCHECK(c, hipMemsetAsync(D.cellCnt_lvlTotals.p, 0, 8 * (size_t) L + 8, c->stream));
     for (int l = 0; l < L; l++) {
         const LevelGeom &g = G.lv[l];
         const long long win = lvlOff[l + 1] - lvlOff[l];
@@ -300,26 +284,26 @@ int ygzf_extract_fast_keypoint(ygzf_ctx *c, const uint8_t *img, int w, int h, in
         int pitch;
         const uint8_t *lp = level_ptr(fs, g, l, 0, &pitch);
         const int ww = g.w - 20, wh = g.h - 20;
-        int *rowCnt = (int *) B[2].p, *rowKept = rowCnt + wh, *totals = (int *) dTot.p + 2 * l;
-        short *xy = (short *) B[3].p + 2 * lvlOff[l];
-        int *scores = (int *) B[4].p + lvlOff[l], *nm = (int *) B[5].p + lvlOff[l];
+        int *rowCnt = (int *) B.rowCnt.p, *rowKept = rowCnt + wh, *totals = (int *) D.cellCnt_lvlTotals.p + 2 * l;
+        short *xy = (short *) B.xy.p + 2 * lvlOff[l];
+        int *scores = (int *) B.scoreList.p + lvlOff[l], *nm = (int *) B.nonmax.p + lvlOff[l];
         {
             ProfScope ps(c, KK_FAST10);
             // fast_corner_detect_10_sse2 on the window that starts 20 px in (:1216-1226): domain [3, ww - 3) x [3, wh - 3), barrier iniThFAST; score and
             // >= non-maximum suppression as fast_corner_score_10 / fast_nonmax_3x3 (:1233-1236)
-            launch_fast10(c->stream, lp, pitch, 20, 20, ww, wh, 3, ww - 3, 3, wh - 3, c->tab.cfg.ini_th_fast, (short *) B[1].p, rowCnt, rowKept, totals, xy, scores,
+            launch_fast10(c->stream, lp, pitch, 20, 20, ww, wh, 3, ww - 3, 3, wh - 3, c->tab.cfg.ini_th_fast, (short *) B.scores.p, rowCnt, rowKept, totals, xy, scores,
                           nm, (int) std::min<long long>(win, 0x7fffffff));
         }
         launch_fgrid_vote(c->stream, lp, pitch, g.w, g.h, l, c->tab.scale[l], xy, nm, totals, (int) std::min<long long>(win, 0x7fffffff), gridCols, nCells,
-                          (const uint8_t *) dOcc.p, (unsigned long long *) dKey.p);
+                          (const uint8_t *) D.occ.p, (unsigned long long *) D.occXY_voteKey.p);
     }
-    launch_fgrid_gather(c->stream, (const unsigned long long *) dKey.p, nCells, (const short *) B[3].p, (const int *) B[5].p, (const long long *) dOff.p,
-                        (unsigned *) dCellXY.p);
+    launch_fgrid_gather(c->stream, (const unsigned long long *) D.occXY_voteKey.p, nCells, (const short *) B.xy.p, (const int *) B.nonmax.p, (const long long *) D.total_lvlOff.p,
+                        (unsigned *) D.cellXY.p);
     HIPCHECK(c, hipGetLastError());
     std::vector<unsigned long long> key((size_t) nCells);
     std::vector<unsigned> cxy((size_t) nCells);
-    HIPCHECK(c, hipMemcpyAsync(key.data(), dKey.p, 8 * (size_t) nCells, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(cxy.data(), dCellXY.p, 4 * (size_t) nCells, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(key.data(), D.occXY_voteKey.p, 8 * (size_t) nCells, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(cxy.data(), D.cellXY.p, 4 * (size_t) nCells, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     // allKeypoints[octave]: the cells in index order (:1260-1266), then level after level (:1104-1125)
     std::vector<std::vector<ygzf_kp>> all(L);
@@ -350,10 +334,10 @@ int ygzf_extract_fast_keypoint(ygzf_ctx *c, const uint8_t *img, int w, int h, in
             list4.push_back((int) kp.x); list4.push_back((int) kp.y); list4.push_back(l); list4.push_back(0);
             keys[at++] = kp;
         }
-    if ((rc = ensure(c, dList, 16 * (size_t) total))) return rc;
-    HIPCHECK(c, hipMemcpyAsync(dList.p, list4.data(), 16 * (size_t) total, hipMemcpyHostToDevice, c->stream));
-    std::vector<float> ang;
-    if ((rc = grid_extract_describe(c, fs, dList.p, total, &ang, desc))) return rc;
+    if ((rc = ensure(c, D.list, 16 * (size_t) total))) return rc;
+    HIPCHECK(c, hipMemcpyAsync(D.list.p, list4.data(), 16 * (size_t) total, hipMemcpyHostToDevice, c->stream));
+    std::vector<float> ang(total);
+    if ((rc = describe_list(c, fs, 0, total, ang.data(), desc))) return rc;
     for (int i = 0; i < total; i++) keys[i].angle = ang[i];
     for (int i = n_existing; i < total; i++)            // keypoint->pt *= scale for levels > 0 (:1116-1121)
         if (keys[i].octave != 0) { keys[i].x *= c->tab.scale[keys[i].octave]; keys[i].y *= c->tab.scale[keys[i].octave]; }
@@ -385,18 +369,17 @@ int ygzf_extract_dso_multilevel(ygzf_ctx *c, const uint8_t *img, int w, int h, i
         maxCells = std::max(maxCells, cells);
     }
     const size_t occWords = ((size_t) w * h + 31) / 32;
-    ygzf_ctx::Buf &dOcc = c->dDso[0], &dOccXY = c->dDso[1], &dCellCnt = c->dDso[2], &dCellXY = c->dDso[3], &dTotal = c->dDso[4], &dList = c->dDso[5],
-                  &dNewXY = c->dDso[6];
+    ygzf_ctx::Grid &D = c->grid;
     const size_t maxEntries = (size_t) n_existing + (size_t) maxNew;
-    if ((rc = ensure(c, dOcc, occWords * 4)) || (rc = ensure(c, dOccXY, 4 * (size_t) (n_existing + 1))) || (rc = ensure(c, dCellCnt, 4 * (size_t) maxCells)) ||
-        (rc = ensure(c, dCellXY, 12 * (size_t) maxCells)) || (rc = ensure(c, dTotal, 64)) || (rc = ensure(c, dList, 16 * maxEntries)) ||
-        (rc = ensure(c, dNewXY, 4 * (size_t) maxNew + 16)))
+    if ((rc = ensure(c, D.occ, occWords * 4)) || (rc = ensure(c, D.occXY_voteKey, 4 * (size_t) (n_existing + 1))) || (rc = ensure(c, D.cellCnt_lvlTotals, 4 * (size_t) maxCells)) ||
+        (rc = ensure(c, D.cellXY, 12 * (size_t) maxCells)) || (rc = ensure(c, D.total_lvlOff, 64)) || (rc = ensure(c, D.list, 16 * maxEntries)) ||
+        (rc = ensure(c, D.newXY, 4 * (size_t) maxNew + 16)))
         return rc;
-    HIPCHECK(c, hipMemsetAsync(dOcc.p, 0, occWords * 4, c->stream));
+    HIPCHECK(c, hipMemsetAsync(D.occ.p, 0, occWords * 4, c->stream));
     if (n_existing > 0) {
-        HIPCHECK(c, hipMemcpyAsync(dOccXY.p, occXY.data(), 4 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(dList.p, list4.data(), 16 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
-        launch_dso_occ(c->stream, (const unsigned *) dOccXY.p, n_existing, w, h, (unsigned *) dOcc.p);
+        HIPCHECK(c, hipMemcpyAsync(D.occXY_voteKey.p, occXY.data(), 4 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(D.list.p, list4.data(), 16 * (size_t) n_existing, hipMemcpyHostToDevice, c->stream));
+        launch_dso_occ(c->stream, (const unsigned *) D.occXY_voteKey.p, n_existing, w, h, (unsigned *) D.occ.p);
     }
     int grid = *grid_size, newTotal = 0;
     std::vector<int> lvlCount(L, 0);
@@ -418,23 +401,23 @@ int ygzf_extract_dso_multilevel(ygzf_ctx *c, const uint8_t *img, int w, int h, i
             const int nRows = g.h / grid, nCols = g.w / grid;
             nInner = (nRows > 2 && nCols > 2) ? (nRows - 2) * (nCols - 2) : 0;
             if (nInner > maxCells) return fail(c, YGZF_ERR_INVALID, "grid size %d: more cells than planned", grid);
-            HIPCHECK(c, hipMemsetAsync(dTotal.p, 0, 4, c->stream));
+            HIPCHECK(c, hipMemsetAsync(D.total_lvlOff.p, 0, 4, c->stream));
             {
                 ProfScope ps(c, KK_DSO);
-                launch_dso_cells(c->stream, lp, pitch, g.w, g.h, grid, nCols, nRows, (unsigned *) dOcc.p, (int *) dCellCnt.p, (unsigned *) dCellXY.p, (int *) dTotal.p,
+                launch_dso_cells(c->stream, lp, pitch, g.w, g.h, grid, nCols, nRows, (unsigned *) D.occ.p, (int *) D.cellCnt_lvlTotals.p, (unsigned *) D.cellXY.p, (int *) D.total_lvlOff.p,
                                  c->tab.cfg.ini_th_fast, c->tab.cfg.min_th_fast, 2, w, true);
             }
             cnt = 0;
             if (nInner > 0) {
-                HIPCHECK(c, hipMemcpyAsync(&cnt, dTotal.p, 4, hipMemcpyDeviceToHost, c->stream));
+                HIPCHECK(c, hipMemcpyAsync(&cnt, D.total_lvlOff.p, 4, hipMemcpyDeviceToHost, c->stream));
                 HIPCHECK(c, hipStreamSynchronize(c->stream));
             }
             if (cnt == 0) break;                         // defined: a pass without a single corner ends the level (the reference would spin)
         }
         if (cnt > 0) {
             if ((long long) newTotal + cnt > maxNew) return fail(c, YGZF_ERR_INVALID, "more keypoints than planned");
-            launch_dso_compact(c->stream, (const int *) dCellCnt.p, (const unsigned *) dCellXY.p, nInner, n_existing + newTotal, dList.p,
-                               (unsigned *) dNewXY.p + newTotal, l);
+            launch_dso_compact(c->stream, (const int *) D.cellCnt_lvlTotals.p, (const unsigned *) D.cellXY.p, nInner, n_existing + newTotal, D.list.p,
+                               (unsigned *) D.newXY.p + newTotal, l);
             lvlCount[l] = cnt;
             newTotal += cnt;
         }
@@ -446,9 +429,9 @@ int ygzf_extract_dso_multilevel(ygzf_ctx *c, const uint8_t *img, int w, int h, i
     if (total == 0) return YGZF_OK;
     if (!desc || !keys) return fail(c, YGZF_ERR_INVALID, "null output");
     std::vector<unsigned> nxy(std::max(newTotal, 1));
-    if (newTotal > 0) HIPCHECK(c, hipMemcpyAsync(nxy.data(), dNewXY.p, 4 * (size_t) newTotal, hipMemcpyDeviceToHost, c->stream));
-    std::vector<float> ang;
-    if ((rc = grid_extract_describe(c, fs, dList.p, total, &ang, desc))) return rc;
+    if (newTotal > 0) HIPCHECK(c, hipMemcpyAsync(nxy.data(), D.newXY.p, 4 * (size_t) newTotal, hipMemcpyDeviceToHost, c->stream));
+    std::vector<float> ang(total);
+    if ((rc = describe_list(c, fs, 0, total, ang.data(), desc))) return rc;
     for (int i = 0; i < n_existing; i++) keys[i].angle = ang[i];
     int at = 0;
     for (int l = 0; l < L; l++)

@@ -13,15 +13,10 @@ static void kfdb_mark_dirty(ygzf_ctx::Kfdb &K, int lo, int hi) {
     K.dirtyHi = std::max(K.dirtyHi, hi);
 }
 
-static int kfdb_alloc_arena(ygzf_ctx *c, size_t entries, void **ids, void **vals) {
-    *ids = *vals = nullptr;
-    HIPCHECK(c, hipMalloc(ids, sizeof(uint32_t) * entries));
-    const hipError_t e = hipMalloc(vals, sizeof(double) * entries);
-    if (e != hipSuccess) {
-        (void) hipFree(*ids);
-        *ids = nullptr;
-        return fail(c, YGZF_ERR_HIP, "hipMalloc of the keyframe database's values failed: %s", hipGetErrorString(e));
-    }
+// a fresh arena of `entries` entries in two buffers of the caller's: a local Buf that does not reach the context frees itself
+static int kfdb_alloc_arena(ygzf_ctx *c, size_t entries, ygzf_ctx::Buf &ids, ygzf_ctx::Buf &vals) {
+    int rc;
+    if ((rc = ensure(c, ids, sizeof(uint32_t) * entries)) || (rc = ensure(c, vals, sizeof(double) * entries))) return rc;
     return YGZF_OK;
 }
 
@@ -35,10 +30,7 @@ static int kfdb_reserve(ygzf_ctx *c, size_t n) {
     if (K.cap == 0) {
         size_t cap = YGZF_KFDB_INITIAL_ENTRIES;
         while (cap < n) cap *= 2;
-        void *ids, *vals;
-        if ((rc = kfdb_alloc_arena(c, cap, &ids, &vals))) return rc;
-        K.dIds.p = ids; K.dIds.bytes = sizeof(uint32_t) * cap;
-        K.dVals.p = vals; K.dVals.bytes = sizeof(double) * cap;
+        if ((rc = kfdb_alloc_arena(c, cap, K.dIds, K.dVals))) return rc;
         K.cap = cap;
         return YGZF_OK;
     }
@@ -50,28 +42,23 @@ static int kfdb_reserve(ygzf_ctx *c, size_t n) {
     size_t top = 0;
     for (size_t s = 0; s < S; s++)
         if (K.slots[s].live) { newOff[s] = (long long) top; top += (size_t) K.slots[s].len; }
-    void *ids, *vals;
-    if ((rc = kfdb_alloc_arena(c, cap, &ids, &vals))) return rc;
+    ygzf_ctx::Buf ids, vals;
+    if ((rc = kfdb_alloc_arena(c, cap, ids, vals))) return rc;
     if (top > 0) {
         PackedTransfer P(c);
         const size_t iT = P.add_in(K.slots.data(), sizeof(KfdbSlot) * S), iO = P.add_in(newOff.data(), sizeof(long long) * S);
         uint8_t *d;
-        if ((rc = P.upload(&d))) { (void) hipFree(ids); (void) hipFree(vals); return rc; }
+        if ((rc = P.upload(&d))) return rc;
         launch_kfdb_repack(c->stream, (int) S, (const KfdbSlot *) (d + iT), (const long long *) (d + iO), (const unsigned *) K.dIds.p, (const double *) K.dVals.p,
-                           (unsigned *) ids, (double *) vals);
+                           (unsigned *) ids.p, (double *) vals.p);
         hipError_t e = hipGetLastError();
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            (void) hipFree(ids); (void) hipFree(vals);
-            return fail(c, YGZF_ERR_HIP, "repacking the keyframe database failed: %s", hipGetErrorString(e));
-        }
+        if (e != hipSuccess) return fail(c, YGZF_ERR_HIP, "repacking the keyframe database failed: %s", hipGetErrorString(e));
     } else {
         HIPCHECK(c, hipStreamSynchronize(c->stream));
     }
-    (void) hipFree(K.dIds.p);
-    (void) hipFree(K.dVals.p);
-    K.dIds.p = ids; K.dIds.bytes = sizeof(uint32_t) * cap;
-    K.dVals.p = vals; K.dVals.bytes = sizeof(double) * cap;
+    K.dIds = std::move(ids);     // the repack has completed: the old arena goes
+    K.dVals = std::move(vals);
     K.cap = cap;
     K.top = top;
     for (size_t s = 0; s < S; s++)

@@ -26,8 +26,9 @@ static int kfs_reserve(ygzf_ctx *c, size_t bytes) {
     if (S.top + bytes <= S.cap) return YGZF_OK;
     size_t cap = S.liveBytes + bytes <= S.cap / 2 ? S.cap : S.cap * 2;
     while (S.liveBytes + bytes > cap) cap *= 2;
-    void *fresh = nullptr;
-    HIPCHECK(c, hipMalloc(&fresh, cap));
+    ygzf_ctx::Buf fresh;   // (a local: it frees itself on the error returns below)
+    int rc = ensure(c, fresh, cap);
+    if (rc) return rc;
     const size_t n = S.slots.size();
     std::vector<long long> newOff(n, 0);
     size_t top = 0;
@@ -36,17 +37,12 @@ static int kfs_reserve(ygzf_ctx *c, size_t bytes) {
         const ygzf_ctx::KfStore::Slot &L = S.slots[s];
         if (!L.live) continue;
         newOff[s] = (long long) top;
-        e = hipMemcpyAsync((uint8_t *) fresh + top, (const uint8_t *) S.dArena.p + L.off, L.bytes, hipMemcpyDeviceToDevice, c->stream);
+        e = hipMemcpyAsync((uint8_t *) fresh.p + top, (const uint8_t *) S.dArena.p + L.off, L.bytes, hipMemcpyDeviceToDevice, c->stream);
         top += L.bytes;
     }
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    if (e != hipSuccess) {
-        (void) hipFree(fresh);
-        return fail(c, YGZF_ERR_HIP, "repacking the keyframe store failed: %s", hipGetErrorString(e));
-    }
-    (void) hipFree(S.dArena.p);
-    S.dArena.p = fresh;
-    S.dArena.bytes = cap;
+    if (e != hipSuccess) return fail(c, YGZF_ERR_HIP, "repacking the keyframe store failed: %s", hipGetErrorString(e));
+    S.dArena = std::move(fresh);   // the repack has completed: the old arena goes
     S.cap = cap;
     S.top = top;
     for (size_t s = 0; s < n; s++)

@@ -79,8 +79,8 @@ static int plan_match_lds(ygzf_ctx *c, MatchArgs &A, int nPairs, size_t *ldsByte
 static int run_match(ygzf_ctx *c, MatchArgs &A, int nPairs, int dbgPair, const char *label) {
     int rc;
     if (c->matchDebug) {
-        if ((rc = ensure(c, c->dTmpC, (size_t) nPairs * 8 * sizeof(long long)))) return rc;
-        A.dbg = (long long *) c->dTmpC.p;
+        if ((rc = ensure(c, c->dMatchClk, (size_t) nPairs * 8 * sizeof(long long)))) return rc;
+        A.dbg = (long long *) c->dMatchClk.p;
     }
     size_t lds;
     if ((rc = plan_match_lds(c, A, nPairs, &lds))) return rc;
@@ -688,7 +688,7 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
     NodeSearchOut out;
     out.add(P, match12, N1);
     uint8_t *d;
-    if ((rc = P.upload(&d)) || (rc = ensure(c, c->dGen[9], N1 + 16)) || (rc = out.clear(c, P))) return rc;
+    if ((rc = P.upload(&d)) || (rc = ensure(c, c->dTriBinOf, N1 + 16)) || (rc = out.clear(c, P))) return rc;
     A.nEntries = ne1; A.nNodes = n_nodes; A.n1 = n1;
     A.off1 = (const int *) (d + iO1); A.idx1 = (const int *) (d + iI1); A.off2 = (const int *) (d + iO2); A.idx2 = (const int *) (d + iI2);
     A.keys1 = (const ygzf_kp *) (d + iK1); A.keys2 = (const ygzf_kp *) (d + iK2);
@@ -698,7 +698,7 @@ int ygzf_search_for_triangulation(ygzf_ctx *c, int n_nodes, const int *off1, con
     A.sf2 = (const float *) (d + iSf); A.sigma2 = (const float *) (d + iSg);
     A.onlyStereo = only_stereo != 0; A.checkOri = check_orientation != 0;
     A.match12 = out.match(P);
-    A.binOf = (unsigned char *) c->dGen[9].p;
+    A.binOf = (unsigned char *) c->dTriBinOf.p;
     A.nmatches = out.nmatches(P);
     A.hist = out.hist(P);
     {
@@ -1089,16 +1089,16 @@ int ygzf_features_in_area(ygzf_ctx *c, const ygzf_camera *cam, int n_keys, const
         A.outN = (int *) P.d_out(oN);
         A.outIdx = (int *) P.d_out(oI);
     } else {
-        if ((rc = ensure(c, c->dTmpA, kBytes + 64)) || (rc = ensure(c, c->dTmpB, qBytes + lBytes + 64)) || (rc = ensure(c, c->dTmpC, nPad + oBytes + 64)))
+        if ((rc = ensure(c, c->tmp.a, kBytes + 64)) || (rc = ensure(c, c->tmp.b, qBytes + lBytes + 64)) || (rc = ensure(c, c->tmp.c, nPad + oBytes + 64)))
             return rc;
-        if (n_keys > 0) HIPCHECK(c, hipMemcpyAsync(c->dTmpA.p, keys, kBytes, hipMemcpyHostToDevice, c->stream));
-        HIPCHECK(c, hipMemcpyAsync(c->dTmpB.p, xyr, qBytes, hipMemcpyHostToDevice, c->stream));
-        if (levels) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->dTmpB.p + qBytes, levels, lBytes, hipMemcpyHostToDevice, c->stream));
-        A.keys = (const ygzf_kp *) c->dTmpA.p;
-        A.xyr = (const float *) c->dTmpB.p;
-        A.levels = levels ? (const int *) ((uint8_t *) c->dTmpB.p + qBytes) : nullptr;
-        A.outN = (int *) c->dTmpC.p;
-        A.outIdx = (int *) ((uint8_t *) c->dTmpC.p + nPad);
+        if (n_keys > 0) HIPCHECK(c, hipMemcpyAsync(c->tmp.a.p, keys, kBytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHECK(c, hipMemcpyAsync(c->tmp.b.p, xyr, qBytes, hipMemcpyHostToDevice, c->stream));
+        if (levels) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->tmp.b.p + qBytes, levels, lBytes, hipMemcpyHostToDevice, c->stream));
+        A.keys = (const ygzf_kp *) c->tmp.a.p;
+        A.xyr = (const float *) c->tmp.b.p;
+        A.levels = levels ? (const int *) ((uint8_t *) c->tmp.b.p + qBytes) : nullptr;
+        A.outN = (int *) c->tmp.c.p;
+        A.outIdx = (int *) ((uint8_t *) c->tmp.c.p + nPad);
     }
     {
         ProfScope ps(c, KK_GRID);
@@ -1126,19 +1126,19 @@ int ygzf_distinctive_descriptors_batch(ygzf_ctx *c, int n_points, const int *obs
     HIPCHECK(c, hipSetDevice(c->device));
     int rc;
     const size_t offBytes = (4 * (size_t) (n_points + 1) + 15) & ~(size_t) 15;
-    if ((rc = ensure(c, c->dTmpA, offBytes + 4 * large.size() + 16)) || (rc = ensure(c, c->dTmpB, 4 * (size_t) n_points)) ||
-        (rc = ensure(c, c->dTmpC, 32 * (size_t) (total + 1))))
+    if ((rc = ensure(c, c->tmp.a, offBytes + 4 * large.size() + 16)) || (rc = ensure(c, c->tmp.b, 4 * (size_t) n_points)) ||
+        (rc = ensure(c, c->tmp.c, 32 * (size_t) (total + 1))))
         return rc;
-    HIPCHECK(c, hipMemcpyAsync(c->dTmpA.p, obs_off, 4 * (size_t) (n_points + 1), hipMemcpyHostToDevice, c->stream));
-    if (!large.empty()) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->dTmpA.p + offBytes, large.data(), 4 * large.size(), hipMemcpyHostToDevice, c->stream));
-    if (total > 0) HIPCHECK(c, hipMemcpyAsync(c->dTmpC.p, desc, 32 * (size_t) total, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(c->tmp.a.p, obs_off, 4 * (size_t) (n_points + 1), hipMemcpyHostToDevice, c->stream));
+    if (!large.empty()) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->tmp.a.p + offBytes, large.data(), 4 * large.size(), hipMemcpyHostToDevice, c->stream));
+    if (total > 0) HIPCHECK(c, hipMemcpyAsync(c->tmp.c.p, desc, 32 * (size_t) total, hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, KK_DISTINCTIVE);
-        launch_distinctive(c->stream, n_points, (const int *) c->dTmpA.p, (const uint8_t *) c->dTmpC.p, (int *) c->dTmpB.p, (int) large.size(),
-                           (const int *) ((uint8_t *) c->dTmpA.p + offBytes));
+        launch_distinctive(c->stream, n_points, (const int *) c->tmp.a.p, (const uint8_t *) c->tmp.c.p, (int *) c->tmp.b.p, (int) large.size(),
+                           (const int *) ((uint8_t *) c->tmp.a.p + offBytes));
     }
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(best_idx, c->dTmpB.p, 4 * (size_t) n_points, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(best_idx, c->tmp.b.p, 4 * (size_t) n_points, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
@@ -1160,13 +1160,13 @@ int ygzf_vocabulary_set(ygzf_ctx *c, int n_nodes, int depth_levels, const int *p
         for (int i = 1; i < n_nodes; i++) idx[(size_t) fill[parent[i]]++] = i;
     }
     int rc;
-    if ((rc = ensure(c, c->dVoc[0], off.size() * sizeof(int))) || (rc = ensure(c, c->dVoc[1], idx.size() * sizeof(int))) ||
-        (rc = ensure(c, c->dVoc[2], (size_t) n_nodes * 32)))
+    if ((rc = ensure(c, c->voc.childOff, off.size() * sizeof(int))) || (rc = ensure(c, c->voc.childIdx, idx.size() * sizeof(int))) ||
+        (rc = ensure(c, c->voc.nodeDesc, (size_t) n_nodes * 32)))
         return rc;
     c->vocNodes = 0;
-    HIPCHECK(c, hipMemcpyAsync(c->dVoc[0].p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(c->dVoc[1].p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(c->dVoc[2].p, desc, (size_t) n_nodes * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(c->voc.childOff.p, off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(c->voc.childIdx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(c->voc.nodeDesc.p, desc, (size_t) n_nodes * 32, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     c->vocNodes = n_nodes;
     c->vocLevels = depth_levels;
@@ -1181,16 +1181,16 @@ int ygzf_bow_transform(ygzf_ctx *c, int n, const uint8_t *desc, int levelsup, in
     if (!desc || !leaf_node || !level_node) return fail(c, YGZF_ERR_INVALID, "null argument");
     HIPCHECK(c, hipSetDevice(c->device));
     int rc;
-    if ((rc = ensure(c, c->dBow[0], (size_t) n * 32)) || (rc = ensure(c, c->dBow[1], (size_t) n * 4)) || (rc = ensure(c, c->dBow[2], (size_t) n * 4))) return rc;
-    HIPCHECK(c, hipMemcpyAsync(c->dBow[0].p, desc, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));
+    if ((rc = ensure(c, c->bow.desc, (size_t) n * 32)) || (rc = ensure(c, c->bow.leaf, (size_t) n * 4)) || (rc = ensure(c, c->bow.levelNode, (size_t) n * 4))) return rc;
+    HIPCHECK(c, hipMemcpyAsync(c->bow.desc.p, desc, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));
     {
         ProfScope ps(c, KK_BOW);
-        launch_bow_descend(c->stream, n, (const uint8_t *) c->dBow[0].p, (const int *) c->dVoc[0].p, (const int *) c->dVoc[1].p, (const uint8_t *) c->dVoc[2].p,
-                           c->vocLevels - levelsup, (int *) c->dBow[1].p, (int *) c->dBow[2].p);
+        launch_bow_descend(c->stream, n, (const uint8_t *) c->bow.desc.p, (const int *) c->voc.childOff.p, (const int *) c->voc.childIdx.p, (const uint8_t *) c->voc.nodeDesc.p,
+                           c->vocLevels - levelsup, (int *) c->bow.leaf.p, (int *) c->bow.levelNode.p);
     }
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(leaf_node, c->dBow[1].p, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(level_node, c->dBow[2].p, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(leaf_node, c->bow.leaf.p, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(level_node, c->bow.levelNode.p, (size_t) n * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }

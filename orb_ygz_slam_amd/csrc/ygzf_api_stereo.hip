@@ -22,6 +22,17 @@ static void fill_stereo_common(ygzf_ctx *c, StereoArgs &A, float mb, float mbf, 
     A.nBins = ((std::max(h, 1) - 1) >> A.binShift) + 1;
 }
 
+// the context's stereo buffers as the kernels take them: right-eye records of recStride per pair, results of outStride per pair
+static void stereo_buffers(const ygzf_ctx::Stereo &s, StereoArgs &A, long long recStride, long long outStride) {
+    A.rec = (StereoRec *) s.rec.p;
+    A.recStride = recStride;
+    A.binStart = (int *) s.bins.p;
+    A.uRight = (float *) s.uRight.p;
+    A.depth = (float *) s.depth.p;
+    A.sad = (int *) s.sad.p;
+    A.outStride = outStride;
+}
+
 int ygzf_stereo_batch(ygzf_ctx *c, float mb, float mbf) {
     if (!c) return YGZF_ERR_INVALID;
     if (c->held.frames < 2 || (c->held.frames & 1)) return fail(c, YGZF_ERR_STATE, "stereo needs an extracted batch of (left, right) frame pairs");
@@ -32,9 +43,9 @@ int ygzf_stereo_batch(ygzf_ctx *c, float mb, float mbf) {
     if (G.kpStride > 65535) return fail(c, YGZF_ERR_UNSUPPORTED, "more than 65535 keypoints per frame");
     int rc;
     const size_t per = (size_t) G.kpStride;
-    if ((rc = ensure(c, c->dSt[0], sizeof(StereoRec) * per * P + 64)) || (rc = ensure(c, c->dSt[1], 4 * per * P + 64)) ||
-        (rc = ensure(c, c->dSt[2], 4 * per * P + 64)) || (rc = ensure(c, c->dSt[3], 4 * per * P + 64)) ||
-        (rc = ensure(c, c->dStBins, sizeof(int) * kStereoBinInts * (size_t) P)))
+    if ((rc = ensure(c, c->st.rec, sizeof(StereoRec) * per * P + 64)) || (rc = ensure(c, c->st.uRight, 4 * per * P + 64)) ||
+        (rc = ensure(c, c->st.depth, 4 * per * P + 64)) || (rc = ensure(c, c->st.sad, 4 * per * P + 64)) ||
+        (rc = ensure(c, c->st.bins, sizeof(int) * kStereoBinInts * (size_t) P)))
         return rc;
     StereoArgs A;
     memset(&A, 0, sizeof A);
@@ -51,13 +62,7 @@ int ygzf_stereo_batch(ygzf_ctx *c, float mb, float mbf) {
     A.frame0 = 0;
     A.frameStep = 2;
     fill_stereo_common(c, A, mb, mbf, G.h);
-    A.rec = (StereoRec *) c->dSt[0].p;
-    A.recStride = (long long) per;
-    A.binStart = (int *) c->dStBins.p;
-    A.uRight = (float *) c->dSt[1].p;
-    A.depth = (float *) c->dSt[2].p;
-    A.sad = (int *) c->dSt[3].p;
-    A.outStride = (long long) per;
+    stereo_buffers(c->st, A, (long long) per, (long long) per);
     {
         ProfScope ps(c, KK_STEREO);
         launch_stereo(c->stream, A, P, G.kpStride, G.kpStride);
@@ -84,8 +89,8 @@ int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf) {
     if (G.kpStride > 65535) return fail(l, YGZF_ERR_UNSUPPORTED, "more than 65535 keypoints per frame");
     int rc;
     const size_t per = (size_t) G.kpStride;
-    if ((rc = ensure(l, l->dSt[0], sizeof(StereoRec) * per + 64)) || (rc = ensure(l, l->dSt[1], 4 * per + 64)) || (rc = ensure(l, l->dSt[2], 4 * per + 64)) ||
-        (rc = ensure(l, l->dSt[3], 4 * per + 64)) || (rc = ensure(l, l->dStBins, sizeof(int) * kStereoBinInts)))
+    if ((rc = ensure(l, l->st.rec, sizeof(StereoRec) * per + 64)) || (rc = ensure(l, l->st.uRight, 4 * per + 64)) || (rc = ensure(l, l->st.depth, 4 * per + 64)) ||
+        (rc = ensure(l, l->st.sad, 4 * per + 64)) || (rc = ensure(l, l->st.bins, sizeof(int) * kStereoBinInts)))
         return rc;
     StereoArgs A;
     memset(&A, 0, sizeof A);
@@ -108,13 +113,7 @@ int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf) {
     A.frame0 = 0;
     A.frameStep = 0;
     fill_stereo_common(l, A, mb, mbf, G.h);
-    A.rec = (StereoRec *) l->dSt[0].p;
-    A.recStride = (long long) per;
-    A.binStart = (int *) l->dStBins.p;
-    A.uRight = (float *) l->dSt[1].p;
-    A.depth = (float *) l->dSt[2].p;
-    A.sad = (int *) l->dSt[3].p;
-    A.outStride = (long long) per;
+    stereo_buffers(l->st, A, (long long) per, (long long) per);
     {
         ProfScope ps(l, KK_STEREO);
         launch_stereo(l->stream, A, 1, G.kpStride, G.kpStride);
@@ -135,8 +134,8 @@ int ygzf_stereo_fetch(ygzf_ctx *c, int pair, float *u_right, float *depth, int c
     if (n > cap) return fail(c, YGZF_ERR_INVALID, "capacity %d < %d left keypoints", cap, n);
     if (n == 0) return YGZF_OK;
     const size_t off = (size_t) pair * c->geo.kpStride;
-    HIPCHECK(c, hipMemcpyAsync(u_right, (float *) c->dSt[1].p + off, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(depth, (float *) c->dSt[2].p + off, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(u_right, (float *) c->st.uRight.p + off, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(depth, (float *) c->st.depth.p + off, 4 * (size_t) n, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
@@ -147,8 +146,8 @@ int ygzf_stereo_fetch_all(ygzf_ctx *c, float *u_right, float *depth, int stride)
     if (c->held.stereoPairs < 1) return fail(c, YGZF_ERR_STATE, "no stereo result");
     const int ks = c->geo.kpStride, P = c->held.stereoPairs;
     if (stride < ks) return fail(c, YGZF_ERR_INVALID, "stride %d < %d (ygzf_max_keypoints)", stride, ks);
-    HIPCHECK(c, hipMemcpy2DAsync(u_right, 4 * (size_t) stride, c->dSt[1].p, 4 * (size_t) ks, 4 * (size_t) ks, P, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpy2DAsync(depth, 4 * (size_t) stride, c->dSt[2].p, 4 * (size_t) ks, 4 * (size_t) ks, P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpy2DAsync(u_right, 4 * (size_t) stride, c->st.uRight.p, 4 * (size_t) ks, 4 * (size_t) ks, P, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpy2DAsync(depth, 4 * (size_t) stride, c->st.depth.p, 4 * (size_t) ks, 4 * (size_t) ks, P, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     return YGZF_OK;
 }
@@ -184,12 +183,12 @@ int ygzf_compute_stereo_matches(ygzf_ctx *c, const uint8_t *img_left, const uint
     forget_outputs(c);
     const size_t nk = (size_t) n_left + n_right;
     int counts[2] = {n_left, n_right};
-    if ((rc = ensure(c, c->dSt[0], sizeof(StereoRec) * (size_t) (n_right + 1))) || (rc = ensure(c, c->dSt[1], 4 * (size_t) n_left)) ||
-        (rc = ensure(c, c->dSt[2], 4 * (size_t) n_left)) || (rc = ensure(c, c->dSt[3], 4 * (size_t) n_left)) ||
-        (rc = ensure(c, c->dSt[4], sizeof(ygzf_kp) * nk + 64)) || (rc = ensure(c, c->dSt[5], 32 * nk + 64)) ||
-        (rc = ensure(c, c->dStBins, sizeof(int) * kStereoBinInts)))
+    if ((rc = ensure(c, c->st.rec, sizeof(StereoRec) * (size_t) (n_right + 1))) || (rc = ensure(c, c->st.uRight, 4 * (size_t) n_left)) ||
+        (rc = ensure(c, c->st.depth, 4 * (size_t) n_left)) || (rc = ensure(c, c->st.sad, 4 * (size_t) n_left)) ||
+        (rc = ensure(c, c->st.keys, sizeof(ygzf_kp) * nk + 64)) || (rc = ensure(c, c->st.desc, 32 * nk + 64)) ||
+        (rc = ensure(c, c->st.bins, sizeof(int) * kStereoBinInts)))
         return rc;
-    uint8_t *dk = (uint8_t *) c->dSt[4].p, *dd = (uint8_t *) c->dSt[5].p;
+    uint8_t *dk = (uint8_t *) c->st.keys.p, *dd = (uint8_t *) c->st.desc.p;
     HIPCHECK(c, hipMemcpyAsync(dk, keys_left, sizeof(ygzf_kp) * (size_t) n_left, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemcpyAsync(dd, desc_left, 32 * (size_t) n_left, hipMemcpyHostToDevice, c->stream));
     if (n_right > 0) {
@@ -213,20 +212,14 @@ int ygzf_compute_stereo_matches(ygzf_ctx *c, const uint8_t *img_left, const uint
     A.frame0 = 0;
     A.frameStep = 2;
     fill_stereo_common(c, A, mb, mbf, h);
-    A.rec = (StereoRec *) c->dSt[0].p;
-    A.recStride = n_right + 1;
-    A.binStart = (int *) c->dStBins.p;
-    A.uRight = (float *) c->dSt[1].p;
-    A.depth = (float *) c->dSt[2].p;
-    A.sad = (int *) c->dSt[3].p;
-    A.outStride = n_left;
+    stereo_buffers(c->st, A, n_right + 1, n_left);
     {
         ProfScope ps(c, KK_STEREO);
         launch_stereo(c->stream, A, 1, n_left, n_right);
     }
     HIPCHECK(c, hipGetLastError());
-    HIPCHECK(c, hipMemcpyAsync(u_right, c->dSt[1].p, 4 * (size_t) n_left, hipMemcpyDeviceToHost, c->stream));
-    HIPCHECK(c, hipMemcpyAsync(depth, c->dSt[2].p, 4 * (size_t) n_left, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(u_right, c->st.uRight.p, 4 * (size_t) n_left, hipMemcpyDeviceToHost, c->stream));
+    HIPCHECK(c, hipMemcpyAsync(depth, c->st.depth.p, 4 * (size_t) n_left, hipMemcpyDeviceToHost, c->stream));
     HIPCHECK(c, hipStreamSynchronize(c->stream));
     set_stereo_pairs(c, 0);
     return YGZF_OK;

@@ -19,6 +19,7 @@
 #include <limits>
 #include <mutex>
 #include <set>
+#include <type_traits>
 #include <unordered_map>
 
 #include "ygzf_plan.h"
@@ -62,14 +63,61 @@ struct ygzf_ctx {
     int maxW = 0, maxH = 0, maxBatch = 0;
     Geometry geo;
     std::string err;
-    // device buffers (grow-only)
+    // A device buffer (grow-only through ensure()).  It owns its allocation: the destructor frees it, so a buffer declared anywhere in the
+    // context -- or as a local, while an arena is rebuilt -- needs no line elsewhere to be given back.  ygzf_destroy selects the device and
+    // drains the stream before the context, and with it every Buf, is deleted.
     struct Buf {
         void *p = nullptr;
         size_t bytes = 0;
+        Buf() = default;
+        Buf(const Buf &) = delete;
+        Buf &operator=(const Buf &) = delete;
+        Buf(Buf &&o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+        Buf &operator=(Buf &&o) noexcept {
+            if (this != &o) {
+                (void) release();
+                p = o.p; bytes = o.bytes;
+                o.p = nullptr; o.bytes = 0;
+            }
+            return *this;
+        }
+        ~Buf() { (void) release(); }
+        hipError_t release() {
+            const hipError_t e = p ? hipFree(p) : hipSuccess;
+            p = nullptr;
+            bytes = 0;
+            return e;
+        }
     };
+    static_assert(!std::is_copy_constructible<Buf>::value, "a Buf owns its allocation: a copy would free it twice");
+    static_assert(std::is_nothrow_move_constructible<Buf>::value, "a Buf moves (the arenas are rebuilt in locals and moved into the context)");
     Buf dGeom, dXofs, dXalpha, dYofs, dYbeta, dImg0, dPyr, dCellCnt, dSlots, dK0, dV0, dK1, dV1, dXY, dLvlXY, dLvlScore,
-        dLvlCnt, dLvlBase, dLvlCand, dOutKp, dOutDesc, dOutCnt, dTmpA, dTmpB, dTmpC, dWorld, dOwner, dMatch, dNMatch, dPoses, dQp,
-        dGen[12], dVoc[3], dBow[3], dSia[8], dProcOrder, dF10[6], dSpill, dCarryPyr, dAl[5], dDso[8], dSt[6], dStBins, dCacheImg, dCachePyr, dDir[8], dFr[6], dSplitCnt, dSplitX, dPyrPlan, dPyrCols, dPyrRows, dPyrTiles, dOctHist;
+        dLvlCnt, dLvlBase, dLvlCand, dOutKp, dOutDesc, dOutCnt, dWorld, dOwner, dMatch, dNMatch, dPoses, dQp,
+        dProcOrder, dSpill, dCarryPyr, dCacheImg, dCachePyr, dSplitCnt, dSplitX, dPyrPlan, dPyrCols, dPyrRows, dPyrTiles, dOctHist;
+    // Scratch shared by the entry points that need a few arrays for the length of one call (the matcher's fallback uploads of ygzf_features_in_area,
+    // _distinctive_descriptors_batch and _descriptor_distance, level packing and re-pitching, the describe-list descriptors, the octree's and the
+    // aligner's YGZF_DEBUG clocks).  The rule: contents are valid only inside the entry point that wrote them, every such entry point synchronises
+    // before it returns, and no two uses of one buffer overlap inside one call.
+    struct Scratch { Buf a, b, c; } tmp;
+    Buf dMatchClk;                         // YGZF_DEBUG=match: k_match_last's phase stamps (not in tmp: ygzf_match_batch_prev returns without synchronising)
+    // One record per stage: the buffers of its entry points, named as the *Args records they feed name them.
+    struct Stereo { Buf rec, uRight, depth, sad, keys, desc, bins; } st;   // ComputeStereoMatches; keys / desc: the one-pair entry's uploads; results stay in uRight / depth for the fetches
+    struct Direct { Buf refSlot, refTcw7, refKp, mpWorld, pxCurr, searchLevel, success, patches; } dir;   // FindDirectProjection
+    struct Fast10 { Buf img, scores, rowCnt, xy, scoreList, nonmax; } f10;   // Thirdparty/fast (FAST_KEYPOINT keeps every level's lists in the last three)
+    struct Align { Buf levels, poses, patchCache, out; } al;   // ygzf_align_batch_prev: SiaLevel tables, poses, reference patches, results (ygzf_align_fetch)
+    struct Sia { Buf images, patchCache; } sia;                // ygzf_sia_run: both frames' levels from host memory, reference patches
+    struct Voc { Buf childOff, childIdx, nodeDesc; } voc;      // the vocabulary tree as CSR children lists + node descriptors
+    struct Bow { Buf desc, leaf, levelNode; } bow;             // ygzf_bow_transform
+    // The DSO / FAST_KEYPOINT grid detectors and ygzf_describe_keys (which uses list and angles only).  Three allocations serve one role in the
+    // two DSO detectors and another in FAST_KEYPOINT -- never both in one call -- and carry both names:
+    //   occXY_voteKey      the existing keys' packed level-0 positions | the vote key of every 5-px cell
+    //   cellCnt_lvlTotals  corners per grid cell                       | every level's corner totals
+    //   total_lvlOff       the pass's corner count                     | every level's offset into the corner lists
+    struct Grid {
+        Buf occ, cellXY, list, newXY, angles;   // occupancy (a bitmap / a byte per cell), winners per cell, describe-list entries, new keys' positions, angles
+        Buf occXY_voteKey, cellCnt_lvlTotals, total_lvlOff;
+    } grid;
+    Buf dTriBinOf;                         // SearchForTriangulation: the bin of every keypoint of the first keyframe
     int vocNodes = 0, vocLevels = 0;
     int cacheSlots = 0, cacheW = 0, cacheH = 0, cachePitch = 0;
     long long cachePyrBytes = 0;
@@ -217,9 +265,7 @@ static int fail(ygzf_ctx *c, int code, const char *fmt, ...) {
 // a buffer that grows loses its contents (the caller forgets what it held: apply_geometry, upload_frames)
 static int ensure(ygzf_ctx *c, ygzf_ctx::Buf &b, size_t bytes) {
     if (bytes <= b.bytes) return YGZF_OK;
-    if (b.p) HIPCHECK(c, hipFree(b.p));
-    b.p = nullptr;
-    b.bytes = 0;
+    HIPCHECK(c, b.release());
     HIPCHECK(c, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
     return YGZF_OK;
