@@ -18,6 +18,7 @@
 #include "kernels.h"
 #include "wave_ops.h"
 #include "describe_lds.h"
+#include "fast9_quad.h"
 #include "orb_pattern_table.h"
 
 namespace ygzf {
@@ -706,9 +707,11 @@ constexpr int kCornerCap = 512;  // corners listed per cell before the dense fal
 // dwords with a compile-time shift.  One v_lerp_u8 compares four bytes at once (bit 7 of (a + b + r) >> 1 is the carry of the 9-bit sum):
 //   bright_k  = bit7 lerp(ring_k, 255 - min(c + t, 255), 0)   <=> ring_k >  c + t
 //   !dark_k   = bit7 lerp(ring_k, 255 - max(c - t, 0),   1)   <=> ring_k >= c - t
-// and "9 contiguous of the circular 16" is evaluated bit-sliced over the 16 ring registers (3-input AND / OR trees: an arc of 9 is three
-// arcs of 3), so no per-pixel mask is ever assembled.  The low 7 bits of every byte are don't-care throughout.  Results (polarity per
-// pixel) are identical to fast9_test; the score / NMS passes work per listed corner.
+// and "9 contiguous of the circular 16" is evaluated bit-sliced over the 16 ring registers, so no per-pixel mask is ever assembled: 32 two- and
+// three-input operations per polarity (pairs that start at odd ring positions, runs of eight made of four pairs, and one of the two ring
+// pixels that flank a run -- csrc/fast9_quad.h, which holds the thresholds, the comparison and this network and also compiles for the host).
+// The low 7 bits of every byte are don't-care throughout.  Results (polarity per pixel) are identical to fast9_test; the score / NMS passes
+// work per listed corner.
 // ------------------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ unsigned fast9_quad(const unsigned *w, int pd, int t) {
 #define QROW(r) const unsigned a##r = w[(r) * pd], b##r = w[(r) * pd + 1], c##r = w[(r) * pd + 2];
@@ -724,51 +727,8 @@ __device__ __forceinline__ unsigned fast9_quad(const unsigned *w, int pd, int t)
     R[14] = AB(b5, a5, 2); R[2] = AB(c5, b5, 2);                          // dy = +2
     R[0] = b6;            R[15] = AB(b6, a6, 3);  R[1] = AB(c6, b6, 1);   // dy = +3
 #undef AB
-    // per-byte saturated thresholds on the complemented centre: 255 - min(c + t, 255) = max(nc - t, 0); 255 - max(c - t, 0) = min(nc + t, 255)
-    const unsigned nc = ~b3;
-    const unsigned ev = nc & 0x00FF00FFu, od = (nc >> 8) & 0x00FF00FFu;
-    const unsigned tt = (unsigned) t * 0x10001u;
-    const v2u tv = __builtin_bit_cast(v2u, tt), cap = __builtin_bit_cast(v2u, 0x00FF00FFu);
-    const unsigned nhiE = __builtin_bit_cast(unsigned, __builtin_elementwise_sub_sat(__builtin_bit_cast(v2u, ev), tv));
-    const unsigned nhiO = __builtin_bit_cast(unsigned, __builtin_elementwise_sub_sat(__builtin_bit_cast(v2u, od), tv));
-    const unsigned nloE = __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(v2u, ev) + tv, cap));
-    const unsigned nloO = __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(v2u, od) + tv, cap));
-    const unsigned nhi = nhiE | (nhiO << 8), nlo = nloE | (nloO << 8);
-    unsigned B[16], N[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        B[k] = __builtin_amdgcn_lerp(R[k], nhi, 0u);
-        N[k] = __builtin_amdgcn_lerp(R[k], nlo, 0x01010101u);
-    }
-    // "9 contiguous of the circular 16", bit-sliced: arcs of 3, then arcs of 9 = three arcs of 3, then the reduction over the 16 start
-    // positions -- 80 three-input operations.  Every one is written as v_bitop3_b32: on gfx950 that instruction issues at the full rate
-    // (2 cycles per wave64) while v_or3_b32 / v_and_or_b32, which the compiler would pick for `a | b | c`, issue at half rate like most
-    // three-operand integer instructions (profiles/micro/r02_valu_issue_rates.txt).
-#define AND3(a, b, c) __builtin_amdgcn_bitop3_b32(a, b, c, 0x80)
-#define OR3(a, b, c) __builtin_amdgcn_bitop3_b32(a, b, c, 0xFE)
-    unsigned A3[16], O3[16], A9[16], O9[16];
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        A3[k] = AND3(B[k], B[(k + 1) & 15], B[(k + 2) & 15]);
-        O3[k] = OR3(N[k], N[(k + 1) & 15], N[(k + 2) & 15]);
-    }
-#pragma unroll
-    for (int k = 0; k < 16; k++) {
-        A9[k] = AND3(A3[k], A3[(k + 3) & 15], A3[(k + 6) & 15]);
-        O9[k] = OR3(O3[k], O3[(k + 3) & 15], O3[(k + 6) & 15]);
-    }
-    unsigned bright = OR3(A9[0], A9[1], A9[2]), ndark = AND3(O9[0], O9[1], O9[2]);
-#pragma unroll
-    for (int k = 3; k < 15; k += 2) {
-        bright = OR3(bright, A9[k], A9[k + 1]);
-        ndark = AND3(ndark, O9[k], O9[k + 1]);
-    }
-    bright |= A9[15];
-    ndark &= O9[15];
-#undef AND3
-#undef OR3
-    const unsigned fb = bright & 0x80808080u, fd = ~(ndark | bright) & 0x80808080u;
-    return (fb >> 7) | (fd >> 6);   // per byte: 1 bright corner, 2 dark corner, 0 none
+    // thresholds, comparison and the arc network: csrc/fast9_quad.h (the same text runs on the host in tests/cpp/fast9_quad_cpu.hip)
+    return f9::polarity(R, f9::thresholds(b3, t));   // per byte: 1 bright corner, 2 dark corner, 0 none
 }
 
 // a / x for 0 <= a <= 64, 1 <= x <= 64 as (a * kRcp16[x]) >> 16 (exact in that range): lane -> (row, column) splits without the
@@ -835,7 +795,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
                 const unsigned long long m = __ballot(pb != 0);
                 if (m) {
                     if (pb) qlist[nQ + (int) __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u))] =
-                                pb | ((unsigned) y << 2) | ((unsigned) q << 10);
+                                __builtin_amdgcn_bitop3_b32(pb, (unsigned) y << 2, (unsigned) q << 10, 0xFE);   // a | b | c at the full rate (not v_or3_b32)
                     nQ += __popcll(m);
                 }
                 y += qy; q += qx;
