@@ -771,6 +771,68 @@ int ygzf_fuse_candidates_resident(ygzf_ctx *ctx, int n_kf, const ygzf_kf_ref *re
 int ygzf_fuse_sim3_candidates_resident(ygzf_ctx *ctx, int n_kf, const ygzf_kf_ref *refs, int n_points, const ygzf_fuse_points *pts,
                                        const uint8_t *skip, float th, int *best_idx, int *best_dist);
 
+/* ---- Frame::ComputeImagePyramid's undistortion: cv::remap(mImGray, ..., map1, map2, cv::INTER_LINEAR)  src/Frame.cc:775-805 ----
+ * The reference undistorts every camera image in front of ORBextractor::ComputePyramid whenever the calibration has a non-zero distortion
+ * coefficient (src/Frame.cc:139-142), with the CV_16SC2 / CV_16UC1 maps of cv::initUndistortRectifyMap; the right eye gets the same remap
+ * (:792-797).  Covered: 8-bit, one channel, INTER_LINEAR, BORDER_CONSTANT with value 0 -- the defaults, and the only combination the reference uses.
+ *   map_xy  (sx, sy) per destination pixel, interleaved int16, rows tight (map1)
+ *   map_tab fy * 32 + fx per destination pixel, fx, fy in 0..31, rows tight (map2; INTER_BITS = 5)
+ * With a0 = 32 - fx, a1 = fx, b0 = 32 - fy, b1 = fy and the taps p_jk = src(sy + j, sx + k), a tap outside the source counting as 0:
+ *     dst = (sum_jk b_j * a_k * p_jk + 512) >> 10
+ * This is OpenCV's (sum_jk W_jk * p_jk + 2^14) >> 15 with its weight table W = saturate_cast<short>(float(b_j / 32) * float(a_k / 32) * 32768):
+ * every product is the exact integer 32 * b * a, nothing rounds, and the weights sum to 32768 without OpenCV's sum correction.  The one exception is
+ * tab = 0: 32768 saturates to 32767 and the correction puts the missing 1 on the opposite tap; (32767 * p00 + p11 + 16384) >> 15 == p00 for
+ * all bytes, so the formula holds there too.  Coordinates are widened to 32 bits before sx + 1 is formed (no wrap at 32767).  A map_tab entry
+ * above 1023 reads past OpenCV's table: undefined there, refused here.  The arithmetic is restated from OpenCV's imgwarp.cpp, not pinned against
+ * a build of it yet (tools/make_golden_remap_opencv.py writes the fixture that does).
+ *
+ * A context holds up to two maps (map_id 0 and 1: one per eye) in buffers of their own: none of these calls changes what the context holds of
+ * an extraction batch -- ygzf_compute_pyramid_remapped excepted, which IS ygzf_compute_pyramid -- and with no map set nothing in the library
+ * behaves differently.
+ *
+ *   ygzf_remap_plan_host   how a map is cut up, without a context or a device (host arithmetic only; inspection and tests).  Output tiles of
+ *       geom[0] x geom[1] pixels, geom[2] x geom[3] of them, row-major.  Per tile t: boxes[4 t ..] = bx0, by0, bx1, by1, the bounding box of all
+ *       the tile's taps, unclipped and inclusive; classes[t] (ygzf_remap_class): INSIDE every tap lies inside the source, LDS some do not and
+ *       the box fits the staging budget of geom[4] bytes, GATHER the box does not fit, EMPTY no tap lies inside the source (zeros); staged[3 t ..] =
+ *       first staged column (bx0 rounded down to 4), row pitch, rows of the box as it is staged (pitch, rows = 0 for GATHER and EMPTY tiles).
+ *       records[y * w + x] = fx | fy << 5 | offset << 10 with offset = (sy - by0) * pitch + (sx - first staged column), the pixel's first tap inside
+ *       its tile's staged box (0 in GATHER and EMPTY tiles).  geom[5] = frames per run (one read of the map serves that many consecutive
+ *       frames), geom[6 .. 9] = tiles per class.  geom (10 ints), boxes, staged, classes and records may be NULL.
+ *   ygzf_remap_set         plans and uploads; replaces the id's previous map.  YGZF_ERR_INVALID -- and nothing changes -- for a map_id other than
+ *       0 / 1, null maps, a map_tab entry above 1023 or sizes beyond the context's max_width x max_height (source and destination alike).
+ *   ygzf_remap_clear       forgets the id's map (no error when none is set).
+ *   ygzf_remap_info        info[0 .. 3] = src_w, src_h, w, h, info[4 .. 7] = tiles per class (INSIDE, LDS, GATHER, EMPTY), info[8] = frames per run;
+ *       YGZF_ERR_STATE when the id holds no map.
+ *   ygzf_remap_set_path    which kernel runs the tiles (identical results under every setting):
+ *       YGZF_REMAP_PATH_AUTO    (default) the library's choice: INSIDE, LDS and EMPTY tiles staged, GATHER tiles gathered
+ *       YGZF_REMAP_PATH_LDS     k_remap_tiles wherever the box fits (GATHER tiles are still gathered)
+ *       YGZF_REMAP_PATH_GATHER  k_remap_gather for every tile
+ *   ygzf_remap_stats       of the context's last remap of any form: stats[0] = tiles k_remap_tiles staged, stats[1] = tiles it zeroed (EMPTY),
+ *       stats[2] = tiles k_remap_gather ran, stats[3] = runs (workgroups per tile).
+ *   ygzf_remap_batch_device  n_frames frames, device to device, asynchronous on the context's stream (ygzf_sync synchronises).  Frame f is
+ *       read at d_src + f * src_frame_stride (src_w x src_h, rows src_row_pitch apart) and written at d_dst + f * dst_frame_stride (w x h, rows
+ *       dst_row_pitch apart); only the w pixels of a destination row are written, never its padding, and only source pixels are read.  Any
+ *       pitch >= the width and any alignment work; with base, pitch and stride multiples of 4 on a side that side moves as 32-bit words -- what
+ *       ygzf_extract_batch_device asks of its frames, so the output feeds it directly.  The buffers must not overlap.
+ *   ygzf_remap_host        one host image up, remapped, back (the right eye's mImRight, :792-797).  Synchronises.
+ *   ygzf_compute_pyramid_remapped  ygzf_compute_pyramid of the remapped image: the raw src_w x src_h image is uploaded once, remapped into the
+ *       context's level 0, and the pyramid is built from there.  levels_out[0] (w x h, tight) receives the undistorted image -- what Frame keeps
+ *       as mImGray and mvImagePyramid[0] -- and levels_out[l] the levels above it.  ygzf_extract_resident and extract-ahead work after it exactly
+ *       as after ygzf_compute_pyramid. */
+typedef enum ygzf_remap_class { YGZF_REMAP_INSIDE = 0, YGZF_REMAP_LDS = 1, YGZF_REMAP_GATHER = 2, YGZF_REMAP_EMPTY = 3 } ygzf_remap_class;
+typedef enum ygzf_remap_path { YGZF_REMAP_PATH_AUTO = 0, YGZF_REMAP_PATH_LDS = 1, YGZF_REMAP_PATH_GATHER = 2 } ygzf_remap_path;
+int ygzf_remap_plan_host(int src_w, int src_h, int w, int h, const int16_t *map_xy, const uint16_t *map_tab, int *geom, int *boxes, int *staged,
+                         uint8_t *classes, uint32_t *records);
+int ygzf_remap_set(ygzf_ctx *ctx, int map_id, int src_w, int src_h, int w, int h, const int16_t *map_xy, const uint16_t *map_tab);
+int ygzf_remap_clear(ygzf_ctx *ctx, int map_id);
+int ygzf_remap_info(const ygzf_ctx *ctx, int map_id, int *info);
+int ygzf_remap_set_path(ygzf_ctx *ctx, int path);
+int ygzf_remap_stats(const ygzf_ctx *ctx, int *stats);
+int ygzf_remap_batch_device(ygzf_ctx *ctx, int map_id, const uint8_t *d_src, int n_frames, int src_row_pitch, size_t src_frame_stride, uint8_t *d_dst,
+                            int dst_row_pitch, size_t dst_frame_stride);
+int ygzf_remap_host(ygzf_ctx *ctx, int map_id, const uint8_t *src, int src_stride, uint8_t *dst, int dst_stride);
+int ygzf_compute_pyramid_remapped(ygzf_ctx *ctx, int map_id, const uint8_t *img, int stride, uint8_t *const *levels_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,6 +247,15 @@ def load_library(build_if_missing=True):
     L.ygzf_profile_enable.argtypes = [vp, C.c_int]
     L.ygzf_profile_read.argtypes = [vp, C.POINTER(C.c_char_p), fp, ip, C.c_int]
     L.ygzf_profile_reset.argtypes = [vp]
+    L.ygzf_remap_plan_host.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp]
+    L.ygzf_remap_set.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp]
+    L.ygzf_remap_clear.argtypes = [vp, C.c_int]
+    L.ygzf_remap_info.argtypes = [vp, C.c_int, vp]
+    L.ygzf_remap_set_path.argtypes = [vp, C.c_int]
+    L.ygzf_remap_stats.argtypes = [vp, vp]
+    L.ygzf_remap_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_size_t]
+    L.ygzf_remap_host.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
+    L.ygzf_compute_pyramid_remapped.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
     L.ygzf_stream.argtypes = [vp]
     L.ygzf_stream.restype = vp
     _lib = L
@@ -299,6 +308,39 @@ def octree_sort_plan_host(nfeatures, scale_factor, nlevels, w, h):
         raise YgzfError("ygzf_octree_sort_plan_host failed (%d)" % n)
     keys = ("l0", "n", "block", "cap", "lds_cand", "lds_bytes")
     return [dict(zip(keys, (int(v) for v in out[6 * i:6 * i + 6]))) for i in range(n)]
+
+
+REMAP_INSIDE, REMAP_LDS, REMAP_GATHER, REMAP_EMPTY = 0, 1, 2, 3             # ygzf_remap_class
+REMAP_PATH_AUTO, REMAP_PATH_LDS, REMAP_PATH_GATHER = 0, 1, 2                # ygzf_remap_path
+
+
+def _remap_maps(map_xy, map_tab):
+    """cv::remap's fixed-point maps as the C ABI takes them: (h, w, 2) int16 and (h, w) uint16, contiguous"""
+    map_xy = np.ascontiguousarray(map_xy, np.int16)
+    map_tab = np.ascontiguousarray(map_tab, np.uint16)
+    assert map_xy.ndim == 3 and map_xy.shape[2] == 2 and map_tab.shape == map_xy.shape[:2]
+    return map_xy, map_tab
+
+
+def remap_plan_host(src_w, src_h, map_xy, map_tab):
+    """ygzf_remap_plan_host: how an undistortion map (cv::remap, src/Frame.cc:775-805) is cut into tiles (host arithmetic only, no device).  Returns a
+    dict: `tile` (w, h), `tiles` (nx, ny), `lds_bytes`, `frames_per_run`, `count` (tiles per class), `boxes` [tiles, 4] = bx0, by0, bx1, by1
+    (inclusive, unclipped), `staged` [tiles, 3] = first staged column, pitch, rows, `classes` [tiles] and the packed `records` [h, w]."""
+    L = load_library()
+    map_xy, map_tab = _remap_maps(map_xy, map_tab)
+    h, w = map_tab.shape
+    geom = np.zeros(10, np.int32)
+    rc = L.ygzf_remap_plan_host(src_w, src_h, w, h, _p(map_xy), _p(map_tab), _p(geom), None, None, None, None)
+    if rc != 0:
+        raise YgzfError("ygzf_remap_plan_host failed (%d)" % rc)
+    nt = int(geom[2] * geom[3])
+    boxes, staged = np.zeros((nt, 4), np.int32), np.zeros((nt, 3), np.int32)
+    classes, records = np.zeros(nt, np.uint8), np.zeros((h, w), np.uint32)
+    rc = L.ygzf_remap_plan_host(src_w, src_h, w, h, _p(map_xy), _p(map_tab), _p(geom), _p(boxes), _p(staged), _p(classes), _p(records))
+    if rc != 0:
+        raise YgzfError("ygzf_remap_plan_host failed (%d)" % rc)
+    return {"tile": (int(geom[0]), int(geom[1])), "tiles": (int(geom[2]), int(geom[3])), "lds_bytes": int(geom[4]), "frames_per_run": int(geom[5]),
+            "count": [int(v) for v in geom[6:10]], "boxes": boxes, "staged": staged, "classes": classes, "records": records}
 
 
 class Extractor:
@@ -357,6 +399,53 @@ class Extractor:
         arr = (C.c_void_p * self.nlevels)(*[o.ctypes.data for o in outs])
         self._ck(self.L.ygzf_compute_pyramid(self.h, _p(img), w, h, w, arr))
         self._wh = (w, h, 1)                    # (with extract-ahead the extraction of this frame is the context's last batch)
+        return outs
+
+    # ---- Frame::ComputeImagePyramid's undistortion (cv::remap, src/Frame.cc:775-805)
+    def remap_set(self, map_id, src_w, src_h, map_xy, map_tab):
+        map_xy, map_tab = _remap_maps(map_xy, map_tab)
+        h, w = map_tab.shape
+        self._ck(self.L.ygzf_remap_set(self.h, map_id, src_w, src_h, w, h, _p(map_xy), _p(map_tab)))
+
+    def remap_clear(self, map_id):
+        self._ck(self.L.ygzf_remap_clear(self.h, map_id))
+
+    def remap_info(self, map_id):
+        """dict: src (w, h), dst (w, h), count (tiles per class), frames_per_run"""
+        v = np.zeros(9, np.int32)
+        self._ck(self.L.ygzf_remap_info(self.h, map_id, _p(v)))
+        return {"src": (int(v[0]), int(v[1])), "dst": (int(v[2]), int(v[3])), "count": [int(x) for x in v[4:8]], "frames_per_run": int(v[8])}
+
+    def remap_set_path(self, path):
+        self._ck(self.L.ygzf_remap_set_path(self.h, path))
+
+    def remap_stats(self):
+        """dict of the last remap: tiles staged / zeroed / gathered, runs"""
+        v = np.zeros(4, np.int32)
+        self._ck(self.L.ygzf_remap_stats(self.h, _p(v)))
+        return {"staged": int(v[0]), "zeroed": int(v[1]), "gathered": int(v[2]), "runs": int(v[3])}
+
+    def remap_batch_device(self, map_id, src_ptr, n, src_row_pitch, src_frame_stride, dst_ptr, dst_row_pitch, dst_frame_stride):
+        self._ck(self.L.ygzf_remap_batch_device(self.h, map_id, C.c_void_p(src_ptr), n, src_row_pitch, src_frame_stride, C.c_void_p(dst_ptr),
+                                                dst_row_pitch, dst_frame_stride))
+
+    def remap_host(self, map_id, img):
+        img = np.asarray(img, np.uint8)
+        if img.ndim != 2 or img.strides[1] != 1 or img.strides[0] < img.shape[1]:
+            img = np.ascontiguousarray(img)
+        w, h = self.remap_info(map_id)["dst"]
+        out = np.zeros((h, w), np.uint8)
+        self._ck(self.L.ygzf_remap_host(self.h, map_id, img.ctypes.data_as(C.c_void_p), int(img.strides[0]), _p(out), w))
+        return out
+
+    def compute_pyramid_remapped(self, map_id, img):
+        """levels of the undistorted image; level 0 is the undistorted image itself"""
+        img = np.ascontiguousarray(img, np.uint8)
+        w, h = self.remap_info(map_id)["dst"]
+        outs = [np.zeros(self.level_size(w, h, l)[::-1], np.uint8) for l in range(self.nlevels)]
+        arr = (C.c_void_p * self.nlevels)(*[o.ctypes.data for o in outs])
+        self._ck(self.L.ygzf_compute_pyramid_remapped(self.h, map_id, _p(img), img.shape[1], arr))
+        self._wh = (w, h, 1)
         return outs
 
     def extract(self, img):

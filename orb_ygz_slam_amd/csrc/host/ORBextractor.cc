@@ -90,6 +90,7 @@ ygzf_ctx *ORBextractor::ensureContext(int w, int h) {
         return nullptr;
     }
     mAheadOn = false;
+    mMapsUploaded = false;   // (the maps lived in the context that has just gone)
     mCtxW = w;
     mCtxH = h;
     return mCtx;
@@ -124,20 +125,74 @@ cv::Mat ORBextractor::acquireLevel(int level, int rows, int cols) {
     return m;
 }
 
-void ORBextractor::ComputePyramid(cv::Mat image) {
+void ORBextractor::ComputePyramid(cv::Mat image) { computePyramid(image, false); }
+
+void ORBextractor::ComputePyramidUndistorted(cv::Mat raw) { computePyramid(raw, true); }
+
+#ifndef CV_16UC1
+#define CV_16UC1 2
+#endif
+#ifndef CV_16SC2
+#define CV_16SC2 11
+#endif
+
+bool ORBextractor::SetUndistortMaps(const cv::Mat &map1, const cv::Mat &map2) {
+    if (map1.empty() || map2.empty() || map1.type() != CV_16SC2 || map2.type() != CV_16UC1 || map1.rows != map2.rows || map1.cols != map2.cols) {
+        ygzf_host::report_failure("ygz::ORBextractor::SetUndistortMaps", "the maps must be CV_16SC2 and CV_16UC1 of one size (cv::initUndistortRectifyMap(..., CV_16SC2, map1, map2))");
+        return false;
+    }
+    if (map1.data == mMap1.data && map2.data == mMap2.data && map1.rows == mMap1.rows && map1.cols == mMap1.cols) return true;   // the ones it holds
+    mMap1 = map1.isContinuous() ? map1 : map1.clone();
+    mMap2 = map2.isContinuous() ? map2 : map2.clone();
+    mMapsUploaded = false;
+    return true;
+}
+
+ygzf_ctx *ORBextractor::ensureMaps(int rawW, int rawH) {
+    if (mMap1.empty()) {
+        ygzf_host::report_failure("ygz::ORBextractor", "no undistortion maps (SetUndistortMaps)");
+        return nullptr;
+    }
+    ygzf_ctx *c = ensureContext(std::max(rawW, mMap1.cols), std::max(rawH, mMap1.rows));
+    if (!c) return nullptr;
+    if (mMapsUploaded && rawW == mMapSrcW && rawH == mMapSrcH) return c;
+    if (ygzf_remap_set(c, 0, rawW, rawH, mMap1.cols, mMap1.rows, (const int16_t *) mMap1.data, (const uint16_t *) mMap2.data) != YGZF_OK) {
+        ygzf_host::report_failure("ygz::ORBextractor (undistortion maps)", ygzf_last_error(c));
+        return nullptr;
+    }
+    mMapsUploaded = true;
+    mMapSrcW = rawW;
+    mMapSrcH = rawH;
+    return c;
+}
+
+bool ORBextractor::Undistort(const cv::Mat &raw, cv::Mat &dst) {
+    if (raw.empty()) return false;
+    ygzf_ctx *c = ensureMaps(raw.cols, raw.rows);
+    if (!c) return false;
+    dst.create(mMap1.rows, mMap1.cols, CV_8UC1);
+    if (ygzf_remap_host(c, 0, raw.data, (int) raw.step, dst.data, (int) dst.step) != YGZF_OK) {
+        ygzf_host::report_failure("ygz::ORBextractor::Undistort", ygzf_last_error(c));
+        return false;
+    }
+    return true;
+}
+
+void ORBextractor::computePyramid(const cv::Mat &image, bool undistort) {
     if (image.empty()) return;
-    ygzf_ctx *c = ensureContext(image.cols, image.rows);
+    ygzf_ctx *c = undistort ? ensureMaps(image.cols, image.rows) : ensureContext(image.cols, image.rows);
     if (!c) return;
+    const int w = undistort ? mMap1.cols : image.cols, h = undistort ? mMap1.rows : image.rows;   // of level 0
     std::vector<uint8_t *> out(nlevels);
     mResidentLevel0 = cv::Mat();
     for (int l = 0; l < nlevels; l++) {
         int lw, lh;
-        ygzf_level_size(c, image.cols, image.rows, l, &lw, &lh);
+        ygzf_level_size(c, w, h, l, &lw, &lh);
         mvImagePyramid[l] = cv::Mat();                  // this pyramid's own hold on its previous level buffer goes first
         mvImagePyramid[l] = acquireLevel(l, lh, lw);    // a buffer nobody else refers to: Frames keep (shared) references to earlier levels
         out[l] = mvImagePyramid[l].data;
     }
-    mHeldImage = image;
+    mHeldImage = undistort ? mvImagePyramid[0] : image;   // what the context holds as level 0
     mVerifiedData = nullptr;
     {   // extract-ahead follows the tracker's habit: on when the previous pyramid's image was extracted, off when it was not
         const bool want = mExtractAhead && mExtractedSincePyramid;
@@ -147,8 +202,11 @@ void ORBextractor::ComputePyramid(cv::Mat image) {
         }
         mExtractedSincePyramid = false;
     }
-    if (ygzf_compute_pyramid(c, image.data, image.cols, image.rows, (int) image.step, out.data()) != YGZF_OK) {
-        ygzf_host::report_failure("ygz::ORBextractor::ComputePyramid", ygzf_last_error(c));
+    const int rc = undistort ? ygzf_compute_pyramid_remapped(c, 0, image.data, (int) image.step, out.data())
+                             : ygzf_compute_pyramid(c, image.data, image.cols, image.rows, (int) image.step, out.data());
+    if (rc != YGZF_OK) {
+        ygzf_host::report_failure(undistort ? "ygz::ORBextractor::ComputePyramidUndistorted" : "ygz::ORBextractor::ComputePyramid", ygzf_last_error(c));
+        if (undistort) mHeldImage = cv::Mat();
         return;
     }
     mResidentLevel0 = mvImagePyramid[0];   // the context still holds this image and its pyramid (see operator()(Frame*, ...))

@@ -85,6 +85,17 @@ public:
     // its pyramid on the device; nullptr otherwise.  The shells that read Frame images (SparseImgAlign::run, FindDirectProjection) pass it to
     // the image cache, which then copies device to device instead of uploading the image a second time.
     ygzf_ctx *ResidentContext(const cv::Mat &level0) const;
+    // The undistortion Frame::ComputeImagePyramid runs in front of ComputePyramid (src/Frame.cc:775-805: cv::remap(mImGray, ..., map1, map2,
+    // cv::INTER_LINEAR)) on the device (include/ygzf.h, ygzf_remap_*; host/FrameUndistort.cc is that member bound to these three).
+    // SetUndistortMaps: the CV_16SC2 / CV_16UC1 maps of cv::initUndistortRectifyMap, of one size; they are planned and uploaded on the next use
+    // (the source size is the first raw image's).  false, with a diagnostic, for any other type or differing sizes; handing over the maps the
+    // extractor already holds costs nothing.
+    bool SetUndistortMaps(const cv::Mat &map1, const cv::Mat &map2);
+    // ComputePyramid of the undistorted image: the raw image crosses the link once, mvImagePyramid[0] is the undistorted image.  Everything
+    // else -- the resident pyramid operator()(Frame *, ...) extracts from, the extract-ahead habit, ResidentContext -- as after ComputePyramid.
+    void ComputePyramidUndistorted(cv::Mat raw);
+    // cv::remap(raw, dst, map1, map2, cv::INTER_LINEAR) of one more image with the same maps (the right eye's mImRight, :792-797); false on failure.
+    bool Undistort(const cv::Mat &raw, cv::Mat &dst);
 
 protected:
     int nfeatures = 0;
@@ -105,6 +116,11 @@ protected:
 
 private:
     ygzf_ctx *ensureContext(int w, int h);
+    void computePyramid(const cv::Mat &image, bool undistort);
+    ygzf_ctx *ensureMaps(int rawW, int rawH);   // the context, with the maps uploaded for raw images of this size; nullptr (reported) on failure
+    cv::Mat mMap1, mMap2;             // SetUndistortMaps' (continuous; headers of the caller's buffers where those are)
+    bool mMapsUploaded = false;       // the context holds them as map 0, planned for mMapSrcW x mMapSrcH sources
+    int mMapSrcW = 0, mMapSrcH = 0;
     ygzf_ctx *mCtx = nullptr;
     cv::Mat mResidentLevel0;     // level 0 of the pyramid the context still holds on the device (set by ComputePyramid), or empty
     int mCtxW = 0, mCtxH = 0;

@@ -53,6 +53,8 @@ inline int mat_refcount(const cv::Mat &m) {
 #define CV_8U 0
 #define CV_8UC1 0
 #define CV_32F 5
+#define CV_16UC1 2    // the types of cv::initUndistortRectifyMap's fixed-point maps (ORBextractor::SetUndistortMaps)
+#define CV_16SC2 11
 
 #include <set>
 namespace cv {
@@ -92,7 +94,7 @@ public:
         return m;
     }
 private:
-    static size_t esz(int type) { return type == CV_32F ? 4 : 1; }
+    static size_t esz(int type) { return type == CV_32F || type == CV_16SC2 ? 4 : type == CV_16UC1 ? 2 : 1; }
     int type_ = CV_8U;
     std::shared_ptr<unsigned char> hold_;
 };

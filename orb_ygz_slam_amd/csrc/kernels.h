@@ -2,6 +2,7 @@
 #ifndef YGZF_KERNELS_H
 #define YGZF_KERNELS_H
 #include "ygzf_internal.h"
+#include "ygzf_remap_plan.h"
 
 namespace ygzf {
 
@@ -476,6 +477,23 @@ size_t sia_stage_bytes(size_t featBytes, size_t largestLevelBytes);
 hipError_t sia_prepare(size_t ldsBytes);
 void launch_sia_precompute(hipStream_t st, const SiaArgs &A, int nPairs, int maxN);
 void launch_sia(hipStream_t st, const SiaArgs &A, int nPairs, size_t ldsBytes);
+
+// ---- cv::remap, fixed-point bilinear (remap_kernels.hip; the plan: ygzf_remap_plan.h) ----
+// One launch of either kernel: tile list[i] (null: tile i) of the map, for the frames [0, nFrames) in runs of framesPerRun.  src / dst: frame 0,
+// rows and frames the given bytes apart; srcAligned / dstAligned: base, row pitch and frame stride are all multiples of 4 (32-bit accesses allowed).
+struct RemapArgs {
+    const uint32_t *rec, *xy;       // [h][recPitch]
+    const RemapTileRec *tiles;
+    const int *list;
+    int w, h, recPitch, tilesX, srcW, srcH;
+    const uint8_t *src;
+    long long srcPitch, srcStride;
+    uint8_t *dst;
+    long long dstPitch, dstStride;
+    int nFrames, framesPerRun, srcAligned, dstAligned;
+};
+void launch_remap_tiles(hipStream_t st, const RemapArgs &A, int nTiles);    // Inside / Lds / Empty tiles only (the box is staged in LDS)
+void launch_remap_gather(hipStream_t st, const RemapArgs &A, int nTiles);   // any tile (bounds-checked byte loads from global memory)
 
 }  // namespace ygzf
 #endif

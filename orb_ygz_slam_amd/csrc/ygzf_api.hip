@@ -466,6 +466,59 @@ int upload_frames(ygzf_ctx *c, const uint8_t *imgs, int nFrames, int w, int h, i
     return YGZF_OK;
 }
 
+// The rest of ygzf_compute_pyramid once level 0 of the one frame lies in fs: the pyramid chain, the levels' way back, the queued extraction.
+// hostLevel0: the caller's image IS level 0 (rows `stride` apart): it is copied on the host while the other levels are on the link; null: level 0 was
+// made on the device (ygzf_compute_pyramid_remapped) and comes back with them.
+int pyramid_readback(ygzf_ctx *c, const FrameSet &fs, int w, int h, const uint8_t *hostLevel0, int stride, uint8_t *const *levels_out) {
+    int rc;
+    const uint8_t *img = hostLevel0;
+    const int first = hostLevel0 ? 1 : 0;
+    const Geometry &G = c->geo;
+    const int L = c->tab.cfg.nlevels;
+    if ((rc = pyramid_chain(c, fs, 1)) || (rc = mark_pyramid_done(c))) return rc;
+    HIPCHECK(c, hipGetLastError());
+    // The levels go back tight (pitch = width) into caller memory that is pageable as a rule (cv::Mat buffers).  Eight pitched device-to-host
+    // copies took 10-13 ms for a 752x480 pyramid (the copy engine works an odd-width pitched copy off row by row, into page-locked memory
+    // as well): the levels are packed on the device and leave in one linear copy through the context's page-locked staging buffer.
+    // Level 0 IS the caller's image: it is copied on the host while the other levels are on the link.
+    unsigned offs[kMaxLevels + 1];
+    offs[0] = 0;
+    offs[1] = first ? 0u : (unsigned) w * (unsigned) h;
+    for (int l = 1; l < L; l++) offs[l + 1] = offs[l] + (unsigned) G.lv[l].w * (unsigned) G.lv[l].h;
+    const size_t total = offs[L];
+    if ((rc = ensure_stage(c, total + 64)) || (rc = ensure(c, c->tmp.c, total + 64))) return rc;
+    // (the page-locked staging area as the device addresses it: the packing kernel -- 16-byte stores -- writes the levels over the link itself, on the
+    // stream the copy would have taken; a byte-per-thread packing kernel doing so was slower than the copy engine: ComputePyramid 94 -> 97 us)
+    const bool linkPack = c->hStageDev != nullptr && c->linkKernels && c->pyrLink;
+    if (!linkPack) {
+        launch_pack_levels(c->stream, fs, (const LevelGeom *) c->dGeom.p, first, L, offs, (uint8_t *) c->tmp.c.p);
+        HIPCHECK(c, hipGetLastError());
+    }
+    // extract-ahead: FAST / octree / descriptors of this image are queued behind the pyramid now and run while the levels travel back on
+    // the copy stream and the caller works on them (a Frame constructor clones them); ygzf_extract_resident then only collects the results.
+    // (Measured alternatives: the copy on the context's own stream with an event behind it and the extraction queued after that event --
+    // the event is reported 30 us later than on a stream that ends there; two half copies to overlap the host's copy-out -- slower too.)
+    hipStream_t rd = c->stream;
+    bool ahead = false;
+    if (c->extractAhead && c->streamCopy) {
+        HIPCHECK(c, hipEventRecord(c->evPyramid, c->stream));
+        HIPCHECK(c, hipStreamWaitEvent(c->streamCopy, c->evPyramid, 0));
+        rd = c->streamCopy;
+        ahead = true;
+    }
+    if (total && linkPack) {
+        launch_pack_levels(rd, fs, (const LevelGeom *) c->dGeom.p, first, L, offs, (uint8_t *) c->hStageDev);
+        HIPCHECK(c, hipGetLastError());
+    } else if (total) HIPCHECK(c, hipMemcpyAsync(c->hStage, c->tmp.c.p, total, hipMemcpyDeviceToHost, rd));
+    if (ahead && (rc = run_extract(c, fs, 1, true))) return rc;   // (queued after the copy so that the copy starts while these launches are issued)
+    if (img && (levels_out[0] != img || stride != w))
+        for (int y = 0; y < h; y++) memcpy(levels_out[0] + (size_t) y * w, img + (size_t) y * stride, (size_t) w);
+    HIPCHECK(c, hipStreamSynchronize(rd));
+    for (int l = first; l < L; l++) memcpy(levels_out[l], c->hStage + offs[l], offs[l + 1] - offs[l]);
+    pyramid_computed(c, w, h, ahead);
+    return YGZF_OK;
+}
+
 extern "C" {
 
 int ygzf_create(int device, const ygzf_extractor_cfg *cfg, int max_width, int max_height, int max_batch, ygzf_ctx **out) {
@@ -663,49 +716,7 @@ int ygzf_compute_pyramid(ygzf_ctx *c, const uint8_t *img, int w, int h, int stri
     // leaves dPyr before this frame's pyramid is written over it
     if (c->extractAhead && c->streamCopy && (rc = save_carry_pyramid(c))) return rc;
     if ((rc = upload_frames(c, img, 1, w, h, stride, 0, &fs))) return rc;
-    const Geometry &G = c->geo;
-    const int L = c->tab.cfg.nlevels;
-    if ((rc = pyramid_chain(c, fs, 1)) || (rc = mark_pyramid_done(c))) return rc;
-    HIPCHECK(c, hipGetLastError());
-    // The levels go back tight (pitch = width) into caller memory that is pageable as a rule (cv::Mat buffers).  Eight pitched device-to-host
-    // copies took 10-13 ms for a 752x480 pyramid (the copy engine works an odd-width pitched copy off row by row, into page-locked memory
-    // as well): the levels are packed on the device and leave in one linear copy through the context's page-locked staging buffer.
-    // Level 0 IS the caller's image: it is copied on the host while the other levels are on the link.
-    unsigned offs[kMaxLevels + 1];
-    offs[0] = offs[1] = 0;
-    for (int l = 1; l < L; l++) offs[l + 1] = offs[l] + (unsigned) G.lv[l].w * (unsigned) G.lv[l].h;
-    const size_t total = offs[L];
-    if ((rc = ensure_stage(c, total + 64)) || (rc = ensure(c, c->tmp.c, total + 64))) return rc;
-    // (the page-locked staging area as the device addresses it: the packing kernel -- 16-byte stores -- writes the levels over the link itself, on the
-    // stream the copy would have taken; a byte-per-thread packing kernel doing so was slower than the copy engine: ComputePyramid 94 -> 97 us)
-    const bool linkPack = c->hStageDev != nullptr && c->linkKernels && c->pyrLink;
-    if (!linkPack) {
-        launch_pack_levels(c->stream, fs, (const LevelGeom *) c->dGeom.p, 1, L, offs, (uint8_t *) c->tmp.c.p);
-        HIPCHECK(c, hipGetLastError());
-    }
-    // extract-ahead: FAST / octree / descriptors of this image are queued behind the pyramid now and run while the levels travel back on
-    // the copy stream and the caller works on them (a Frame constructor clones them); ygzf_extract_resident then only collects the results.
-    // (Measured alternatives: the copy on the context's own stream with an event behind it and the extraction queued after that event --
-    // the event is reported 30 us later than on a stream that ends there; two half copies to overlap the host's copy-out -- slower too.)
-    hipStream_t rd = c->stream;
-    bool ahead = false;
-    if (c->extractAhead && c->streamCopy) {
-        HIPCHECK(c, hipEventRecord(c->evPyramid, c->stream));
-        HIPCHECK(c, hipStreamWaitEvent(c->streamCopy, c->evPyramid, 0));
-        rd = c->streamCopy;
-        ahead = true;
-    }
-    if (total && linkPack) {
-        launch_pack_levels(rd, fs, (const LevelGeom *) c->dGeom.p, 1, L, offs, (uint8_t *) c->hStageDev);
-        HIPCHECK(c, hipGetLastError());
-    } else if (total) HIPCHECK(c, hipMemcpyAsync(c->hStage, c->tmp.c.p, total, hipMemcpyDeviceToHost, rd));
-    if (ahead && (rc = run_extract(c, fs, 1, true))) return rc;   // (queued after the copy so that the copy starts while these launches are issued)
-    if (levels_out[0] != img || stride != w)
-        for (int y = 0; y < h; y++) memcpy(levels_out[0] + (size_t) y * w, img + (size_t) y * stride, (size_t) w);
-    HIPCHECK(c, hipStreamSynchronize(rd));
-    for (int l = 1; l < L; l++) memcpy(levels_out[l], c->hStage + offs[l], offs[l + 1] - offs[l]);
-    pyramid_computed(c, w, h, ahead);
-    return YGZF_OK;
+    return pyramid_readback(c, fs, w, h, img, stride, levels_out);
 }
 
 int ygzf_extract_batch_device(ygzf_ctx *c, const uint8_t *d_imgs, int n_frames, int w, int h, int row_pitch, size_t frame_stride) {

@@ -9,6 +9,7 @@
 //   ygzf_api_stereo.hip  Frame::ComputeStereoMatches
 //   ygzf_api_kfdb.hip    KeyFrameDatabase: the BowVector store and its query
 //   ygzf_api_kfstore.hip the resident keyframes: put / erase / clear / grid (their searches are in ygzf_api_match.hip beside the non-resident ones)
+//   ygzf_api_remap.hip   Frame::ComputeImagePyramid's undistortion (cv::remap): maps, device / host / pyramid forms (the plan: ygzf_remap_plan.hip)
 #ifndef YGZF_CTX_H
 #define YGZF_CTX_H
 #include <cmath>
@@ -200,6 +201,22 @@ struct ygzf_ctx {
         std::unordered_map<uint64_t, int> slotOf;   // live keys
         std::set<int> freeSlots;                    // reused lowest first
     } kfs;
+    // The undistortion maps (ygzf_api_remap.hip; src/Frame.cc:775-805).  Buffers of its own, as the database above: no other entry point reads or
+    // writes them.  Per map id (one per eye) the plan's device tables; `in` / `out`: the raw image of ygzf_remap_host and
+    // ygzf_compute_pyramid_remapped, and the former's result, tight.  stats: what the last launch ran (ygzf_remap_stats).
+    struct Remap {
+        struct Map {
+            Buf rec, xy, tiles, listStaged, listGather;   // the lists: tile indices in launch order, per kernel
+            bool set = false;
+            int srcW = 0, srcH = 0, w = 0, h = 0, recPitch = 0, tilesX = 0, tilesY = 0, nStaged = 0, nGather = 0;
+            int count[4] = {0, 0, 0, 0};   // tiles per RemapClass
+        } map[kRemapMaps];
+        Buf in, out;
+        int path = 0;                      // ygzf_remap_path
+        int framesPerRun = (int) forced("remap_frames_per_run", kRemapFramesPerRun);
+        bool xcdOrder = forced("remap_xcd_order", 1) != 0;   // staged tiles listed so that neighbours share an XCD (ygzf_remap_set)
+        int stats[4] = {0, 0, 0, 0};
+    } remap;
     Held held;                             // what the buffers hold between calls (the transitions below ygzf_ctx are its only writers)
     int img0Pitch = 0;
     // timing
@@ -482,6 +499,7 @@ YGZF_HIDDEN int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames);
 YGZF_HIDDEN int pyramid_chain(ygzf_ctx *c, const ygzf::FrameSet &fs, int nFrames);
 YGZF_HIDDEN int stereo_across(ygzf_ctx *l, ygzf_ctx *r, float mb, float mbf);   // ygzf_api_stereo.hip
 YGZF_HIDDEN int mark_pyramid_done(ygzf_ctx *c);
+YGZF_HIDDEN int pyramid_readback(ygzf_ctx *c, const ygzf::FrameSet &fs, int w, int h, const uint8_t *hostLevel0, int stride, uint8_t *const *levels_out);
 YGZF_HIDDEN int run_extract(ygzf_ctx *c, const ygzf::FrameSet &fs, int nFrames, bool pyramidReady = false);
 YGZF_HIDDEN int upload_rows(ygzf_ctx *c, void *dst, size_t dstPitch, const uint8_t *src, size_t srcPitch, int w, size_t rows);
 // ygzf_api_match.hip: a keyframe's argument checks (needSigma: mvInvLevelSigma2 is read) and the pose-free part of its device record
