@@ -418,7 +418,7 @@ __device__ __forceinline__ void sia_accumulate_feature(const SiaArgs &A, const S
     float J[12];
     {
         float4 ja, jb;
-        if (A.jacLds) { ja = jacp[0]; jb = jacp[1]; }
+        if (A.lds.jac) { ja = jacp[0]; jb = jacp[1]; }
         else jac_terms(xr, ja, jb);
         J[0] = -ja.x; J[1] = 0.f; J[2] = ja.y; J[3] = ja.z; J[4] = ja.w; J[5] = jb.x;
         J[6] = 0.f; J[7] = -ja.x; J[8] = jb.y; J[9] = jb.z; J[10] = -ja.z; J[11] = jb.w;
@@ -526,9 +526,10 @@ __global__ __launch_bounds__(kSiaBlock) void k_sia_run(SiaArgs A) {
         s_iters = 0;
         for (int i = 0; i < 36; i++) s_H[i] = 0;
     }
-    float2 *s_uv = (float2 *) (s_feat + A.ldsFeat);
-    float4 *s_jac = (float4 *) (s_uv + A.ldsFeat);   // two per feature when A.jacLds
-    uint8_t *s_img = (uint8_t *) s_feat + A.stageOff;   // A.stageBytes: the current image of a level that fits (coarse levels)
+    const SiaPtrs P = sia_carve(s_feat, A.lds);
+    float2 *s_uv = P.uv;
+    float4 *s_jac = P.jac;     // two per feature when A.lds.jac
+    uint8_t *s_img = P.img;    // A.lds.stageBytes: the current image of a level that fits (coarse levels)
     if (!A.perLevel && N > 2 * kSiaBlock)   // (only pairs beyond the register form ever read the cache)
         for (int j = 0; j < 9; j++)
             for (int i = tid; i < N; i += kSiaBlock) rowCache[j * plane + i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -548,7 +549,7 @@ __global__ __launch_bounds__(kSiaBlock) void k_sia_run(SiaArgs A) {
             } else
                 se3_act(Tref, world + 3 * (size_t) i, xyz);
             s_feat[i] = make_float4(xyz[0], xyz[1], xyz[2], 0.f);
-            if (A.jacLds) jac_terms(xyz, s_jac[2 * i], s_jac[2 * i + 1]);
+            if (A.lds.jac) jac_terms(xyz, s_jac[2 * i], s_jac[2 * i + 1]);
         }
     }
     __syncthreads();
@@ -579,7 +580,7 @@ __global__ __launch_bounds__(kSiaBlock) void k_sia_run(SiaArgs A) {
         // 5 x 5-byte patch gathers then cost LDS bank cycles instead of 64 scattered cache lines per load instruction (the texture path
         // works such a gather off one line at a time, and the eight waves of the workgroup queue behind each other).
         const unsigned imgBytes = (unsigned) Lc.h * (unsigned) Lc.pitch;
-        const bool staged = imgBytes + 8 <= (unsigned) A.stageBytes;
+        const bool staged = imgBytes + 8 <= (unsigned) A.lds.stageBytes;
         if (staged) {
             // every level image the library hands to this kernel starts dword-aligned and is followed by >= 3 bytes of its own allocation
             // (64-byte pitches in the pyramid buffers, 64-byte rounded slots for uploaded frames): whole dwords, the last one may over-read
@@ -754,12 +755,6 @@ __global__ __launch_bounds__(kSiaBlock) void k_sia_run(SiaArgs A) {
     }
 }
 
-// per feature: float4 s_feat + float2 s_uv, plus two float4 of Jacobian terms while that keeps the workgroup under 96 KB (4000 features)
-bool sia_jac_in_lds(int maxFeatures) { return (size_t) maxFeatures * 56 + 16 <= 96 * 1024; }
-size_t sia_lds_bytes(int maxFeatures) {
-    return (size_t) maxFeatures * (sizeof(float4) + sizeof(float2) + (sia_jac_in_lds(maxFeatures) ? 2 * sizeof(float4) : 0)) + 16;
-}
-
 // dynamic LDS the kernel may use (160 KB minus its static part)
 static int sia_dyn_ceiling(hipError_t *err) {
     // a constant of the compiled kernel: asked once per process (thread-safe static initialisation), not on every call
@@ -767,20 +762,19 @@ static int sia_dyn_ceiling(hipError_t *err) {
     static const Q q = [] {
         hipFuncAttributes fa;
         Q r{hipFuncGetAttributes(&fa, (const void *) k_sia_run<false>), 0};
-        if (r.e == hipSuccess) r.v = (int) std::min<size_t>(kMaxDynLds, 160 * 1024 - ((fa.sharedSizeBytes + 255) & ~(size_t) 255));
+        if (r.e == hipSuccess) r.v = sia_ceiling(fa.sharedSizeBytes);
         return r;
     }();
     *err = q.e;
     return q.v;
 }
 
-// bytes of LDS left for the staged current image behind a feature table of featBytes (0 when nothing useful fits)
-size_t sia_stage_bytes(size_t featBytes, size_t largestLevelBytes) {
+// the launch's LDS record (lds_layout.h) at this kernel's ceiling; without a ceiling (sia_prepare reports that error) nothing is staged
+bool sia_plan_lds(SiaArgs &A, int features, size_t largestLevelBytes, size_t capBytes) {
     hipError_t e;
     const int ceiling = sia_dyn_ceiling(&e);
-    if (e != hipSuccess || (size_t) ceiling < featBytes + 4096) return 0;
-    const size_t avail = ((size_t) ceiling - featBytes) & ~(size_t) 15;
-    return std::min(avail, (largestLevelBytes + 8 + 15) & ~(size_t) 15);
+    A.lds = sia_lds(features, largestLevelBytes, e == hipSuccess ? (size_t) ceiling : 0, capBytes);
+    return sia_fits(A.lds);
 }
 
 hipError_t sia_prepare(size_t ldsBytes) {

@@ -698,7 +698,6 @@ __device__ __forceinline__ int fast9_arc_score(const uint8_t *c, int tp, int pol
 
 // LDS pitch of a cell's score map = the window pitch (wCell + 2 columns used, the window pitch is >= wCell + 7)
 struct FastGroupBases { int v[kMaxLevels]; };   // first 2x2 cell group of every level inside a frame (LevelGeom::groupBase), by value
-constexpr int kCornerCap = 512;  // corners listed per cell before the dense fallback takes over
 
 // ------------------------------------------------------------------------------------------------------------------
 // K2q  The same cell loop with FOUR pixels per lane in pass 1 (byte-sliced FAST-9 test).
@@ -989,14 +988,11 @@ __device__ __forceinline__ void fast_cell(const FrameSet &fs, const LevelGeom *_
         return;
     }
     const int P = kP ? kP : winPitch;
-    const int winBytes = (winRows * P + 16 + 15) & ~15;   // 16 bytes of slack: the last quad of the last row reads past its row
-    // the quad list lives only between pass 1 and the expansion, the score map only after the expansion: they share their bytes (one
-    // more workgroup fits a CU: 8 x 4 waves instead of 6 x 4 at the usual 30-px cells)
-    const int smapBytes = (max(smapRows * P, quadCap * 4) + 15) & ~15;
-    const int perWave = winBytes + smapBytes + kCornerCap * 2;    // all multiples of 16
-    uint8_t *win = fdyn + wv * perWave;
-    uint8_t *smap = win + winBytes;
-    unsigned short *clist = (unsigned short *) (smap + smapBytes);
+    // (the quad list and the score map share their bytes: one more workgroup fits a CU, 8 x 4 waves instead of 6 x 4 at the usual 30-px cells)
+    const FastWaveLds W = fast_wave_lds(P, winRows, smapRows, quadCap);
+    uint8_t *win = fdyn + wv * W.perWave;
+    uint8_t *smap = win + W.winBytes;
+    unsigned short *clist = (unsigned short *) (smap + W.smapBytes);
     {   // stage the window: LDS column 1 + b of row r = image pixel (iniX + b, iniY + r), i.e. tested pixel x of the cell at column x + 4.
         // All global loads of a chunk are issued before the first use; lanes past the end repeat the last dword.
         int pitch;
@@ -1080,7 +1076,6 @@ __global__ __launch_bounds__(kFastBlock) void k_fast_quads(FrameSet fs, const Le
 // Cells wider than 41 px (window > 48 bytes) keep k_fast_quads.
 // ------------------------------------------------------------------------------------------------------------------
 typedef __attribute__((address_space(3))) void lds_void_t;
-constexpr int kTabPitch = 48;
 #ifndef YGZF_FAST_TAB_WAVES
 #define YGZF_FAST_TAB_WAVES 4
 #endif
@@ -1143,10 +1138,8 @@ __global__ __launch_bounds__(64 * kFastTabWaves) void k_fast_tab(FrameSet fs, co
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rec = blk * kFastTabWaves + wv;                              // (groupsPerXcd / totalGroups count workgroups of kFastTabWaves cells here)
     if (rec >= totalGroups * kFastTabWaves) return;
-    const int winBytes = (winRows * kTabPitch + 16 + 15) & ~15;
-    const int smapBytes = (max(smapRows * kTabPitch, quadCap * 4) + 15) & ~15;
-    const int perWave = winBytes + smapBytes + kCornerCap * 2;
-    fast_tab_cell<kIniFirst>(fs, cells, rec, f, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, fdyn + wv * perWave, winBytes, smapBytes, lane, stats, pc);
+    const FastWaveLds W = fast_wave_lds(kTabPitch, winRows, smapRows, quadCap);
+    fast_tab_cell<kIniFirst>(fs, cells, rec, f, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, fdyn + wv * W.perWave, W.winBytes, W.smapBytes, lane, stats, pc);
     pc.flush(0, lane, (unsigned) rec + (unsigned) f * (unsigned) (totalGroups * kFastTabWaves));
 }
 
@@ -1161,7 +1154,7 @@ __global__ __launch_bounds__(64 * kFastTabWaves) void k_fast_tab(FrameSet fs, co
 // XCD's share.  The draw for the NEXT cell is issued before the current one's window is requested, so its round trip hides behind that window's.
 // ------------------------------------------------------------------------------------------------------------------
 template <bool kIniFirst>
-__global__ __launch_bounds__(256) void k_fast_tab_persist(FrameSet fs, const FastCellRec *__restrict__ cells, int iniTh, int minTh,
+__global__ __launch_bounds__(64 * kFastPersistWaves) void k_fast_tab_persist(FrameSet fs, const FastCellRec *__restrict__ cells, int iniTh, int minTh,
                                                           unsigned short *__restrict__ cellCnt, unsigned *__restrict__ slots, int totalCells,
                                                           long long totalSlots, unsigned recsPerFrame, unsigned long long recMagic, unsigned totalItems,
                                                           unsigned itemsPerXcd, int winRows, int smapRows, int quadCap, unsigned *__restrict__ stats,
@@ -1169,10 +1162,8 @@ __global__ __launch_bounds__(256) void k_fast_tab_persist(FrameSet fs, const Fas
     extern __shared__ __attribute__((aligned(16))) uint8_t fdyn[];
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int winBytes = (winRows * kTabPitch + 16 + 15) & ~15;
-    const int smapBytes = (max(smapRows * kTabPitch, quadCap * 4) + 15) & ~15;
-    const int perWave = winBytes + smapBytes + kCornerCap * 2;
-    uint8_t *win = fdyn + wv * perWave;
+    const FastWaveLds W = fast_wave_lds(kTabPitch, winRows, smapRows, quadCap);
+    uint8_t *win = fdyn + wv * W.perWave;
     PhaseClk pc;
     pc.start();
     // 64 counters, 256 bytes apart: XCD x (= blockIdx.x % 8) owns counters 8 x .. 8 x + 7, each over an eighth of the XCD's items.  The draws are
@@ -1204,7 +1195,7 @@ __global__ __launch_bounds__(256) void k_fast_tab_persist(FrameSet fs, const Fas
         if (f * recsPerFrame > item) f--;
         if ((f + 1u) * recsPerFrame <= item) f++;
         const unsigned rec = item - f * recsPerFrame;
-        fast_tab_cell<kIniFirst>(fs, cells, (int) rec, (int) f, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, win, winBytes, smapBytes, lane, stats, pc);
+        fast_tab_cell<kIniFirst>(fs, cells, (int) rec, (int) f, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, win, W.winBytes, W.smapBytes, lane, stats, pc);
         pc.flush(0, lane, item);
         pc.start();
         wave_lds_handoff();                                // the next cell reuses this wave's LDS region
@@ -1350,29 +1341,25 @@ template <int kBlock> __device__ __forceinline__ void oct_empty_level(const OctA
     for (int i = w.tid; i < w.g.kpCap; i += kBlock) a.procRec[(long long) w.f * a.kpStride + w.g.kpBase + i] = make_uint2(0u, kNoKeypoint);
 }
 
-// ---- LDS carve-up (the sizes it must match: octree_lds_bytes / octree_lds_cand / octree_hist_lds_bytes, ygzf_plan.hip) ----
+// ---- LDS carve-up: oct_lds (lds_layout.h) with this level's own cell count; the launch is sized with the largest of its levels ----
 template <bool kGlobalNodes, bool kHist> __device__ __forceinline__ void oct_carve(const OctArgs &a, OctLevel &w, int *dyn) {
     OctShared &S = w.S;
     const int cap = a.cap;
-    int *p = dyn;
-    w.PS = nullptr; w.candB = nullptr; S.cellPref = p;
-    if (kHist) w.PS = dyn + a.regionInts;      // (the node arrays start at dyn as well: the cell prefix table is dead once the keys exist)
-    else p += (w.nCells + 1 + 3) & ~3;         // (16-byte aligned node arrays: cap is a multiple of 4)
-    int *candLds = p;
-    if (kGlobalNodes) p = a.nodeArena + ((long long) blockIdx.y * a.nlevels + w.l) * (19LL * cap);
+    const OctLds Y = oct_lds_front(kHist ? kOctLdsHist : kGlobalNodes ? kOctLdsArena : kOctLdsSort, w.nCells, cap, a.regionInts, a.histBins);
+    S.cellPref = dyn + Y.cellPref;
+    w.PS = kHist ? dyn + Y.PS : nullptr;
+    w.candB = kHist || kGlobalNodes ? nullptr : (unsigned *) dyn;   // (over the front: oct_lds)
+    int *p = kGlobalNodes ? a.nodeArena + ((long long) blockIdx.y * a.nlevels + w.l) * ((long long) kOctNodeArrays * cap) : dyn + Y.nodes;
     for (int b = 0; b < 2; b++) { S.nlo[b] = p; p += cap; S.ncnt[b] = p; p += cap; S.ndep[b] = p; p += cap; }
     S.kArr = p; p += cap; S.eArr = p; p += cap; S.sArr = p; p += cap;
     S.b1 = p; p += cap; S.b2 = p; p += cap; S.b3 = p; p += cap;
     S.Epos = p; p += cap; S.Ecnt = p; p += cap;
     for (int b = 0; b < 2; b++) { S.sk[b] = (unsigned *) p; p += cap; S.sv[b] = (unsigned *) p; p += cap; }
-    S.flag = p; p += cap;
-    if (kGlobalNodes) S.cand = (unsigned *) candLds;   // 4 * ldsCand words: key/val double buffers when the level's candidates fit
-    else if (!kHist) {
-        w.candB = (unsigned *) dyn;
-        S.cand = (unsigned *) dyn + max((int) (p - dyn), 2 * a.ldsCand);   // (p - dyn: a multiple of 4, as is ldsCand)
-    }
+    S.flag = p; p += cap;   // (kOctNodeArrays arrays; in LDS, p - dyn is now where the front ends, Y.ints: a multiple of 4, as is ldsCand)
+    if (kGlobalNodes) S.cand = (unsigned *) dyn + Y.ints;   // 4 * ldsCand words: key/val double buffers when the level's candidates fit
+    else if (!kHist) S.cand = (unsigned *) dyn + oct_lds_sort_cand((int) (p - dyn), a.ldsCand);   // 2 * ldsCand words; the second pair is candB
     // the key tables, when they are used: in the node arrays (idle until the tree passes), kHist: behind the cell prefix table
-    w.xTab = (unsigned *) (kHist ? dyn + w.nCells + 1 : S.nlo[0]);
+    w.xTab = (unsigned *) (kGlobalNodes ? S.nlo[0] : dyn + Y.xTab);
 }
 
 // ---- 1. candidate offsets per cell (cell-major order == the reference's vToDistributeKeys order); returns M ----
@@ -1862,7 +1849,7 @@ template <bool kHist, int kBlock> __device__ __forceinline__ OctOutcome oct_atte
         else { w.key1 = w.S.cand + 2 * a.ldsCand; w.val1 = w.S.cand + 3 * a.ldsCand; }
     }
     const int lenX = max(g.regW, g.nCols * g.wCell) + 9, lenY = max(g.regH, g.nRows * g.hCell) + 9;
-    const bool useTab = (kHist ? lenX + lenY + w.nCells <= a.regionInts - (w.nCells + 1) : lenX + lenY + w.nCells <= 19 * a.cap) && g.depth <= 15;
+    const bool useTab = lenX + lenY + w.nCells <= oct_lds_tab_room(kHist, w.nCells, a.cap, a.regionInts) && g.depth <= 15;
     if (useTab) oct_key_tables<kBlock>(w, lenX, lenY);
     if (w.hist) {
         for (int b = tid; b <= w.nBins; b += kBlock) w.PS[b] = 0;
@@ -2662,11 +2649,6 @@ void launch_pyr_strips(hipStream_t st, const FrameSet &fs, int nlevels, const Py
     hipLaunchKernelGGL(k_pyr_strips, dim3(nStrips, nFrames), dim3(kPyrStripThreads), ldsBytes, st, fs, nlevels, plans, levels, offA, offB, xofs, xalpha, yofs, ybeta);
 }
 
-size_t fast_quads_lds_bytes(int winPitch, int winRows, int smapRows, int quadCap) {
-    const size_t smapBytes = (std::max((size_t) smapRows * winPitch, (size_t) quadCap * 4) + 15) & ~(size_t) 15;   // score map and quad list share their bytes
-    return (size_t) (kFastBlock / 64) * ((((size_t) winRows * winPitch + 16 + 15) & ~(size_t) 15) + smapBytes + kCornerCap * sizeof(unsigned short)) + 64;
-}
-
 void launch_fast_cells(hipStream_t st, const FrameSet &fs, const LevelGeom *dGeom, int nlevels, int iniTh, int minTh,
                        unsigned short *cellCnt, unsigned *slots, int totalCells, long long totalSlots, int totalGroups, int smapRows,
                        int nFrames, int winPitch, int winRows, int quadCap, const int *groupBaseHost, bool iniFirst, unsigned *stats) {
@@ -2675,7 +2657,7 @@ void launch_fast_cells(hipStream_t st, const FrameSet &fs, const LevelGeom *dGeo
     for (int k = 0; k < kMaxLevels; k++) gb.v[k] = k < nlevels ? groupBaseHost[k] : 0x7fffffff;
     const int groupsPerXcd = ((totalGroups + kFastRep - 1) / kFastRep + 7) / 8;    // workgroups (of kFastRep groups) per XCD
     const dim3 grid(8 * groupsPerXcd, nFrames), block(kFastBlock);
-    const size_t lds = fast_quads_lds_bytes(winPitch, winRows, smapRows, quadCap);
+    const size_t lds = fast_lds_bytes(fast_wave_lds(winPitch, winRows, smapRows, quadCap), kFastBlock / 64);
 #define YGZF_FAST_LAUNCH(KP)                                                                                                                       \
     do {                                                                                                                                           \
         if (iniFirst)                                                                                                                              \
@@ -2695,9 +2677,6 @@ void launch_fast_cells(hipStream_t st, const FrameSet &fs, const LevelGeom *dGeo
 }
 
 // ---- table-driven form (k_fast_tab) ----
-size_t fast_tab_lds_bytes(int winRows, int smapRows, int quadCap) {
-    return (fast_quads_lds_bytes(kTabPitch, winRows, smapRows, quadCap) - 64) / (kFastBlock / 64) * kFastTabWaves + 64;
-}
 void launch_fast_tab(hipStream_t st, const FrameSet &fs, const FastCellRec *dCells, int iniTh, int minTh, unsigned short *cellCnt, unsigned *slots,
                      int totalCells, long long totalSlots, int totalGroups, int smapRows, int nFrames, int winRows, int quadCap, bool iniFirst,
                      unsigned *stats) {
@@ -2705,7 +2684,7 @@ void launch_fast_tab(hipStream_t st, const FrameSet &fs, const FastCellRec *dCel
     const int totalWgs = totalGroups * (4 / kFastTabWaves);                 // workgroups of kFastTabWaves cells
     const int groupsPerXcd = (totalWgs + 7) / 8;
     const dim3 grid(8 * groupsPerXcd, nFrames), block(64 * kFastTabWaves);
-    const size_t lds = fast_tab_lds_bytes(winRows, smapRows, quadCap);
+    const size_t lds = fast_lds_bytes(fast_wave_lds(kTabPitch, winRows, smapRows, quadCap), kFastTabWaves);
 #define YGZF_LAUNCH_TAB(INI) hipLaunchKernelGGL((k_fast_tab<INI>), grid, block, lds, st, fs, dCells, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, totalWgs, \
                                                    groupsPerXcd, winRows, smapRows, quadCap, stats)
     if (iniFirst) YGZF_LAUNCH_TAB(true); else YGZF_LAUNCH_TAB(false);
@@ -2722,8 +2701,8 @@ void launch_fast_tab_persist(hipStream_t st, const FrameSet &fs, const FastCellR
     const unsigned totalItems = recsPerFrame * (unsigned) nFrames;
     // whole frames per XCD where the frames divide (a frame's windows then meet in one L2), equal shares of the items otherwise
     const unsigned perXcd = nFrames >= 8 ? recsPerFrame * (unsigned) ((nFrames + 7) / 8) : (totalItems + 7u) / 8u;
-    const size_t lds = fast_tab_lds_bytes(winRows, smapRows, quadCap);
-    const dim3 grid((unsigned) nWorkgroups), block(256);
+    const size_t lds = fast_lds_bytes(fast_wave_lds(kTabPitch, winRows, smapRows, quadCap), kFastPersistWaves);
+    const dim3 grid((unsigned) nWorkgroups), block(64 * kFastPersistWaves);
     if (iniFirst)
         hipLaunchKernelGGL((k_fast_tab_persist<true>), grid, block, lds, st, fs, dCells, iniTh, minTh, cellCnt, slots, totalCells, totalSlots, recsPerFrame, magic,
                            totalItems, perXcd, winRows, smapRows, quadCap, stats, counters);
@@ -2732,7 +2711,6 @@ void launch_fast_tab_persist(hipStream_t st, const FrameSet &fs, const FastCellR
                            totalItems, perXcd, winRows, smapRows, quadCap, stats, counters);
 }
 
-// (octree_lds_bytes / octree_lds_cand / octree_hist_lds_bytes, the sizes of k_octree's dynamic LDS, are host arithmetic: ygzf_plan.hip)
 hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist) {
     constexpr int kOctMaxDyn = 160 * 1024 - 10 * 1024;   // the kernel's static LDS (radix histogram, scan scratch) is ~8.5 KB at 1024 threads
     if (hist) return hipFuncSetAttribute((const void *) k_octree<false, true, kOctBlock>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);

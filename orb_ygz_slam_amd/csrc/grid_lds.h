@@ -10,7 +10,6 @@
 
 namespace ygzf {
 
-constexpr int GRID_COLS = 64, GRID_ROWS = 48, GRID_CELLS = GRID_COLS * GRID_ROWS;
 constexpr int kMatchBlock = 1024;
 
 // Frame::AssignFeaturesToGrid in LDS (one workgroup of kMatchBlock threads): cellStart[GRID_CELLS + 1] holds the exclusive prefix of the cell

@@ -3,6 +3,7 @@
 #define YGZF_KERNELS_H
 #include "ygzf_internal.h"
 #include "ygzf_remap_plan.h"
+#include "lds_layout.h"
 
 namespace ygzf {
 
@@ -65,13 +66,11 @@ void launch_link_copy(hipStream_t st, void *dst, const void *src, size_t bytes);
 void launch_carry_slot(hipStream_t st, ygzf_kp *outKp, uint8_t *outDesc, int *outCnt, long long srcSlot, int kpStride);
 void launch_pack_results(hipStream_t st, const int *cnt, const ygzf_kp *kp, const uint8_t *desc, int nFrames, int kpStride, void *dst, size_t offKp, size_t offDesc);
 void launch_pack_levels(hipStream_t st, const FrameSet &fs, const LevelGeom *dGeom, int firstLevel, int nlevels, const unsigned *offsets, uint8_t *dst);
-size_t fast_quads_lds_bytes(int winPitch, int winRows, int smapRows, int quadCap);
 void launch_fast_cells(hipStream_t st, const FrameSet &fs, const LevelGeom *dGeom, int nlevels, int iniTh, int minTh,
                        unsigned short *cellCnt, unsigned *slots, int totalCells, long long totalSlots, int totalGroups, int smapRows,
                        int nFrames, int winPitch, int winRows, int quadCap, const int *groupBaseHost, bool iniFirst, unsigned *stats);
 // table-driven form of the same cell loop (k_fast_tab): per-cell records built on the host, window staged by LDS-DMA; cells up to 41 px wide
 constexpr int kFastTabMaxCell = 41;
-size_t fast_tab_lds_bytes(int winRows, int smapRows, int quadCap);
 void launch_fast_tab(hipStream_t st, const FrameSet &fs, const FastCellRec *dCells, int iniTh, int minTh, unsigned short *cellCnt, unsigned *slots,
                      int totalCells, long long totalSlots, int totalGroups, int smapRows, int nFrames, int winRows, int quadCap, bool iniFirst,
                      unsigned *stats);
@@ -81,9 +80,7 @@ void launch_fast_tab_persist(hipStream_t st, const FrameSet &fs, const FastCellR
                              int totalCells, long long totalSlots, int totalGroups, int smapRows, int nFrames, int winRows, int quadCap, bool iniFirst,
                              unsigned *stats, unsigned *counters, int nWorkgroups);
 constexpr int kFastStatWords = 8 * 64;   // `stats`: 64 x {cells sampled, cells whose keypoints are FAST(minTh)'s, score rounds beyond the first, plan: 1 one pass / 2 iniTh first, corner-bearing quads, quads, -, pass-1 runs}
-size_t octree_lds_bytes(int maxCellsPerLevel, int cap, int ldsCand, bool globalNodes);
 int octree_lds_cand(int maxCellsPerLevel, int cap, size_t budget);   // the sort plan's candidate budget within `budget` bytes of LDS node arrays + buffers (0: < 256)
-size_t octree_hist_lds_bytes(int regionInts, int histBins);
 hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist);
 // One launch of k_octree: levels [levelBase, levelBase + gridDim.x) of gridDim.y frames, one workgroup per (level, frame) -- the histogram plan
 // with gridDim.z - 1 helper workgroups beside it.  histBins > 0 selects the histogram plan, nodeArena the sort plan with node arrays in global memory.
@@ -193,9 +190,7 @@ struct MatchArgs {
 // when non-zero.
 constexpr int kMatchStatFallbacks = 0, kMatchStatRoundCap = 1, kMatchStatExtRoom = 2, kMatchStatExtended = 3, kMatchStatRescans = 4, kMatchStatWords = 5;
 constexpr int kMatchCauseRounds = 1, kMatchCauseExtRoom = 2;   // why a pair left the fixpoint (k_match_last: s_tmp[15])
-constexpr int kSpillSpec = 1, kSpillMisc = 2;
 constexpr int kMatchSplitRec = 56;   // uint4 + uint4 (lists of eight) + ushort4 + ushort4 + float angle + hasObs word
-size_t match_lds_bytes(int capCur, int capLast, bool descInLds, int spill, size_t *spillBytes, bool specDeep);
 hipError_t match_prepare(size_t ldsBytes);
 void launch_backproject_unit(hipStream_t st, const ygzf_kp *keys, const int *cnt, long long kpStride, int maxKp, int nFrames, float fx,
                              float fy, float cx, float cy, float *world);
@@ -388,7 +383,6 @@ struct FiaArgs {                    // Frame::GetFeaturesInArea queries against 
     int cap;
     int *outIdx, *outN;             // nq x cap indices (reference order), nq counts (uncapped)
 };
-size_t fia_lds_bytes(int n);
 hipError_t launch_features_in_area(hipStream_t st, const FiaArgs &A);
 
 // The projection searches of one snapshot (match_kernels.hip: k_proj_search<mode>): ORBmatcher::Fuse(KeyFrame*, const vector<MapPoint*>&, th),
@@ -405,7 +399,6 @@ struct FuseKf {                     // one keyframe; keys / desc / uRight are by
     float scale[kMaxLevels];        // mvScaleFactors
     float invSigma2[kMaxLevels];    // mvInvLevelSigma2 (read by PM_FUSE only)
 };
-size_t fuse_lds_bytes(int maxKeys);
 enum ProjMode { PM_FUSE = 0, PM_FUSE_SCW = 1, PM_PROJ_SCW = 2, PM_SIM3 = 3 };
 struct ProjRow {
     FuseKf kf;                      // the target keyframe; Rcw / tcw = the (first) transform, Ow = its camera centre (unused by PM_SIM3)
@@ -430,7 +423,7 @@ hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys);
 
 // The resident keyframes (kfstore_kernels.hip; entry points in ygzf_api_kfstore.hip): k_kf_grid_build writes the CSR build_grid_lds produces --
 // cellStart[GRID_CELLS + 1] (64 x 48 cells, column-major px * 48 + py) and list[n], key indices ascending inside a cell, the entries behind
-// cellStart[GRID_CELLS] (keys outside the cells are in no list) set to -1 -- once per keyframe.  n is bounded by fuse_lds_bytes(n) <= kMaxDynLds.
+// cellStart[GRID_CELLS] (keys outside the cells are in no list) set to -1 -- once per keyframe.  n is at most kGridMaxKeys.
 constexpr int kKfGridCells = 64 * 48;
 struct KfGridArgs {
     const ygzf_kp *keys;
@@ -441,9 +434,7 @@ struct KfGridArgs {
 hipError_t launch_kf_grid_build(hipStream_t st, const KfGridArgs &A);
 
 struct SiaArgs {
-    int ldsFeat;                    // feature slots of the dynamic LDS carve-up (float4 s_feat[ldsFeat] | float2 s_uv[ldsFeat] | float4 s_jac[2*ldsFeat])
-    int stageOff, stageBytes;       // byte offset (from the start of dynamic LDS) and size of the staged current-image region
-    int jacLds;                     // the point-only Jacobian terms are staged in LDS (sia_jac_in_lds(ldsFeat))
+    SiaLds lds;                     // the dynamic LDS of the launch (lds_layout.h: sia_lds)
     const ygzf_kp *keys;            // ref keypoints, pair p at keys + p*kpStride
     const float *world;             // MapPoint world positions, 3 per keypoint
     const uint8_t *mpValid, *outlier;  // nullable
@@ -471,9 +462,8 @@ struct SiaArgs {
     float *out;                     // 48 floats per pair: TCR[7], ret, iters, chi2, pad[2], H[36]
     long long *dbg;                 // nullable: phase clocks of pair 0 (debug)
 };
-size_t sia_lds_bytes(int maxFeatures);
-bool sia_jac_in_lds(int maxFeatures);
-size_t sia_stage_bytes(size_t featBytes, size_t largestLevelBytes);
+// fills A.lds for pairs of up to `features` feature slots (capBytes: 0, or the LDS a workgroup should keep to); false: the feature table does not fit
+bool sia_plan_lds(SiaArgs &A, int features, size_t largestLevelBytes, size_t capBytes);
 hipError_t sia_prepare(size_t ldsBytes);
 void launch_sia_precompute(hipStream_t st, const SiaArgs &A, int nPairs, int maxN);
 void launch_sia(hipStream_t st, const SiaArgs &A, int nPairs, size_t ldsBytes);

@@ -15,10 +15,9 @@ static_assert(kKfGridCells == GRID_CELLS, "the stored grid is the matcher's grid
 __global__ __launch_bounds__(kMatchBlock) void k_kf_grid_build(KfGridArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ int s_tmp[kMatchBlock / 64];
-    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
-    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
-    int *list = cellFill + GRID_CELLS;               // n
-    build_grid_lds(A.keys, A.n, A.minX, A.minY, A.gridInvW, A.gridInvH, cellStart, cellFill, list, s_tmp);
+    const GridPtrs G = grid_carve(dyn);
+    int *cellStart = G.cellStart, *list = G.list;
+    build_grid_lds(A.keys, A.n, A.minX, A.minY, A.gridInvW, A.gridInvH, G.cellStart, G.cellFill, G.list, s_tmp);
     const int total = cellStart[GRID_CELLS];
     for (int i = threadIdx.x; i <= GRID_CELLS; i += kMatchBlock) A.cellStart[i] = cellStart[i];
     for (int i = threadIdx.x; i < A.n; i += kMatchBlock) A.list[i] = i < total ? list[i] : -1;
@@ -27,7 +26,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_kf_grid_build(KfGridArgs A) {
 hipError_t launch_kf_grid_build(hipStream_t st, const KfGridArgs &A) {
     hipError_t e = hipFuncSetAttribute((const void *) k_kf_grid_build, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(k_kf_grid_build, dim3(1), dim3(kMatchBlock), fia_lds_bytes(A.n), st, A);
+    hipLaunchKernelGGL(k_kf_grid_build, dim3(1), dim3(kMatchBlock), grid_lds_bytes(A.n), st, A);
     return hipSuccess;
 }
 

@@ -17,7 +17,7 @@
 // of mode 1 -- are match_rules.h's, for every kernel of this file.
 #include "kernels.h"
 #include "wave_ops.h"
-#include "grid_lds.h"   // GRID_COLS / GRID_ROWS / GRID_CELLS, kMatchBlock, build_grid_lds
+#include "grid_lds.h"   // kMatchBlock, build_grid_lds (GRID_COLS / GRID_ROWS / GRID_CELLS and every LDS layout of this file: lds_layout.h)
 #include "match_rules.h"
 
 namespace ygzf {
@@ -47,7 +47,6 @@ struct QueryParam {  // per Last keypoint, precomputed by all waves (32 bytes)
 };
 
 constexpr unsigned kNoKey = (256u << 16);
-constexpr int kExtSlots = 64;
 
 // The Cur descriptors live either in LDS or in global memory (MatchArgs::descInLds).  Read through generic pointers the compiler folds the two
 // branches into ONE flat load with a selected address -- and a flat load that lands in LDS costs ~1 us per candidate at this kernel's occupancy
@@ -352,43 +351,22 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
 #define STAMP(k) do { if (dbg && tid == 0) dbg[k] = wall_clock64(); } while (0)
     const long long tStart = dbg ? wall_clock64() : 0;   // (with several workgroups per pair only the one that survives the hand-over reports)
     // ---- LDS carve-up ----
-    MatchLds L;
+    MatchLds L = {};
     // Arrays that do not fit the LDS budget (large keypoint counts: 4000 / 8000 features) live in a per-pair global
     // scratch arena instead; `spill` is the host's plan, bit per array group.
     unsigned char *p = dyn;
     unsigned char *gp = (unsigned char *) A.spillScratch + (long long) pair * A.spillStride;
-#define CARVE(ptr, type, count, bit)                                                        \
+    // (the arrays, their order and their spill bits: YGZF_MATCH_LDS_ARRAYS, lds_layout.h -- match_lds_bytes sums the same list)
+#define CARVE(member, type, count, bit)                                                     \
     do {                                                                                    \
-        if (A.spill & (bit)) { ptr = (type *) gp; gp += (((size_t) sizeof(type) * (count)) + 15) & ~(size_t) 15; } \
-        else { ptr = (type *) p; p += (((size_t) sizeof(type) * (count)) + 15) & ~(size_t) 15; }                   \
-    } while (0)
-    CARVE(L.cellStart, int, GRID_CELLS + 1, 0);
-    CARVE(L.cellFill, int, GRID_CELLS, 0);
-    CARVE(L.list, int, A.capCur, 0);
-    CARVE(L.cx, float, A.capCur, 0);
-    CARVE(L.cy, float, A.capCur, 0);
-    CARVE(L.owner, unsigned char, A.capCur, 0);
-    CARVE(L.octave, unsigned char, A.capCur, 0);
-    CARVE(L.qobs, unsigned char, A.capLast, 0);
-    CARVE(L.specKey, uint4, A.capLast, kSpillSpec);
-    CARVE(L.specI2, ushort4, A.capLast, kSpillSpec);
-    L.specKeyB = nullptr;
-    L.specI2B = nullptr;
-    if (A.specDeep) {
-        CARVE(L.specKeyB, uint4, A.capLast, kSpillSpec);
-        CARVE(L.specI2B, ushort4, A.capLast, kSpillSpec);
-    }
-    CARVE(L.events, int, A.capLast, kSpillMisc);
-    CARVE(L.qang, float, A.capLast, kSpillMisc);
-    CARVE(L.cang, float, A.capCur, kSpillMisc);
-    CARVE(L.match, int, A.capCur, kSpillMisc);
-    CARVE(L.claim, int, A.capCur, kSpillMisc);
-    CARVE(L.extOf, unsigned char, 2 * (size_t) A.capLast, kSpillMisc);
-    CARVE(L.extKey, unsigned, 8 * kExtSlots, kSpillMisc);
-    CARVE(L.extI2, unsigned short, 8 * kExtSlots, kSpillMisc);
-    CARVE(L.extWork, int, kExtSlots, kSpillMisc);
-    L.desc = nullptr;
-    if (A.descInLds) CARVE(L.desc, unsigned long long, 4 * (size_t) A.capCur, 0);
+        if (A.spill & (bit)) { L.member = (type *) gp; gp += al16((size_t) sizeof(type) * (count)); } \
+        else { L.member = (type *) p; p += al16((size_t) sizeof(type) * (count)); }                   \
+    } while (0);
+#define CARVE_IF(cond) if (A.cond) {
+#define CARVE_END }
+    YGZF_MATCH_LDS_ARRAYS(CARVE, CARVE_IF, CARVE_END, A.capCur, A.capLast)
+#undef CARVE_END
+#undef CARVE_IF
 #undef CARVE
     L.qp = (QueryParam *) A.qpScratch + (long long) pair * A.capLast;   // global: only the rare full rescans read it back
 
@@ -1717,8 +1695,6 @@ void launch_bow_descend(hipStream_t st, int n, const uint8_t *desc, const int *c
     if (n > 0) hipLaunchKernelGGL(k_bow_descend, dim3((n + 3) / 4), dim3(256), 0, st, n, desc, childOff, childIdx, nodeDesc, nidLevel, leafNode, levelNode);
 }
 
-static inline size_t al16(size_t b) { return (b + 15) & ~(size_t) 15; }
-
 // ------------------------------------------------------------------------------------------------------------------
 // Frame::AssignFeaturesToGrid + Frame::GetFeaturesInArea as a direct query (src/Frame.cc:314-330, 483-493, 424-481): the index list the
 // reference returns for (x, y, r, minLevel, maxLevel), in its order -- grid columns ix ascending, cells iy ascending inside a column,
@@ -1730,11 +1706,10 @@ static inline size_t al16(size_t b) { return (b + 15) & ~(size_t) 15; }
 __global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ int s_tmp[kMatchBlock / 64];
-    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
-    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
-    int *list = cellFill + GRID_CELLS;               // n
+    const GridPtrs G = grid_carve(dyn);
+    int *cellStart = G.cellStart, *list = G.list;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    build_grid_lds(A.keys, A.n, A.minX, A.minY, A.gridInvW, A.gridInvH, cellStart, cellFill, list, s_tmp);
+    build_grid_lds(A.keys, A.n, A.minX, A.minY, A.gridInvW, A.gridInvH, G.cellStart, G.cellFill, G.list, s_tmp);
     const unsigned long long lt = (1ull << lane) - 1ull;
     const int wavesTotal = gridDim.x * (kMatchBlock / 64);
     for (int q = blockIdx.x * (kMatchBlock / 64) + wave; q < A.nq; q += wavesTotal) {
@@ -1777,10 +1752,8 @@ __global__ __launch_bounds__(kMatchBlock) void k_features_in_area(FiaArgs A) {
     }
 }
 
-size_t fia_lds_bytes(int n) { return sizeof(int) * ((size_t) GRID_CELLS + 4 + GRID_CELLS + (size_t) n) + 16; }
-
 hipError_t launch_features_in_area(hipStream_t st, const FiaArgs &A) {
-    const size_t lds = fia_lds_bytes(A.n);
+    const size_t lds = grid_lds_bytes(A.n);
     hipError_t e = hipFuncSetAttribute((const void *) k_features_in_area, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     if (e != hipSuccess) return e;
     const int perWg = kMatchBlock / 64;
@@ -1941,8 +1914,6 @@ __device__ __forceinline__ void proj_search_point(const FuseKf &K, const float *
         for (int k = found; k < nBest; k++) { outIdx[k] = -1; outDist[k] = 256; }
 }
 
-size_t fuse_lds_bytes(int maxKeys) { return fia_lds_bytes(maxKeys); }
-
 // Every projection search: workgroup = one row (blockIdx.y: a target keyframe with its own point list) x a slice of that row's points.
 // Rows shorter than the longest leave their surplus workgroups idle (SearchBySim3's two directions have N1 and N2 points).  Fuse's K keyframes
 // x P points are K rows over one copy of the point arrays, row k's skip mask and results at k * P.
@@ -1957,9 +1928,8 @@ template <int MODE, bool RES>
 __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ int s_tmp[kMatchBlock / 64];
-    int *cellStart = (int *) dyn;                    // GRID_CELLS + 1 (+ 3 pad)
-    int *cellFill = cellStart + GRID_CELLS + 4;      // GRID_CELLS
-    int *list = cellFill + GRID_CELLS;               // n
+    const GridPtrs G = grid_carve(dyn);
+    int *cellStart = G.cellStart, *list = G.list;
     const ProjRow &R = A.rows[blockIdx.y];
     const int p0 = blockIdx.x * A.slice, p1 = min(R.nPoints, p0 + A.slice);
     if (p0 >= p1) return;                            // the whole workgroup, before any barrier
@@ -1981,7 +1951,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_proj_search(ProjArgs A) {
         gStart = (const int *) (A.kfBase + R.cellStart);
         gList = (const int *) (A.kfBase + R.list);
     } else {
-        build_grid_lds(keys, K.n, K.minX, K.minY, K.gridInvW, K.gridInvH, cellStart, cellFill, list, s_tmp);
+        build_grid_lds(keys, K.n, K.minX, K.minY, K.gridInvW, K.gridInvH, G.cellStart, G.cellFill, G.list, s_tmp);
     }
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int i = p0 + wave; i < p1; i += kMatchBlock / 64) {
@@ -2001,7 +1971,7 @@ template <int MODE>
 static hipError_t launch_proj_mode(hipStream_t st, const ProjArgs &A, int maxKeys) {
     hipError_t e = hipFuncSetAttribute((const void *) k_proj_search<MODE, false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL((k_proj_search<MODE, false>), dim3((A.maxPoints + A.slice - 1) / A.slice, A.nRows), dim3(kMatchBlock), fuse_lds_bytes(maxKeys), st, A);
+    hipLaunchKernelGGL((k_proj_search<MODE, false>), dim3((A.maxPoints + A.slice - 1) / A.slice, A.nRows), dim3(kMatchBlock), grid_lds_bytes(maxKeys), st, A);
     return hipSuccess;
 }
 template <int MODE>
@@ -2026,22 +1996,6 @@ hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys) {
     case PM_SIM3: return launch_proj_mode<PM_SIM3>(st, A, maxKeys);
     }
     return hipErrorInvalidValue;
-}
-
-// LDS bytes / per-pair global spill bytes of the carve-up in k_match_last for a given plan
-size_t match_lds_bytes(int capCur, int capLast, bool descInLds, int spill, size_t *spillBytes, bool specDeep) {
-    size_t lds = al16(sizeof(int) * (GRID_CELLS + 1)) + al16(sizeof(int) * GRID_CELLS) + al16(sizeof(int) * (size_t) capCur) +
-                 2 * al16(sizeof(float) * (size_t) capCur) + 2 * al16((size_t) capCur) + al16((size_t) capLast);
-    size_t gl = 0;
-    const size_t spec = (specDeep ? 2 : 1) * (al16(sizeof(uint4) * (size_t) capLast) + al16(sizeof(ushort4) * (size_t) capLast));
-    const size_t misc = al16(sizeof(int) * (size_t) capLast) + al16(sizeof(float) * (size_t) capLast) + al16(sizeof(float) * (size_t) capCur) +
-                        2 * al16(sizeof(int) * (size_t) capCur) + al16(2 * (size_t) capLast) + al16(sizeof(unsigned) * 8 * kExtSlots) +
-                        al16(sizeof(unsigned short) * 8 * kExtSlots) + al16(sizeof(int) * kExtSlots);
-    if (spill & kSpillSpec) gl += spec; else lds += spec;
-    if (spill & kSpillMisc) gl += misc; else lds += misc;
-    if (descInLds) lds += al16((size_t) 32 * capCur);
-    if (spillBytes) *spillBytes = gl;
-    return lds + 64;
 }
 
 hipError_t match_prepare(size_t ldsBytes) {

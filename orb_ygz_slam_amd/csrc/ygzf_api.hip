@@ -348,7 +348,7 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
     if (G.totalCells > 0) {
         bool iniFirst = false, collect = false;
         fast_threshold_plan(c, &iniFirst, &collect);
-        const FastChoice fast = choose_fast(G, c->fastKernel, c->pins, c->cuCount, nFrames, fast_tab_lds_bytes(G.fastWinRows, G.fastSmapRows, G.fastQuadCap));
+        const FastChoice fast = choose_fast(G, c->fastKernel, c->pins, c->cuCount, nFrames, fast_lds_bytes(fast_wave_lds(kTabPitch, G.fastWinRows, G.fastSmapRows, G.fastQuadCap), kFastPersistWaves));
         if ((rc = launch_fast(c, fs, nFrames, fast, iniFirst, collect))) return rc;
         long long *odbg = nullptr;
         if (c->octDebug) {

@@ -134,15 +134,8 @@ static int sia_run_impl(ygzf_ctx *c, const ygzf_sia_frame *ref, const ygzf_sia_f
             HIPCHECK(c, hipMemsetAsync(c->tmp.b.p, 0, 256, c->stream));
             A.dbg = (long long *) c->tmp.b.p;
         }
-        size_t sl = sia_lds_bytes((int) N);
-        A.ldsFeat = (int) N;
-        A.jacLds = sia_jac_in_lds((int) N) ? 1 : 0;
-        if (sl > 150 * 1024) return fail(c, YGZF_ERR_UNSUPPORTED, "SparseImgAlign supports at most %d features", (int) (150 * 1024 / 24));
-        {
-            A.stageOff = (int) ((sl + 15) & ~(size_t) 15);
-            A.stageBytes = (int) sia_stage_bytes((size_t) A.stageOff, largestCur);
-            sl = (size_t) A.stageOff + (size_t) A.stageBytes;
-        }
+        if (!sia_plan_lds(A, (int) N, largestCur, 0)) return fail(c, YGZF_ERR_UNSUPPORTED, "SparseImgAlign supports at most %d features", kSiaMaxFeatures);
+        const size_t sl = sia_lds_bytes(A.lds);
         HIPCHECK(c, sia_prepare(sl));
         ProfScope ps(c, KK_SIA);
         if (A.perLevel) launch_sia_precompute(c->stream, A, 1, (int) N);
@@ -419,25 +412,14 @@ int ygzf_align_batch_prev(ygzf_ctx *c, const ygzf_camera *cam, int max_level, in
         A2.momCache += (size_t) first * G.kpStride * 4;
         if (A2.perLevel) A2.levelFlags += (size_t) first * G.kpStride;
         A2.out += (size_t) first * 48;
-        size_t sl = sia_lds_bytes(G.kpStride);
-        A2.ldsFeat = G.kpStride;
-        A2.jacLds = sia_jac_in_lds(G.kpStride) ? 1 : 0;
-        if (sl > 150 * 1024) return fail(c, YGZF_ERR_UNSUPPORTED, "SparseImgAlign supports at most %d features", (int) (150 * 1024 / 24));
-        {
-            size_t largest = 0;
-            for (int l = min_level; l <= max_level; l++) largest = std::max(largest, (size_t) G.lv[l].pitch * G.lv[l].h);
-            A2.stageOff = (int) ((sl + 15) & ~(size_t) 15);
-            A2.stageBytes = (int) sia_stage_bytes((size_t) A2.stageOff, largest);
-            // Many pairs in flight: the workgroup keeps to 74 KB of LDS so that TWO share a CU -- one pair's solve (a single wave) and barriers
-            // then overlap the other's accumulate; the coarse levels that no longer fit the staging area are gathered from L2 instead
-            // (measured on 256-pair launches from three streams: 141.1 -> 147.2 k frames/s; a lone pair keeps the full staging area).
-            constexpr long capKb = 74;
-            if (B - first >= 128) {
-                const long cap = capKb * 1024 - A2.stageOff;
-                A2.stageBytes = cap > 4096 ? (int) std::min<long>(A2.stageBytes, cap & ~15L) : 0;
-            }
-            sl = (size_t) A2.stageOff + (size_t) A2.stageBytes;
-        }
+        size_t largest = 0;
+        for (int l = min_level; l <= max_level; l++) largest = std::max(largest, (size_t) G.lv[l].pitch * G.lv[l].h);
+        // Many pairs in flight: the workgroup keeps to 74 KB of LDS so that TWO share a CU -- one pair's solve (a single wave) and barriers
+        // then overlap the other's accumulate; the coarse levels that no longer fit the staging area are gathered from L2 instead
+        // (measured on 256-pair launches from three streams: 141.1 -> 147.2 k frames/s; a lone pair keeps the full staging area).
+        const size_t capBytes = B - first >= 128 ? (size_t) 74 * 1024 : 0;
+        if (!sia_plan_lds(A2, G.kpStride, largest, capBytes)) return fail(c, YGZF_ERR_UNSUPPORTED, "SparseImgAlign supports at most %d features", kSiaMaxFeatures);
+        const size_t sl = sia_lds_bytes(A2.lds);
         HIPCHECK(c, sia_prepare(sl));
         ProfScope ps(c, KK_SIA);
         if (A2.perLevel) launch_sia_precompute(c->stream, A2, B - first, G.kpStride);

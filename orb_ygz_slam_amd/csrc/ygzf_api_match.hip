@@ -21,16 +21,15 @@ static void fill_view_scales(MatchArgs &A, const ygzf_frame_view *F) {
 }
 
 static int plan_match_lds(ygzf_ctx *c, MatchArgs &A, int nPairs, size_t *ldsBytes) {
-    const size_t budget = 156 * 1024;
     if (A.capCur > 65535) return fail(c, YGZF_ERR_UNSUPPORTED, "matcher supports at most 65535 keypoints per frame");
     A.qpInLds = 0;
-    // plans in order of preference: everything in LDS; descriptors in global; + speculative lists in global; + misc arrays
-    const struct { int desc, spill; } plans[] = {{1, 0}, {0, 0}, {0, kSpillSpec}, {0, kSpillSpec | kSpillMisc}};
     size_t b = 0, sp = 0;
     bool ok = false;
-    for (const auto &pl : plans) {
-        b = match_lds_bytes(A.capCur, A.capLast, pl.desc != 0, pl.spill, &sp, A.specDeep != 0);
-        if (b <= budget) { A.descInLds = pl.desc; A.spill = pl.spill; ok = true; break; }
+    for (const MatchLdsPlan &pl : kMatchLdsPlans) {   // in order of preference (lds_layout.h)
+        const MatchLdsBytes need = match_lds_bytes(A.capCur, A.capLast, pl.desc != 0, pl.spill, A.specDeep != 0);
+        b = need.lds;
+        sp = need.spill;
+        if (b <= kMatchLdsBudget) { A.descInLds = pl.desc; A.spill = pl.spill; ok = true; break; }
     }
     if (!ok) return fail(c, YGZF_ERR_UNSUPPORTED, "matcher needs %zu bytes of LDS for %d/%d keypoints", b, A.capCur, A.capLast);
     int rc = ensure(c, c->dQp, (size_t) nPairs * A.capLast * 32);
@@ -726,8 +725,7 @@ int kf_args_check(ygzf_ctx *c, const ygzf_frame_view &view, const ygzf_camera &c
     for (int i = 0; i < n; i++)
         if (view.keys[i].octave < 0 || view.keys[i].octave >= L)
             return fail(c, YGZF_ERR_INVALID, "keyframe %d: keypoint octave outside the scale tables", k);
-    if (fuse_lds_bytes(n) > (size_t) kMaxDynLds)
-        return fail(c, YGZF_ERR_UNSUPPORTED, "keyframe %d: more than %d keypoints in one grid", k, (int) ((kMaxDynLds - 25000) / 4));
+    if (n > kGridMaxKeys) return fail(c, YGZF_ERR_UNSUPPORTED, "keyframe %d: more than %d keypoints in one grid", k, kGridMaxKeys);
     return YGZF_OK;
 }
 // ... and its device record: what does not depend on the pose or on where the arrays lie (a resident keyframe keeps this part) ...
@@ -1063,7 +1061,7 @@ int ygzf_features_in_area(ygzf_ctx *c, const ygzf_camera *cam, int n_keys, const
     if (n_keys < 0 || n_queries < 0 || cap < 0) return fail(c, YGZF_ERR_INVALID, "negative count");
     if (!(cam->max_x > cam->min_x) || !(cam->max_y > cam->min_y)) return fail(c, YGZF_ERR_INVALID, "empty image bounds");
     if (n_queries == 0) return YGZF_OK;
-    if (fia_lds_bytes(n_keys) > (size_t) kMaxDynLds) return fail(c, YGZF_ERR_UNSUPPORTED, "more than %d keypoints in one grid", (int) ((kMaxDynLds - 25000) / 4));
+    if (n_keys > kGridMaxKeys) return fail(c, YGZF_ERR_UNSUPPORTED, "more than %d keypoints in one grid", kGridMaxKeys);
     HIPCHECK(c, hipSetDevice(c->device));
     int rc;
     const size_t qBytes = (size_t) n_queries * 12, lBytes = levels ? (size_t) n_queries * 8 : 0;

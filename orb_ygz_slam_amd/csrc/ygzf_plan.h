@@ -91,7 +91,7 @@ YGZF_HIDDEN std::vector<OctLaunch> plan_oct_sort(const Geometry &G, int L, bool 
 YGZF_HIDDEN int plan_octree(const Geometry &G, int L, const PlanPins &pins, OctPlan &plan, std::string *err);
 
 // Which form of the FAST cell loop a launch of nFrames frames takes and, for Persist, how many workgroups the device holds at once.
-// fastKernelSetting: ygzf_set_fast_kernel's; tabLds: fast_tab_lds_bytes of the geometry.
+// fastKernelSetting: ygzf_set_fast_kernel's; tabLds: the persistent form's LDS for the geometry (fast_lds_bytes, kFastPersistWaves).
 struct FastChoice {
     enum Kind { Quads, Tab, Persist } kind;
     int resident;

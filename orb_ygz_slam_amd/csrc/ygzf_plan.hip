@@ -339,23 +339,14 @@ int build_geometry(const Tables &T, const PlanPins &pins, int w, int h, Geometry
     return YGZF_OK;
 }
 
-// ---- k_octree's dynamic LDS: the sizes oct_carve (extract_kernels.hip) carves up ----
-size_t octree_lds_bytes(int maxCellsPerLevel, int cap, int ldsCand, bool globalNodes) {
-    if (globalNodes) return sizeof(int) * ((size_t) maxCellsPerLevel + 1 + 3 + 4 * (size_t) ldsCand);
-    // (k_octree: the candidates' second sort buffer lies over the cell table and the node arrays, the first one behind them)
-    const size_t region = (((size_t) maxCellsPerLevel + 1 + 3) & ~(size_t) 3) + 19 * (size_t) cap;
-    return sizeof(int) * (std::max(region, 2 * (size_t) ldsCand) + 2 * (size_t) ldsCand);
-}
-
+// ---- k_octree's dynamic LDS is oct_lds (lds_layout.h).  Its inverse for the sort plan: the candidates whose two pairs of sort buffers fit `budget` ----
 int octree_lds_cand(int maxCellsPerLevel, int cap, size_t budget) {
-    const long long region = (((long long) maxCellsPerLevel + 1 + 3) & ~3ll) + 19ll * cap, ints = (long long) (budget / sizeof(int));
+    const long long region = oct_lds_region(maxCellsPerLevel, cap), ints = (long long) (budget / sizeof(int));
     long long c = ints / 4;                              // the second buffer wider than the region it lies over
     if (2 * c < region) c = (ints - region) / 2;         // ... or inside it
     c &= ~3ll;
     return c < 256 ? 0 : (int) std::min(c, 8192ll);
 }
-
-size_t octree_hist_lds_bytes(int regionInts, int histBins) { return sizeof(int) * ((size_t) regionInts + (size_t) histBins + 1); }
 
 // Which octree plan a geometry takes -- NOT the budgets of the launches that run.  The per-list-position arrays (19 x cap ints) stay in LDS while one
 // workgroup fits the CU; very large per-level feature budgets move them to a global arena.  ldsCand = the candidates one 1024-thread launch of all levels
@@ -365,8 +356,8 @@ size_t octree_hist_lds_bytes(int regionInts, int histBins) { return sizeof(int) 
 // (OctPlan::SortOne).  The launches of the sort plan with LDS node arrays take plan_oct_sort's budgets (octree_lds_cand: the second sort
 // buffer over the node arrays) -- a change to one formula does not move the other.
 static void oct_sort_budget(const Geometry &G, bool *globalNodes, int *ldsCand) {
-    *globalNodes = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, 0, false) > 142 * 1024;
-    const size_t fixed = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, 0, *globalNodes);
+    *globalNodes = oct_lds_bytes(kOctLdsSort, G.maxCellsPerLevel, G.kpCapMax, 0, 0, 0) > 142 * 1024;
+    const size_t fixed = oct_lds_bytes(*globalNodes ? kOctLdsArena : kOctLdsSort, G.maxCellsPerLevel, G.kpCapMax, 0, 0, 0);
     const size_t budget = (size_t) 71 * 1024;   // two workgroups per CU beside 9 KB of static LDS each (radix histogram)
     *ldsCand = fixed + 16 * 256 < budget ? (int) ((budget - fixed) / 16) : 0;
     if (*ldsCand > 8192) *ldsCand = 8192;
@@ -386,7 +377,7 @@ std::vector<OctLaunch> plan_oct_sort(const Geometry &G, int L, bool oneGroup, in
         grp.block = b;
         const size_t budget = ldsBytes ? ldsBytes : (size_t) (b == 1024 ? 71 : b == 512 ? 44 : 36) * 1024;
         grp.ldsCand = octree_lds_cand(cells, grp.cap, budget);
-        grp.lds = octree_lds_bytes(cells, grp.cap, grp.ldsCand, false);
+        grp.lds = oct_lds_bytes(kOctLdsSort, cells, grp.cap, grp.ldsCand, 0, 0);
         out.push_back(grp);
     };
     if (oneGroup) {
@@ -431,10 +422,10 @@ static bool size_oct_hist_group(const Geometry &G, int l0, int n, int binsEnv, b
     int want = perNode ? 1024 : 8192;
     while (want < 16 * grp.cap && want < 8192) want *= 2;
     grp.histBins = binsEnv >= 4 && binsEnv <= 8192 ? binsEnv : want;
-    grp.regionInts = std::max(std::max(19 * grp.cap, cells), tabs);
-    if (octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.regionInts = std::max(19 * grp.cap, cells);   // keys without the tables
-    while (grp.histBins > 1024 && !binsEnv && octree_hist_lds_bytes(grp.regionInts, grp.histBins) > budget) grp.histBins /= 2;
-    grp.lds = octree_hist_lds_bytes(grp.regionInts, grp.histBins);
+    grp.regionInts = std::max(std::max(kOctNodeArrays * grp.cap, cells), tabs);
+    if (oct_lds_bytes(kOctLdsHist, 0, grp.cap, 0, grp.regionInts, grp.histBins) > budget) grp.regionInts = std::max(kOctNodeArrays * grp.cap, cells);   // keys without the tables
+    while (grp.histBins > 1024 && !binsEnv && oct_lds_bytes(kOctLdsHist, 0, grp.cap, 0, grp.regionInts, grp.histBins) > budget) grp.histBins /= 2;
+    grp.lds = oct_lds_bytes(kOctLdsHist, 0, grp.cap, 0, grp.regionInts, grp.histBins);
     *out = grp;
     return grp.lds <= budget;
 }
@@ -464,7 +455,7 @@ int plan_octree(const Geometry &G, int L, const PlanPins &pins, OctPlan &plan, s
         else plan.launches.clear();   // it does not fit: the sort plan
     }
     if (plan.kind != OctPlan::Hist) {
-        const size_t lds = octree_lds_bytes(G.maxCellsPerLevel, G.kpCapMax, ldsCand, arena);
+        const size_t lds = oct_lds_bytes(arena ? kOctLdsArena : kOctLdsSort, G.maxCellsPerLevel, G.kpCapMax, ldsCand, 0, 0);
         if (lds > 150 * 1024)
             return plan_fail(err, YGZF_ERR_UNSUPPORTED, "octree kernel needs %zu bytes of LDS (cells/level %d, list cap %d)", lds, G.maxCellsPerLevel, G.kpCapMax);
         // the sort plan's launches with LDS node arrays: level groups of their own workgroup size and LDS (oct_groups=1: one launch of all

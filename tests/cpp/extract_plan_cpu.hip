@@ -6,7 +6,7 @@
 #include <string>
 #include <vector>
 
-#include "ygzf_plan.h"
+#include "extract_sweep.h"
 
 using namespace ygzf;
 
@@ -18,43 +18,6 @@ static std::string g_where;
             if (g_failed++ < 40) fprintf(stderr, "FAILED %s: %s (line %d)\n", g_where.c_str(), #cond, __LINE__); \
         }                                                                                              \
     } while (0)
-
-struct Geo { int w, h, nl, nf; float sf; };
-struct Pin { const char *name; PlanPins p; };
-
-static std::vector<Pin> pin_sets() {
-    std::vector<Pin> v;
-    auto add = [&](const char *name, auto f) { Pin q{name, PlanPins()};   /* (a default PlanPins is the library's own choice: no environment is read) */ f(q.p); v.push_back(q); };
-    add("default", [](PlanPins &) {});
-    // tests/test_gpu_octree_groups.py (every context there pins the sort plan)
-    add("sort", [](PlanPins &p) { p.octPlan = PlanPins::Sort; });
-    add("sort,groups=1", [](PlanPins &p) { p.octPlan = PlanPins::Sort; p.octOneGroup = true; });
-    add("sort,block=256", [](PlanPins &p) { p.octPlan = PlanPins::Sort; p.octBlock = 256; });
-    add("sort,block=512", [](PlanPins &p) { p.octPlan = PlanPins::Sort; p.octBlock = 512; });
-    add("sort,block=1024", [](PlanPins &p) { p.octPlan = PlanPins::Sort; p.octBlock = 1024; });
-    add("sort,block=256,lds=8", [](PlanPins &p) { p.octPlan = PlanPins::Sort; p.octBlock = 256; p.octLdsBytes = 8 * 1024; });
-    add("sort,block=512,lds=24", [](PlanPins &p) { p.octPlan = PlanPins::Sort; p.octBlock = 512; p.octLdsBytes = 24 * 1024; });
-    add("sort,block=1024,lds=20", [](PlanPins &p) { p.octPlan = PlanPins::Sort; p.octBlock = 1024; p.octLdsBytes = 20 * 1024; });
-    // tests/test_gpu_octree_plans.py
-    add("hist", [](PlanPins &p) { p.octPlan = PlanPins::Hist; });
-    add("hist,bins=8192", [](PlanPins &p) { p.octPlan = PlanPins::Hist; p.octHistBins = 8192; });
-    add("hist,bins=512", [](PlanPins &p) { p.octPlan = PlanPins::Hist; p.octHistBins = 512; });
-    add("hist,bins=16", [](PlanPins &p) { p.octPlan = PlanPins::Hist; p.octHistBins = 16; });
-    add("hist,helpers=8,spin=0", [](PlanPins &p) { p.octPlan = PlanPins::Hist; p.octHelpers = 8; p.octHelperSpin = 0; });
-    // the pins alone (no plan pinned with them)
-    add("groups=1", [](PlanPins &p) { p.octOneGroup = true; });
-    add("block=256", [](PlanPins &p) { p.octBlock = 256; });
-    add("lds=8", [](PlanPins &p) { p.octLdsBytes = 8 * 1024; });
-    add("bins=16", [](PlanPins &p) { p.octHistBins = 16; });
-    add("bins=512", [](PlanPins &p) { p.octHistBins = 512; });
-    // tests/test_gpu_extract.py: the pyramid's pins
-    add("strip_frames=0", [](PlanPins &p) { p.pyrStripFrames = 0; });
-    add("strips=32", [](PlanPins &p) { p.pyrStrips = 32; });
-    add("strips=64", [](PlanPins &p) { p.pyrStrips = 64; });
-    add("strip_base=1", [](PlanPins &p) { p.pyrStripBase = 1; });
-    add("strip_base=2,strips=48", [](PlanPins &p) { p.pyrStripBase = 2; p.pyrStrips = 48; });
-    return v;
-}
 
 // every index build_geometry stored lies inside the table it points into
 static void check_geometry(const Geometry &G, int L) {
@@ -158,9 +121,9 @@ static void check_oct_plan(const Geometry &G, int L, const PlanPins &pins, const
         CHECK(g.cap >= 4 && g.cap % 4 == 0);
         for (int l = g.l0; l < g.l0 + g.n && l < L; l++) CHECK(g.cap >= G.lv[l].kpCap);
         CHECK(!g.arena || (plan.kind == OctPlan::SortOne && plan.launches.size() == 1));
-        if (plan.kind == OctPlan::Hist) CHECK(g.histBins >= 4 && g.ldsCand == 0 && g.block == kOctBlock && g.regionInts >= 19 * g.cap && g.lds == octree_hist_lds_bytes(g.regionInts, g.histBins));
+        if (plan.kind == OctPlan::Hist) CHECK(g.histBins >= 4 && g.ldsCand == 0 && g.block == kOctBlock && g.regionInts >= kOctNodeArrays * g.cap && g.lds == oct_lds_bytes(kOctLdsHist, 0, g.cap, 0, g.regionInts, g.histBins));
         else CHECK(g.histBins == 0 && g.regionInts == 0 && (g.ldsCand % 4 == 0 || g.arena));   // (the overlay of the LDS node arrays wants multiples of 4)
-        if (plan.kind == OctPlan::SortGroups) CHECK(g.lds >= sizeof(int) * (19 * (size_t) g.cap + 2 * (size_t) g.ldsCand) || g.lds == 16 * (size_t) g.ldsCand);
+        if (plan.kind == OctPlan::SortGroups) CHECK(g.lds >= oct_lds_bytes(kOctLdsSort, 0, g.cap, g.ldsCand, 0, 0));   // (the layout of a launch whose levels have no cells: the least)
     }
     CHECK(next == L);
     if (plan.kind == OctPlan::SortOne) CHECK(plan.launches.size() == 1 && plan.launches[0].block == kOctBlock && plan.launches[0].cap == G.kpCapMax);
@@ -175,7 +138,7 @@ static void check_oct_plan(const Geometry &G, int L, const PlanPins &pins, const
     if (plan.haveSmall) {
         const OctLaunch &g = plan.small;
         CHECK(g.l0 == 0 && g.n == L && g.histBins >= 4 && g.lds <= 150 * 1024 && g.cap == std::max(G.kpCapMax, 4) && g.block == kOctBlock && !g.arena && g.ldsCand == 0);
-        CHECK(g.lds == octree_hist_lds_bytes(g.regionInts, g.histBins) && g.regionInts >= 19 * g.cap);
+        CHECK(g.lds == oct_lds_bytes(kOctLdsHist, 0, g.cap, 0, g.regionInts, g.histBins) && g.regionInts >= kOctNodeArrays * g.cap);
     }
 }
 
@@ -206,18 +169,7 @@ static void check_fast(const Geometry &G0, const PlanPins &base) {
 }
 
 int main() {
-    std::vector<Geo> sweep = {{752, 480, 8, 1000, 1.2f}, {640, 480, 8, 1000, 1.2f}, {333, 517, 8, 1500, 1.2f}, {1280, 360, 6, 1200, 1.2f}, {1241, 376, 8, 500, 1.2f},
-                              {320, 240, 4, 3000, 1.2f}, {320, 240, 2, 5000, 1.2f}, {200, 150, 3, 150, 1.2f}, {130, 110, 8, 200, 1.2f}, {1920, 1080, 8, 4000, 1.2f},
-                              {3840, 2160, 12, 8000, 1.2f}, {752, 480, 12, 1000, 1.1f}, {640, 480, 4, 500, 2.0f}};
-    // the level-1 widths of test_pyramid_tiles_of_every_fold (tests/test_gpu_extract.py), as that test turns them into images
-    const int level1[] = {31, 32, 33, 64, 95, 128, 129, 160, 223, 224, 225, 255, 256, 257, 266, 288, 320, 383, 448, 479, 512, 522, 544, 767, 1000};
-    for (float sf : {1.1f, 1.2f, 1.27f}) {
-        int i = 0;
-        for (int w1 : level1) {
-            const int hs[4] = {64, 97, 130, 301};
-            sweep.push_back({(int) std::nearbyint((double) w1 * (double) sf) + 1, hs[i++ % 4], 3, 200, sf});
-        }
-    }
+    const std::vector<Geo> sweep = geo_sweep();
     const std::vector<Pin> pins = pin_sets();
     int walked = 0, wideCells = 0;
     for (const Geo &q : sweep) {

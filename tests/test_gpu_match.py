@@ -137,6 +137,49 @@ def test_search_by_projection_mappoints(oracle):
         assert e_n > 50
 
 
+@pytest.fixture(scope="module")
+def dense_pair():
+    """two frames of one scene with some thousand keypoints each, for the tests that choose their own keypoint counts"""
+    from orb_ygz_slam_amd import Extractor
+    w, h = 1000, 760
+    ex = Extractor(5000, 1.2, 8, 20, 7, max_width=w, max_height=h, max_batch=1)
+    base = synth_frame(70, w + 16, h + 16)
+    ka, da = ex.extract(base[8:8 + h, 8:8 + w])
+    kb, db = ex.extract(base[9:9 + h, 11:11 + w])
+    return ex, w, h, ka, da, kb, db
+
+
+@pytest.mark.parametrize("deep,k", [(0, 0), (0, 1), (0, 2), (1, 0)])
+def test_lds_plan_switches_equal_oracle(oracle, dense_pair, deep, k):
+    """k_match_last's four LDS plans (csrc/lds_layout.h: everything in LDS; descriptors in global memory; + the speculative lists; + the misc
+    arrays) at the keypoint counts where plan_match_lds changes from plan k to plan k + 1: the last count plan k admits and the first that
+    plan k + 1 takes, both frames equal -- the three switches of SearchByProjection(Cur, Last) and the first of SearchByProjection(F, MapPoints),
+    whose lists of eight (`deep`) move it.  The counts come from the layout program (tests/cpp/lds_layout_cpu.hip), not from here."""
+    from orb_ygz_slam_amd import make_camera, EUROC
+    from tests import lds_layout_prog
+    ex, w, h, ka, da, kb, db = dense_pair
+    last = {(d, p): c for d, p, c in lds_layout_prog.table()["matcher_switch"]}[deep, k]
+    assert 0 < last and last + 1 <= min(len(ka), len(kb)), (last, len(ka), len(kb))
+    sf = oracle.Extractor(5000, 1.2, 8, 20, 7).tables()["scale"]
+    cam = make_camera(w, h)
+    I, z = np.eye(3, dtype=np.float32), np.zeros(3, np.float32)
+    for n in (last, last + 1):
+        a, ad, b, bd = ka[:n], da[:n], kb[:n], db[:n]
+        if not deep:
+            e = oracle.search_by_projection_last(b, bd, sf, w, h, EUROC, a, _unit_world(a, EUROC), ad, I, z, I, z, 15.0)
+            g = ex.search_by_projection_last(cam, b, bd, a, _unit_world(a, EUROC), ad, I, z, I, z, 15.0, scale_factors=sf)
+        else:
+            rng = np.random.default_rng(11)
+            tiv = (rng.uniform(size=n) > 0.15).astype(np.uint8)
+            px, py = (a["x"] - 3.0).astype(np.float32), (a["y"] - 1.0).astype(np.float32)   # where the second crop shows them
+            vc = rng.uniform(0.99, 1.0, n).astype(np.float32)
+            lvl = a["octave"].astype(np.int32)
+            e = oracle.search_by_projection_mappoints(b, bd, sf, w, h, EUROC, tiv, px, py, vc, lvl, ad, 3.0, True, 0.8)
+            g = ex.search_by_projection_mappoints(cam, b, bd, tiv, px, py, vc, lvl, ad, 3.0, True, 0.8, scale_factors=sf)
+        assert g[0] == e[0] and (g[1] == e[1]).all() and (g[2] == e[2]).all(), (deep, k, n)
+        assert e[0] > 50
+
+
 def test_search_by_projection_keyframe(oracle):
     """SearchByProjection(Cur, KF, found, th, ORBdist) (relocalisation refinement, src/ORBmatcher.cc:1352-1469): the oracle runs the whole
     function; the device gets the host prologue's (valid, u, v, level) and must reproduce assignment, ownership and count."""
