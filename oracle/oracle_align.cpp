@@ -472,6 +472,11 @@ AlignResult sparse_img_align(const AlignFrame &ref, const AlignFrame &cur, int m
     for (int level = max_level; level >= min_level; level -= 1) {
         A.level_ = level;
         std::fill(A.jacobian_cache_.begin(), A.jacobian_cache_.end(), 0.f);
+        // device-order mode: the gradients and their moments are what stands for the Jacobian rows there, so they are zeroed with them -- a feature
+        // that is visible from a coarser level and leaves this level's border keeps its patch under ZERO gradients (tests/align_cases.py, stale_*)
+        std::fill(A.dx_cache_.begin(), A.dx_cache_.end(), 0.f);
+        std::fill(A.dy_cache_.begin(), A.dy_cache_.end(), 0.f);
+        std::fill(A.mom_cache_.begin(), A.mom_cache_.end(), 0.f);
         A.have_ref_patch_cache_ = false;
         A.n_iter_ = n_iter;  // reference indexes iterations[level_] = 10 (OOB for level >= 6; defined as n_iter)
         A.optimizeGaussNewton(T_cur_from_ref);

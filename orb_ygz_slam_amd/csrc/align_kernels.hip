@@ -15,6 +15,7 @@
 
 #include "kernels.h"
 #include "se3_device.h"
+#include "sia_gate.h"
 #include "wave_ops.h"
 
 namespace ygzf {
@@ -278,10 +279,9 @@ __device__ __forceinline__ Se3 se3_exp_wave(const float a[6], int lane) {
 // pixels.  The arithmetic -- which products are fused included -- is part of the aligner's definition (oracle/oracle_align.cpp's device-order mode
 // repeats it): k_sia_run and k_sia_precompute share this one body.
 __device__ __forceinline__ bool sia_ref_patch(const SiaLevel &Lr, float scale, float2 kp, float (&V)[36], float4 &mom) {
-    const int border = 3;                       // patch_halfsize_ + 1
     const float u_ref = kp.x * scale, v_ref = kp.y * scale;
-    const int u_ref_i = (int) floorf(u_ref), v_ref_i = (int) floorf(v_ref);
-    if (u_ref_i - border < 0 || v_ref_i - border < 0 || u_ref_i + border >= Lr.w || v_ref_i + border >= Lr.h) return false;
+    int u_ref_i, v_ref_i;
+    if (!sia_patch_inside(u_ref, v_ref, Lr.w, Lr.h, u_ref_i, v_ref_i)) return false;
     const float su = u_ref - u_ref_i, sv = v_ref - v_ref_i;
     // the reference forms these in double and rounds to float: with u, v >= 3 the fractions are multiples of 2^-22, so 1 - su and
     // 1 - sv are exact in fp32 and the fp32 product is the same single rounding of the same exact product
@@ -363,15 +363,14 @@ __global__ __launch_bounds__(256) void k_sia_precompute(SiaArgs A) {
 // V: the feature's 6 x 6 reference grid (sia_ref_patch), S: its gradient moments (w != 0: gradients are zero at this level).
 __device__ __forceinline__ void sia_accumulate_feature(const SiaArgs &A, const Se3 &T, const SiaLevel &Lc, float scale, bool staged, const uint8_t *s_cur,
                                                        const float4 ft, const float4 *jacp, const float (&V)[36], const float4 S, float (&acc)[kAcc]) {
-    const int border = 3;                       // patch_halfsize_ + 1
-        if (ft.w == 0.f) return;
+    if (ft.w == 0.f) return;
     const float xr[3] = {ft.x, ft.y, ft.z};
     float xc[3];
     se3_act(T, xr, xc);
     const float ucx = A.fx * xc[0] / xc[2] + A.cx, ucy = A.fy * xc[1] / xc[2] + A.cy;   // Frame::Camera2Pixel
     const float u_cur = ucx * scale, v_cur = ucy * scale;
-    const int ui = (int) floorf(u_cur), vi = (int) floorf(v_cur);
-    if (ui < 0 || vi < 0 || ui - border < 0 || vi - border < 0 || ui + border >= Lc.w || vi + border >= Lc.h) return;
+    int ui, vi;
+    if (!sia_patch_inside(u_cur, v_cur, Lc.w, Lc.h, ui, vi)) return;   // (the reference's extra "ui < 0 || vi < 0" is implied)
     acc[29] += 1.f;
     const float su = u_cur - ui, sv = v_cur - vi;
     // the reference forms these in double and rounds to float: with u, v >= 3 the fractions are multiples of 2^-22, so 1 - su and

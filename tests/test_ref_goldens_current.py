@@ -12,7 +12,7 @@ from oracle import oracle_py as O
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GENERATORS = [("make_golden_triangulation", "triangulation_ref.npz"), ("make_golden_matcher_ref", "matcher_ref.npz"), ("make_golden_extract_ref", "extract_ref.npz"),
               ("make_golden_frame_ref", "frame_ref.npz"), ("make_golden_stereo_bow_ref", "stereo_bow_ref.npz"), ("make_golden_direct_ref", "direct_ref.npz"),
-              ("make_golden_align_ref", "align_ref.npz")]
+              ("make_golden_align_ref", "align_ref.npz"), ("make_golden_align_cases_ref", "align_cases_ref.npz")]
 HAVE = all(f() is not None for f in (O.ref_matcher_lib, O.ref_extractor_lib, O.ref_frame_lib, O.ref_mappoint_lib, O.ref_dbow2_lib))
 
 pytestmark = pytest.mark.skipif(not HAVE, reason="oracle/_ref libraries not built (reference checkout absent)")
