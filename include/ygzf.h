@@ -833,6 +833,48 @@ int ygzf_remap_batch_device(ygzf_ctx *ctx, int map_id, const uint8_t *d_src, int
 int ygzf_remap_host(ygzf_ctx *ctx, int map_id, const uint8_t *src, int src_stride, uint8_t *dst, int dst_stride);
 int ygzf_compute_pyramid_remapped(ygzf_ctx *ctx, int map_id, const uint8_t *img, int stride, uint8_t *const *levels_out);
 
+/* ---- Optimizer::PoseOptimization(Frame *pFrame)   src/Optimizer.cc:1656-1842 -----------------------------------------------------------
+ * The motion-only problem of the tracking thread: one SE3 vertex, one unary reprojection edge per correspondence (monocular where
+ * mvuRight[i] < 0, stereo otherwise), Huber kernels, four rounds of <= 10 Levenberg iterations with the chi2 classification between them --
+ * g2o's arithmetic in fp64 (OptimizationAlgorithmLevenberg with the vendored stop rule, the dense pivoted LDLT, the ...OnlyPose edges of
+ * types_six_dof_expmap with their `float invz`, Sophus SE3d::exp), restated in tests/pose_opt_cases.py.  The IMU overloads and every bundle
+ * adjustment stay the reference's.
+ *
+ * n_problems frames per call, each independent of the others (the first pass over Relocalization's candidates, the frames of a clip): one
+ * upload, one launch (a workgroup per problem), one download, one synchronisation.  Per problem:
+ *   Tcw_out[7 k ..]      the optimised pose as SetPose receives it (estimate().cast<float>(), layout of ygzf_sia_frame::Tcw);
+ *   Tcw_out_f64[7 k ..]  the double estimate it was cast from (may be NULL);
+ *   outlier[k]           mvbOutlier, n bytes, in / out: entries of correspondences are written, every other entry is left as it is;
+ *   ret[k]               nInitialCorrespondences - nBad;
+ *   info[k]              (may be NULL) per round: iterations run, Levenberg trials, why the round ended, lambda and the active robust chi2 at its end.
+ * A problem with fewer than 3 correspondences returns ret = 0 and its pose unchanged, bit for bit (its correspondences' outlier entries are
+ * cleared, as the reference has done by then), whatever its neighbours in the batch do.
+ * inv_level_sigma2: mvInvLevelSigma2 -- read up to the largest octave any correspondence names, so it must have that many entries + 1 (at
+ * most 16 levels); NULL: the context's own tables, and octaves below the context's level count.  cam: fx fy cx cy and mbf are read.  Any n >= 0 is accepted: the transfer block and the per-edge scratch are grow-on-demand buffers of the context.
+ * YGZF_ERR_INVALID: a NULL argument or array, n_problems <= 0, n < 0, a correspondence's octave outside those levels. */
+typedef struct ygzf_pose_problem {
+    int n;                      /* Frame::N */
+    const ygzf_kp *keys;        /* mvKeys: pt, octave */
+    const float *u_right;       /* mvuRight, NULL = all monocular */
+    const uint8_t *mp_valid;    /* mvpMapPoints[i] != NULL */
+    const float *mp_world;      /* GetWorldPos, n x 3 */
+    float Tcw[7];               /* qx qy qz qw tx ty tz, as ygzf_sia_frame */
+} ygzf_pose_problem;
+typedef enum ygzf_pose_stop {
+    YGZF_POSE_STOP_MAX_ITERATIONS = 0,   /* all ten iterations ran */
+    YGZF_POSE_STOP_TRIALS = 1,           /* maxTrialsAfterFailure trials failed in one iteration */
+    YGZF_POSE_STOP_RHO_ZERO = 2,         /* a trial changed nothing: rho == 0 */
+    YGZF_POSE_STOP_NO_PROGRESS = 3,      /* (iniChi - currentChi) * 1e3 < iniChi three iterations in a row */
+    YGZF_POSE_STOP_NOT_RUN = 4           /* the round did not run (fewer than 3 correspondences; fewer than 10 after round 0) */
+} ygzf_pose_stop;
+typedef struct ygzf_pose_info {
+    int iterations[4], trials[4], stop[4];
+    double lambda[4], chi2[4];
+    int n_initial;              /* nInitialCorrespondences */
+} ygzf_pose_info;
+int ygzf_pose_optimization(ygzf_ctx *ctx, const ygzf_camera *cam, const float *inv_level_sigma2, int n_problems, const ygzf_pose_problem *p,
+                           float *Tcw_out, double *Tcw_out_f64, uint8_t *const *outlier, int *ret, ygzf_pose_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -83,6 +83,18 @@ class SiaFrame(C.Structure):
                 ("level_h", C.c_void_p)]
 
 
+class PoseProblem(C.Structure):   # ygzf_pose_problem
+    _fields_ = [("n", C.c_int), ("keys", C.c_void_p), ("u_right", C.c_void_p), ("mp_valid", C.c_void_p), ("mp_world", C.c_void_p), ("Tcw", C.c_float * 7)]
+
+
+class PoseInfo(C.Structure):      # ygzf_pose_info
+    _fields_ = [("iterations", C.c_int * 4), ("trials", C.c_int * 4), ("stop", C.c_int * 4), ("lam", C.c_double * 4), ("chi2", C.c_double * 4),
+                ("n_initial", C.c_int)]
+
+
+POSE_STOP_MAX_ITERATIONS, POSE_STOP_TRIALS, POSE_STOP_RHO_ZERO, POSE_STOP_NO_PROGRESS, POSE_STOP_NOT_RUN = range(5)   # ygzf_pose_stop
+
+
 # EuRoC cam0 intrinsics (reference Examples/Monocular/EuRoC.yaml:8-11), used by bench.py / tests
 EUROC = dict(fx=458.654, fy=457.296, cx=367.215, cy=248.375)
 
@@ -256,6 +268,7 @@ def load_library(build_if_missing=True):
     L.ygzf_remap_batch_device.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_size_t]
     L.ygzf_remap_host.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
     L.ygzf_compute_pyramid_remapped.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
+    L.ygzf_pose_optimization.argtypes = [vp, C.POINTER(Camera), vp, C.c_int, C.POINTER(PoseProblem), vp, vp, C.POINTER(vp), vp, C.POINTER(PoseInfo)]
     L.ygzf_stream.argtypes = [vp]
     L.ygzf_stream.restype = vp
     _lib = L
@@ -1163,6 +1176,36 @@ class Extractor:
         self._ck(self.L.ygzf_sia_run(self.h, C.byref(R), C.byref(Cf), C.byref(cam), _p(isf), max_level, min_level, n_iter, _p(out7),
                                      C.byref(ret), _p(info), _p(H)))
         return int(ret.value), out7, info, H.reshape(6, 6)
+
+    def pose_optimization(self, cam, problems, inv_level_sigma2=None):
+        """Optimizer::PoseOptimization(Frame *) over a batch of frames in one call (ygzf_pose_optimization).  problems: dicts with keys (KP_DTYPE),
+        u_right (None: all monocular), mp_valid (bytes), world (n x 3), Tcw (7 floats) and outlier (mvbOutlier before the call; None: zeros).
+        -> list of dicts: Tcw (float32[7]), Tcw64 (float64[7]), outlier (uint8[n]), ret, iterations / trials / stop / lam / chi2 (per round)."""
+        B = len(problems)
+        recs = (PoseProblem * max(B, 1))()
+        keep, flags = [], []
+        for k, q in enumerate(problems):
+            keys = np.ascontiguousarray(q["keys"], KP_DTYPE)
+            n = len(keys)
+            ur = None if q.get("u_right") is None else np.ascontiguousarray(q["u_right"], np.float32)
+            valid = np.ascontiguousarray(q["mp_valid"], np.uint8)
+            world = np.ascontiguousarray(q["world"], np.float32).reshape(-1, 3)
+            assert len(valid) == n and len(world) == n and (ur is None or len(ur) == n)
+            f = np.zeros(max(n, 1), np.uint8)
+            if q.get("outlier") is not None:
+                f[:n] = np.asarray(q["outlier"], np.uint8)
+            keep += [keys, ur, valid, world]
+            flags.append(f)
+            recs[k] = PoseProblem(n, _p(keys), None if ur is None else _p(ur), _p(valid), _p(world), (C.c_float * 7)(*np.asarray(q["Tcw"], np.float32)))
+        T32, T64 = np.zeros((max(B, 1), 7), np.float32), np.zeros((max(B, 1), 7), np.float64)
+        ret = np.zeros(max(B, 1), np.int32)
+        info = (PoseInfo * max(B, 1))()
+        fl = (C.c_void_p * max(B, 1))(*[f.ctypes.data for f in flags])
+        isg = None if inv_level_sigma2 is None else np.ascontiguousarray(inv_level_sigma2, np.float32)
+        self._ck(self.L.ygzf_pose_optimization(self.h, C.byref(cam), None if isg is None else _p(isg), B, recs, _p(T32), _p(T64), fl, _p(ret), info))
+        return [dict(Tcw=T32[k].copy(), Tcw64=T64[k].copy(), outlier=flags[k][:recs[k].n].copy(), ret=int(ret[k]), iterations=list(info[k].iterations),
+                     trials=list(info[k].trials), stop=list(info[k].stop), lam=list(info[k].lam), chi2=list(info[k].chi2), n_initial=info[k].n_initial)
+                for k in range(B)]
 
     def sia_run_cached(self, cam, ref_slot, cur_slot, ref_keys, ref_world, ref_Tcw7, cur_Tcw7, inv_scale, max_level, min_level, n_iter=10,
                        mp_valid=None, outlier=None):

@@ -48,6 +48,7 @@ inline int mat_refcount(const cv::Mat &m) {
 #include <cstring>
 #include <map>
 #include <memory>
+#include <mutex>
 #include <vector>
 
 #define CV_8U 0
@@ -174,6 +175,7 @@ public:
     inline void Replace(MapPoint *pMP);
     inline void ComputeDistinctiveDescriptors();
     inline int PredictScale(const float &currentDist, KeyFrame *pKF);
+    static inline std::mutex mGlobalMutex;   // include/MapPoint.h:134: held while Optimizer::PoseOptimization reads the points (src/Optimizer.cc:1694)
 };
 class Frame {  // the members the hot path reads/writes (reference include/Frame.h)
 public:
@@ -195,6 +197,9 @@ public:
     long unsigned int mnId = 0;
     ORBextractor *mpORBextractorLeft = nullptr;   // the extractor whose ComputePyramid built mvImagePyramid (include/Frame.h:220)
     DBoW2::BowVector mBowVec;                     // read by KeyFrameDatabase::DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:180-284)
+    // read and written by Optimizer::PoseOptimization (src/Optimizer.cc:1656-1842)
+    std::vector<float> mvInvLevelSigma2;
+    void SetPose(const SE3f &Tcw) { mTcw = Tcw; }   // (the reference also refreshes mRcw / mtcw / mOw: src/Frame.cc:338-346)
 };
 inline int MapPoint::PredictScale(const float &currentDist, Frame *pF) {  // src/MapPoint.cc:359-373
     float ratio = mfMaxDistance / currentDist;

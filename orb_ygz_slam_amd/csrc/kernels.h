@@ -485,5 +485,32 @@ struct RemapArgs {
 void launch_remap_tiles(hipStream_t st, const RemapArgs &A, int nTiles);    // Inside / Lds / Empty tiles only (the box is staged in LDS)
 void launch_remap_gather(hipStream_t st, const RemapArgs &A, int nTiles);   // any tile (bounds-checked byte loads from global memory)
 
+// ---- Optimizer::PoseOptimization(Frame *) (pose_kernels.hip): one workgroup of 256 threads per problem, all four rounds in one launch ----
+struct PoseProblemDev {             // one frame; device pointers
+    const ygzf_kp *keys;
+    const float *uRight;            // null: all monocular
+    const uint8_t *mpValid;
+    const float *world;             // n x 3
+    uint8_t *outlier;               // n bytes, in / out (mvbOutlier); doubles as the edges' level between the rounds
+    double *stored;                 // n doubles of scratch: chi2 of every edge's last computeError
+    int n;
+    float Tcw[7];
+};
+struct PoseOut {                    // per problem
+    double T[7];                    // the last round's estimate (not written when ret == 0 for want of correspondences)
+    double lambda[4], chi2[4];
+    int iters[4], trials[4], stop[4];
+    int ret, nInitial;
+};
+enum PoseStop { kPoseMaxIter = 0, kPoseTrials = 1, kPoseRhoZero = 2, kPoseNBad = 3, kPoseNotRun = 4 };
+struct PoseArgs {
+    const PoseProblemDev *probs;
+    PoseOut *out;
+    double fx, fy, cx, cy, bf;
+    double deltaMono, deltaStereo;  // double(float(sqrt(5.991))), double(float(sqrt(7.815)))
+    float invSigma2[kMaxLevels];
+};
+void launch_pose_opt(hipStream_t st, const PoseArgs &A, int nProblems);
+
 }  // namespace ygzf
 #endif

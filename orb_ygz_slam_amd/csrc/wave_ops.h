@@ -80,6 +80,26 @@ __device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v)
     return r;
 }
 
+// fp64 sum over the 64 lanes in ONE fixed order, the same in every lane and on every run: a balanced tree of neighbours -- lanes 2k + (2k + 1)
+// (quad_perm [1,0,3,2]), pairs (quad_perm [2,3,0,1]), quads (row_half_mirror = 0x141), half rows (row_mirror = 0x140), then rows (0 + 1) + (2 + 3).
+// Every step is symmetric (a + b on one side, b + a on the other), so no lane's result depends on which side it sat on; both halves of the
+// double travel through the same DPP step.  k_pose_opt's "device order" (tests/pose_opt_cases.py restates it).
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#define YGZF_F64_STEP(CTRL)                                                                                                        \
+    {                                                                                                                              \
+        const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, 0xf, 0xf, false);                                   \
+        const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, 0xf, 0xf, false);                                   \
+        v = v + __hiloint2double(hi, lo);                                                                                          \
+    }
+    YGZF_F64_STEP(0xb1) YGZF_F64_STEP(0x4e) YGZF_F64_STEP(0x141) YGZF_F64_STEP(0x140)
+#undef YGZF_F64_STEP
+    double r[4];
+#pragma unroll
+    for (int l = 0; l < 4; l++)
+        r[l] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16 * l), __builtin_amdgcn_readlane(__double2loint(v), 16 * l));
+    return (r[0] + r[1]) + (r[2] + r[3]);
+}
+
 // LDS hand-off inside one wave: orders this wave's LDS writes before its later LDS reads by other lanes.  Where each wave works on LDS of its
 // own no block barrier is needed -- and none is allowed where waves of a block may exit early.
 __device__ __forceinline__ void wave_lds_handoff() {
