@@ -19,6 +19,7 @@
 #include "wave_ops.h"
 #include "describe_lds.h"
 #include "fast9_quad.h"
+#include "fast_lane_quads.h"
 #include "orb_pattern_table.h"
 
 namespace ygzf {
@@ -730,10 +731,16 @@ __device__ __forceinline__ unsigned fast9_quad(const unsigned *w, int pd, int t)
     return f9::polarity(R, f9::thresholds(b3, t));   // per byte: 1 bright corner, 2 dark corner, 0 none
 }
 
-// a / x for 0 <= a <= 64, 1 <= x <= 64 as (a * kRcp16[x]) >> 16 (exact in that range): lane -> (row, column) splits without the
-// 30-instruction integer division sequence; x is wave-uniform, so the table read is one scalar load.
-__constant__ unsigned kRcp16[65] = {0, 65537, 32769, 21846, 16385, 13108, 10923, 9363, 8193, 7282, 6554, 5958, 5462, 5042, 4682, 4370, 4097, 3856, 3641, 3450, 3277, 3121, 2979, 2850, 2731, 2622, 2521, 2428, 2341, 2260, 2185, 2115, 2049, 1986, 1928, 1873, 1821, 1772, 1725, 1681, 1639, 1599, 1561, 1525, 1490, 1457, 1425, 1395, 1366, 1338, 1311, 1286, 1261, 1237, 1214, 1192, 1171, 1150, 1130, 1111, 1093, 1075, 1058, 1041, 1025};
-__device__ __forceinline__ int div_small(int a, unsigned m) { return (int) (__umul24((unsigned) a, m) >> 16); }   // both < 2^24: full-rate multiply
+// a / x for 0 <= a <= 64, 1 <= x <= 64 as (a * kRcp16.v[x]) >> 16 (exact in that range, csrc/fast_lane_quads.h): lane -> (row, column) splits
+// without the 30-instruction integer division sequence; x is wave-uniform, so the table read is one scalar load.
+struct Rcp16 { unsigned v[65]; };
+constexpr Rcp16 make_rcp16() {
+    Rcp16 t{};
+    for (int x = 0; x <= 64; x++) t.v[x] = lq::rcp16(x);
+    return t;
+}
+__constant__ Rcp16 kRcp16 = make_rcp16();
+using lq::div_small;
 
 // 3x3 NMS of a listed corner on the score map: survivor at minTh (strictly above all 8 neighbours) and at iniTh.  A corner of
 // FAST(iniTh) has score >= iniTh and competes with the neighbours of score >= iniTh only -- but a neighbour below iniTh <= s cannot
@@ -781,24 +788,38 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
         const int nquadsAll = ((dw + 3) >> 2) * dh;
         {
             const int nq = (dw + 3) >> 2, nquads = nq * dh;
-            const unsigned lastMask = 0x03030303u >> (8 * (4 * nq - dw));
-            const unsigned mnq = kRcp16[nq];
-            int y = div_small(lane, mnq), q = lane - __mul24(y, nq);
-            const int qy = div_small(64, mnq), qx = 64 - qy * nq;
-            for (int base = 0; base < nquads; base += 64) {
+            const unsigned lastMask = lq::last_quad_mask(dw, nq);
+            // Which quad a lane holds in which round: csrc/fast_lane_quads.h.  Where nq divides 64 (wave-uniform, decided here once; nq = 8 for
+            // every cell 29 .. 32 px wide) the lane keeps its column: a round costs it the bound test and two additions, its window address
+            // moves by the wave-uniform rowBytes.  Other widths (cells clipped at the right border) step (y, q) with a wrap and place the lane anew.
+            // The two walks are two loops (one loop with a uniform branch around the step made the compiler copy the walk's registers every
+            // round); the round itself is stated once.  wp = the quad's window dwords: rows y .. y + 6, dwords q .. q + 2.
+            auto round = [&](const lq::Walk &w, const uint8_t *wp) {
                 unsigned pb = 0;
-                if (base + lane < nquads) {
-                    pb = fast9_quad((const unsigned *) (win + __mul24(y, P)) + q, P >> 2, th);
-                    pb &= (q == nq - 1) ? lastMask : 0x03030303u;
-                }
+                if (lq::active(w)) pb = fast9_quad((const unsigned *) wp, P >> 2, th) & w.mask;
                 const unsigned long long m = __ballot(pb != 0);
                 if (m) {
-                    if (pb) qlist[nQ + (int) __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u))] =
-                                __builtin_amdgcn_bitop3_b32(pb, (unsigned) y << 2, (unsigned) q << 10, 0xFE);   // a | b | c at the full rate (not v_or3_b32)
+                    if (pb) qlist[nQ + (int) __builtin_amdgcn_mbcnt_hi((unsigned) (m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned) m, 0u))] = pb | w.yq;
                     nQ += __popcll(m);
                 }
-                y += qy; q += qx;
-                if (q >= nq) { q -= nq; y++; }
+            };
+            if (lq::fixed_column(nq)) {
+                const int sy = 64 >> lq::log2_quads(nq), rowBytes = sy * P;
+                lq::Walk w = lq::start_fixed(lane, nq, dh, lastMask);
+                const uint8_t *wp = win + __mul24(w.y, P) + 4 * w.q;
+                for (int base = 0; base < nquads; base += 64) {
+                    round(w, wp);
+                    lq::step_fixed(w, sy);
+                    wp += rowBytes;
+                }
+            } else {
+                const unsigned mnq = kRcp16.v[nq];
+                const int sy = div_small(64, mnq), sq = 64 - sy * nq;
+                lq::Walk w = lq::start_generic(lane, nq, mnq, dh, lastMask);
+                for (int base = 0; base < nquads; base += 64) {
+                    round(w, win + __mul24(w.y, P) + 4 * w.q);
+                    lq::step_generic(w, nq, sy, sq, dh, lastMask);
+                }
             }
         }
         if (sampled && lane == 0) { atomicAdd(&st[4], (unsigned) nQ); atomicAdd(&st[5], (unsigned) nquadsAll); atomicAdd(&st[7], 1u); }   // corner-bearing quads / quads / pass-1 runs
@@ -907,7 +928,7 @@ __device__ __forceinline__ void fast_cell_process(uint8_t *win, uint8_t *smap, u
         } else {
             // ---- dense fallback (corner list overflow, never on natural images: > 512 corners in one cell): score and NMS every pixel ----
             const int npix = dw * dh;
-            const unsigned mdw = kRcp16[dw];
+            const unsigned mdw = kRcp16.v[dw];
             const int py = div_small(64, mdw), px = 64 - py * dw;
             {
                 int y = div_small(lane, mdw), x = lane - y * dw;
@@ -1003,7 +1024,7 @@ __device__ __forceinline__ void fast_cell(const FrameSet &fs, const LevelGeom *_
         const unsigned sh = g0 & 3u;
         const unsigned *src = (const unsigned *) (img + (unsigned) iniY * (unsigned) pitch + (g0 & ~3u));
         const unsigned pitch4 = (unsigned) pitch >> 2;
-        const unsigned mnd = kRcp16[nd];
+        const unsigned mnd = kRcp16.v[nd];
         int r = div_small(lane, mnd), d = lane - __mul24(r, nd);
         const int sr = div_small(64, mnd), sd = 64 - sr * nd;
         constexpr int kU = 6;
