@@ -875,6 +875,38 @@ typedef struct ygzf_pose_info {
 int ygzf_pose_optimization(ygzf_ctx *ctx, const ygzf_camera *cam, const float *inv_level_sigma2, int n_problems, const ygzf_pose_problem *p,
                            float *Tcw_out, double *Tcw_out_f64, uint8_t *const *outlier, int *ret, ygzf_pose_info *info);
 
+/* ---- Sim3Solver's RANSAC hypotheses   src/Sim3Solver.cc:132-193 (iterate), :209-315 (ComputeSim3), :318-338 (CheckInliers) --------------------
+ * Step 2 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:221-330), between SearchByBoW and SearchBySim3.  A hypothesis -- Horn's closed form
+ * on three correspondences, then both projections of every correspondence against the integer gates -- depends on nothing but its triple, so
+ * the hypotheses of every loop candidate are evaluated in one call; the order-dependent part of iterate (best-so-far, the strict return rule,
+ * bNoMore) is replayed on the host from the counts (host/Sim3Replay.h, host/Sim3Solver.cc).  The arithmetic is fp32 with the cv::Mat
+ * roundings of OpenCV 2.4 / 3.2 as this header fixes them above (float gemm left to right, double factor in scalar * Mat, double accumulation
+ * in dot); cv::eigen is a cyclic Jacobi solver and the rotation is built from the quaternion without trigonometry (csrc/sim3_math.h,
+ * restated in tests/sim3_cases.py).  A triple whose quaternion has an exactly zero imaginary part gives the reference's 0 / 0: hyp is NaN
+ * and the count 0.  There is no depth gate.
+ *
+ * n_problems solvers per call: one upload, one launch, one download, one synchronisation.  Per problem k:
+ *   hyp[k]          n_hyp x 13 floats: R12 row-major, t12, s12 (mR12i, mt12i, ms12i of each iteration);
+ *   n_inliers[k]    n_hyp ints: mnInliersi;
+ *   inlier_bits[k]  n_hyp x ceil(n / 64) words, bit i of word j = mvbInliersi[64 j + i], the bits beyond n zero.  The array, or any entry, may be NULL.
+ * A problem with n_hyp == 0 is legal and nothing of it is read or written (its pointers may be NULL).  Any n and n_hyp are accepted: the
+ * transfer block is a grow-on-demand buffer of the context.
+ * YGZF_ERR_INVALID: a NULL argument or array, n_problems <= 0, n_hyp < 0, n < 3 with n_hyp > 0, a sample index outside [0, n), an index
+ * repeated within a triple. */
+typedef struct ygzf_sim3_problem {
+    int n;                      /* N: the correspondences the constructor kept */
+    const float *X3Dc1;         /* mvX3Dc1, n x 3 */
+    const float *X3Dc2;         /* mvX3Dc2, n x 3 */
+    const float *max_err1;      /* mvnMaxError1 as floats: (float) (size_t) (9.210 * sigma2), already truncated */
+    const float *max_err2;
+    float K1[4], K2[4];         /* fx fy cx cy of mK1 / mK2 */
+    int fix_scale;              /* mbFixScale */
+    int n_hyp;
+    const int *samples;         /* n_hyp x 3 */
+} ygzf_sim3_problem;
+int ygzf_sim3_ransac(ygzf_ctx *ctx, int n_problems, const ygzf_sim3_problem *problems, float *const *hyp, int *const *n_inliers,
+                     uint64_t *const *inlier_bits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -87,6 +87,11 @@ class PoseProblem(C.Structure):   # ygzf_pose_problem
     _fields_ = [("n", C.c_int), ("keys", C.c_void_p), ("u_right", C.c_void_p), ("mp_valid", C.c_void_p), ("mp_world", C.c_void_p), ("Tcw", C.c_float * 7)]
 
 
+class Sim3Problem(C.Structure):   # ygzf_sim3_problem
+    _fields_ = [("n", C.c_int), ("X3Dc1", C.c_void_p), ("X3Dc2", C.c_void_p), ("max_err1", C.c_void_p), ("max_err2", C.c_void_p), ("K1", C.c_float * 4),
+                ("K2", C.c_float * 4), ("fix_scale", C.c_int), ("n_hyp", C.c_int), ("samples", C.c_void_p)]
+
+
 class PoseInfo(C.Structure):      # ygzf_pose_info
     _fields_ = [("iterations", C.c_int * 4), ("trials", C.c_int * 4), ("stop", C.c_int * 4), ("lam", C.c_double * 4), ("chi2", C.c_double * 4),
                 ("n_initial", C.c_int)]
@@ -269,6 +274,7 @@ def load_library(build_if_missing=True):
     L.ygzf_remap_host.argtypes = [vp, C.c_int, vp, C.c_int, vp, C.c_int]
     L.ygzf_compute_pyramid_remapped.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
     L.ygzf_pose_optimization.argtypes = [vp, C.POINTER(Camera), vp, C.c_int, C.POINTER(PoseProblem), vp, vp, C.POINTER(vp), vp, C.POINTER(PoseInfo)]
+    L.ygzf_sim3_ransac.argtypes = [vp, C.c_int, C.POINTER(Sim3Problem), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.ygzf_stream.argtypes = [vp]
     L.ygzf_stream.restype = vp
     _lib = L
@@ -1206,6 +1212,29 @@ class Extractor:
         return [dict(Tcw=T32[k].copy(), Tcw64=T64[k].copy(), outlier=flags[k][:recs[k].n].copy(), ret=int(ret[k]), iterations=list(info[k].iterations),
                      trials=list(info[k].trials), stop=list(info[k].stop), lam=list(info[k].lam), chi2=list(info[k].chi2), n_initial=info[k].n_initial)
                 for k in range(B)]
+
+    def sim3_ransac(self, problems, want_bits=True):
+        """Sim3Solver's RANSAC hypotheses over a batch of solvers in one call (ygzf_sim3_ransac).  problems: dicts with X1 / X2 (n x 3: mvX3Dc1 /
+        mvX3Dc2), max_err1 / max_err2 (n floats, the truncated gates), K1 / K2 (fx fy cx cy), fix_scale and samples (n_hyp x 3).
+        -> list of dicts: hyp (n_hyp x 13: R12 row-major, t12, s12), n_inliers (n_hyp), bits (n_hyp x ceil(n / 64) uint64; None without want_bits)."""
+        B = len(problems)
+        recs = (Sim3Problem * max(B, 1))()
+        keep, out = [], []
+        for k, q in enumerate(problems):
+            X1, X2 = (np.ascontiguousarray(q[key], np.float32).reshape(-1, 3) for key in ("X1", "X2"))
+            e1, e2 = (np.ascontiguousarray(q[key], np.float32).reshape(-1) for key in ("max_err1", "max_err2"))
+            smp = np.ascontiguousarray(q["samples"], np.int32).reshape(-1, 3)
+            n, nh = len(X1), len(smp)
+            assert len(X2) == n and len(e1) == n and len(e2) == n
+            keep += [X1, X2, e1, e2, smp]
+            recs[k] = Sim3Problem(n, _p(X1), _p(X2), _p(e1), _p(e2), (C.c_float * 4)(*q["K1"]), (C.c_float * 4)(*q["K2"]), int(bool(q.get("fix_scale"))), nh, _p(smp))
+            out.append(dict(hyp=np.zeros((nh, 13), np.float32), n_inliers=np.zeros(nh, np.int32),
+                            bits=np.zeros((nh, (n + 63) // 64), np.uint64) if want_bits else None))
+        hp = (C.c_void_p * max(B, 1))(*[o["hyp"].ctypes.data for o in out])
+        cp = (C.c_void_p * max(B, 1))(*[o["n_inliers"].ctypes.data for o in out])
+        bp = (C.c_void_p * max(B, 1))(*[o["bits"].ctypes.data for o in out]) if want_bits else None
+        self._ck(self.L.ygzf_sim3_ransac(self.h, B, recs, hp, cp, bp))
+        return out
 
     def sia_run_cached(self, cam, ref_slot, cur_slot, ref_keys, ref_world, ref_Tcw7, cur_Tcw7, inv_scale, max_level, min_level, n_iter=10,
                        mp_valid=None, outlier=None):

@@ -512,5 +512,23 @@ struct PoseArgs {
 };
 void launch_pose_opt(hipStream_t st, const PoseArgs &A, int nProblems);
 
+// ---- Sim3Solver's RANSAC hypotheses (sim3_kernels.hip): one wave per hypothesis, four waves per workgroup, all problems in one launch ----
+struct Sim3ProblemDev {             // one solver with at least one hypothesis to evaluate; device pointers
+    const float *X1, *X2;           // mvX3Dc1 / mvX3Dc2, n x 3
+    const float *maxErr1, *maxErr2; // mvnMaxError1 / 2 as floats, n
+    const int *samples;             // nHyp x 3 indices into [0, n), distinct within a triple (checked by the host)
+    float *hyp;                     // nHyp x 13: R12 row-major, t12, s12
+    int *nInliers;                  // nHyp
+    unsigned long long *bits;       // nHyp x ceil(n / 64) words, bit i of word j = correspondence 64 j + i; null: not wanted
+    int n, nHyp, fixScale;
+    int firstHyp;                   // the problem's first wave in the launch (ascending over the table)
+    float K1[4], K2[4];             // fx fy cx cy
+};
+struct Sim3Args {
+    const Sim3ProblemDev *probs;
+    int nProblems, totalHyp;
+};
+void launch_sim3_ransac(hipStream_t st, const Sim3Args &A);
+
 }  // namespace ygzf
 #endif
