@@ -907,6 +907,45 @@ typedef struct ygzf_sim3_problem {
 int ygzf_sim3_ransac(ygzf_ctx *ctx, int n_problems, const ygzf_sim3_problem *problems, float *const *hyp, int *const *n_inliers,
                      uint64_t *const *inlier_bits);
 
+/* ---- Optimizer::OptimizeSim3   src/Optimizer.cc:2409-2594 --------------------------------------------------------------------------------
+ * Step 4 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:218-330), between SearchBySim3 and SearchByProjection: one free VertexSim3Expmap
+ * (fixed scale or not), per kept correspondence an EdgeSim3ProjectXYZ (P3D2c through the estimate and K1 against kpUn1.pt) and an
+ * EdgeInverseSim3ProjectXYZ (P3D1c through its inverse and K2 against kpUn2.pt), Huber kernels of delta float(sqrt(th2)), optimize(5), the
+ * gate `e12->chi2() > th2 || e21->chi2() > th2` on the errors of the last Levenberg trial, optimize(nBad > 0 ? 10 : 5), the gate again --
+ * g2o's arithmetic in fp64 with the NUMERIC Jacobian this fork runs (central differences of 1e-9 through a projection that is rounded to
+ * float: a dither), stated once in csrc/sim3_opt_math.h and restated in tests/sim3_opt_cases.py.  PnPsolver stays the reference's.
+ *
+ * n_problems loop candidates per call, each independent of the others: one upload, one launch (a workgroup per problem), one download, one
+ * synchronisation.  The caller does the host part of :2421-2536 (host/OptimizerSim3.h): the filter, GetIndexInKeyFrame and the float
+ * R * P + t.  Per problem k:
+ *   S12_out[8 k ..]  the optimised g2oS12 (r.x r.y r.z r.w, t, s);
+ *   removed[k]       n bytes: 0 the pair is an inlier, 1 removed after round 0, 2 failed the final test (vpMatches1[idx] = NULL for 1 and 2);
+ *   ret[k]           nIn;
+ *   info[k]          (may be NULL) per round: iterations run, Levenberg trials, why the round ended (ygzf_pose_stop), lambda and the active
+ *                    robust chi2 at its end; n and nBad.
+ * n == 0: nothing runs, ret = 0 and S12_out = S12.  nCorrespondences - nBad < 10 after round 0: ret = 0, S12_out equals S12 bit for bit (the
+ * reference returns before it writes g2oS12) and removed still reports the round-0 removals.  Any n >= 0 is accepted: the transfer block and
+ * the per-edge scratch are grow-on-demand buffers of the context.  Non-finite inputs are legal: they end through the bounded loops, whatever
+ * the neighbours in the batch do.
+ * YGZF_ERR_INVALID: a NULL argument or array, n_problems <= 0, n < 0. */
+typedef struct ygzf_sim3_opt_problem {
+    int n;                      /* kept correspondences, compact */
+    const float *P1c, *P2c;     /* n x 3: P3D1c, P3D2c as the float cv::Mat held them */
+    const float *obs1, *obs2;   /* n x 2: kpUn1.pt, kpUn2.pt */
+    const float *inv_sigma2_1, *inv_sigma2_2;   /* n each: mvInvLevelSigma2[octave] of KF1 / KF2 */
+    float K1[4], K2[4];         /* fx fy cx cy */
+    double S12[8];              /* r.x r.y r.z r.w, t, s */
+    float th2;
+    int fix_scale;
+} ygzf_sim3_opt_problem;
+typedef struct ygzf_sim3_opt_info {
+    int iterations[2], trials[2], stop[2];   /* stop: ygzf_pose_stop; NOT_RUN for round 1 after the early return and for both where n == 0 */
+    double lambda[2], chi2[2];
+    int n, n_bad;               /* nCorrespondences, nBad */
+} ygzf_sim3_opt_info;
+int ygzf_optimize_sim3(ygzf_ctx *ctx, int n_problems, const ygzf_sim3_opt_problem *problems, double *S12_out, uint8_t *const *removed, int *ret,
+                       ygzf_sim3_opt_info *info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -92,6 +92,16 @@ class Sim3Problem(C.Structure):   # ygzf_sim3_problem
                 ("K2", C.c_float * 4), ("fix_scale", C.c_int), ("n_hyp", C.c_int), ("samples", C.c_void_p)]
 
 
+class Sim3OptProblem(C.Structure):   # ygzf_sim3_opt_problem
+    _fields_ = [("n", C.c_int), ("P1c", C.c_void_p), ("P2c", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p),
+                ("inv_sigma2_2", C.c_void_p), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("S12", C.c_double * 8), ("th2", C.c_float), ("fix_scale", C.c_int)]
+
+
+class Sim3OptInfo(C.Structure):   # ygzf_sim3_opt_info
+    _fields_ = [("iterations", C.c_int * 2), ("trials", C.c_int * 2), ("stop", C.c_int * 2), ("lam", C.c_double * 2), ("chi2", C.c_double * 2),
+                ("n", C.c_int), ("n_bad", C.c_int)]
+
+
 class PoseInfo(C.Structure):      # ygzf_pose_info
     _fields_ = [("iterations", C.c_int * 4), ("trials", C.c_int * 4), ("stop", C.c_int * 4), ("lam", C.c_double * 4), ("chi2", C.c_double * 4),
                 ("n_initial", C.c_int)]
@@ -275,6 +285,7 @@ def load_library(build_if_missing=True):
     L.ygzf_compute_pyramid_remapped.argtypes = [vp, C.c_int, vp, C.c_int, C.POINTER(vp)]
     L.ygzf_pose_optimization.argtypes = [vp, C.POINTER(Camera), vp, C.c_int, C.POINTER(PoseProblem), vp, vp, C.POINTER(vp), vp, C.POINTER(PoseInfo)]
     L.ygzf_sim3_ransac.argtypes = [vp, C.c_int, C.POINTER(Sim3Problem), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.ygzf_optimize_sim3.argtypes = [vp, C.c_int, C.POINTER(Sim3OptProblem), vp, C.POINTER(vp), vp, C.POINTER(Sim3OptInfo)]
     L.ygzf_stream.argtypes = [vp]
     L.ygzf_stream.restype = vp
     _lib = L
@@ -1235,6 +1246,32 @@ class Extractor:
         bp = (C.c_void_p * max(B, 1))(*[o["bits"].ctypes.data for o in out]) if want_bits else None
         self._ck(self.L.ygzf_sim3_ransac(self.h, B, recs, hp, cp, bp))
         return out
+
+    def optimize_sim3(self, problems):
+        """Optimizer::OptimizeSim3 over a batch of loop candidates in one call (ygzf_optimize_sim3).  problems: dicts with P1c / P2c (n x 3),
+        obs1 / obs2 (n x 2), inv_sigma2_1 / inv_sigma2_2 (n), K1 / K2 (fx fy cx cy), S12 (8 doubles: r.x r.y r.z r.w, t, s), th2 and fix_scale.
+        -> list of dicts: S12 (float64[8]), removed (uint8[n]), ret, n_bad, iterations / trials / stop / lam / chi2 (per round)."""
+        B = len(problems)
+        recs = (Sim3OptProblem * max(B, 1))()
+        keep, flags = [], []
+        for k, q in enumerate(problems):
+            P1, P2 = (np.ascontiguousarray(q[key], np.float32).reshape(-1, 3) for key in ("P1c", "P2c"))
+            o1, o2 = (np.ascontiguousarray(q[key], np.float32).reshape(-1, 2) for key in ("obs1", "obs2"))
+            s1, s2 = (np.ascontiguousarray(q[key], np.float32).reshape(-1) for key in ("inv_sigma2_1", "inv_sigma2_2"))
+            n = len(P1)
+            assert len(P2) == n and len(o1) == n and len(o2) == n and len(s1) == n and len(s2) == n
+            keep += [P1, P2, o1, o2, s1, s2]
+            flags.append(np.full(max(n, 1), 255, np.uint8))
+            recs[k] = Sim3OptProblem(n, _p(P1), _p(P2), _p(o1), _p(o2), _p(s1), _p(s2), (C.c_float * 4)(*q["K1"]), (C.c_float * 4)(*q["K2"]),
+                                     (C.c_double * 8)(*np.asarray(q["S12"], np.float64)), float(q["th2"]), int(bool(q.get("fix_scale"))))
+        S = np.zeros((max(B, 1), 8), np.float64)
+        ret = np.zeros(max(B, 1), np.int32)
+        info = (Sim3OptInfo * max(B, 1))()
+        fl = (C.c_void_p * max(B, 1))(*[f.ctypes.data for f in flags])
+        self._ck(self.L.ygzf_optimize_sim3(self.h, B, recs, _p(S), fl, _p(ret), info))
+        return [dict(S12=S[k].copy(), removed=flags[k][:recs[k].n].copy(), ret=int(ret[k]), n_bad=info[k].n_bad, n=info[k].n,
+                     iterations=list(info[k].iterations), trials=list(info[k].trials), stop=list(info[k].stop), lam=list(info[k].lam),
+                     chi2=list(info[k].chi2)) for k in range(B)]
 
     def sia_run_cached(self, cam, ref_slot, cur_slot, ref_keys, ref_world, ref_Tcw7, cur_Tcw7, inv_scale, max_level, min_level, n_iter=10,
                        mp_valid=None, outlier=None):

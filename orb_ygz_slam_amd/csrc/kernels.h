@@ -530,5 +530,29 @@ struct Sim3Args {
 };
 void launch_sim3_ransac(hipStream_t st, const Sim3Args &A);
 
+// ---- Optimizer::OptimizeSim3 (sim3_opt_kernels.hip): one workgroup of 256 threads per problem, both rounds in one launch ----
+struct Sim3OptProblemDev {          // one loop candidate; device pointers
+    const float *P1c, *P2c;         // n x 3
+    const float *obs1, *obs2;       // n x 2
+    const float *invSigma2_1, *invSigma2_2;   // n
+    uint8_t *removed;               // n bytes out: 0 kept, 1 removed after round 0, 2 failed the final test; the pairs' state between the rounds
+    double *stored;                 // 2 n doubles of scratch: chi2 of e12 / e21's last computeError
+    int n, fixScale;
+    double K1[4], K2[4];            // fx fy cx cy, widened from float
+    double S12[8];                  // r.x r.y r.z r.w, t, s
+    double th2, delta;              // double(th2), double(float(sqrt(th2)))
+};
+struct Sim3OptOut {                 // per problem
+    double S[8];                    // the estimate; S12 itself where the function returns before writing g2oS12
+    double lambda[2], chi2[2];
+    int iters[2], trials[2], stop[2];   // stop: the values of PoseStop
+    int ret, nBad;
+};
+struct Sim3OptArgs {
+    const Sim3OptProblemDev *probs;
+    Sim3OptOut *out;
+};
+void launch_sim3_opt(hipStream_t st, const Sim3OptArgs &A, int nProblems);
+
 }  // namespace ygzf
 #endif
