@@ -1,4 +1,4 @@
-// Sim3OptHost.h -- Optimizer::OptimizeSim3 on one host thread over csrc/sim3_opt_math.h, the arithmetic k_sim3_opt compiles, with the sums in
+// Sim3OptHost.h -- Optimizer::OptimizeSim3 on one host thread over csrc/sim3_opt_math.h and csrc/lm_math.h, the arithmetic k_sim3_opt compiles, with the sums in
 // the reference's order (e12 then e21 of a correspondence, correspondences ascending): mode "reference" of tests/sim3_opt_cases.py bit for
 // bit (tests/test_sim3_opt_host_progs.py, under -fsanitize=address,undefined).  Product code, host side, nothing of HIP, Eigen or OpenCV:
 // ygz::OptimizeSim3Core runs it for calls too small to repay a launch (OptimizerSim3.cc: ygzf_host_sim3_opt_device_min), and
@@ -18,10 +18,11 @@ namespace sim3opt {
 // what ygzf_optimize_sim3 returns for one problem: S12_out[8], removed[n], ret, info (may be NULL)
 inline void optimize_host(const ygzf_sim3_opt_problem &c, double *S12_out, uint8_t *removed, int *ret, ygzf_sim3_opt_info *info) {
     namespace M = ygzf::sim3opt;
+    namespace lm = ygzf::lm;
     const size_t n = (size_t) c.n;
     ygzf_sim3_opt_info r;
     std::memset(&r, 0, sizeof r);
-    r.stop[0] = r.stop[1] = M::kStopNotRun;
+    r.stop[0] = r.stop[1] = lm::kStopNotRun;
     r.n = c.n;
     std::memcpy(S12_out, c.S12, 8 * sizeof(double));
     for (size_t i = 0; i < n; i++) removed[i] = 0;
@@ -38,15 +39,14 @@ inline void optimize_host(const ygzf_sim3_opt_problem &c, double *S12_out, uint8
     std::memcpy(est.t, c.S12 + 4, 3 * sizeof(double));
     est.s = c.S12[7];
     std::vector<double> chi12(n, 0.0), chi21(n, 0.0);
-    M::Lm L;
+    lm::Lm<M::kDim, false> L;
     std::memset(&L, 0, sizeof L);
-    L.lambda = -1.0;
-    L.ni = 2;
+    lm::init(L);
     auto X = [](const float *v, size_t i, double o[3]) { o[0] = (double) v[3 * i]; o[1] = (double) v[3 * i + 1]; o[2] = (double) v[3 * i + 2]; };
     auto O = [](const float *v, size_t i, double o[2]) { o[0] = (double) v[2 * i]; o[1] = (double) v[2 * i + 1]; };
     for (int rnd = 0; rnd < 2; rnd++) {
         const int maxIt = rnd == 0 ? 5 : (r.n_bad > 0 ? 10 : 5);
-        int reason = M::kStopMaxIter;
+        int reason = lm::kStopMaxIter;
         for (int it = 0; it < maxIt; it++) {
             M::S3 Tf[M::kTransforms], Ti[M::kTransforms];
             for (int j = 0; j < M::kTransforms; j++) M::so_transform(est, j, fix, Tf[j], Ti[j]);
@@ -59,9 +59,11 @@ inline void optimize_host(const ygzf_sim3_opt_problem &c, double *S12_out, uint8
                 chi12[i] = M::so_edge_system(Tf, p2, K1, o1, (double) c.inv_sigma2_1[i], delta, acc);
                 chi21[i] = M::so_edge_system(Ti, p1, K2, o2, (double) c.inv_sigma2_2[i], delta, acc);
             }
-            M::so_iteration_begin(L, acc, it == 0);
+            lm::iteration_begin(L, acc, acc + 28, acc[35], it == 0);
             for (int trial = 0; trial < 10; trial++) {
-                const bool ok = M::so_trial_begin(L, est, backup, fix);
+                backup = est;
+                const bool ok = lm::trial_solve(L);
+                M::so_oplus(L.x, fix, est);
                 M::S3 inv;
                 M::so_inverse(est, inv);
                 double tempChi = 0.0;
@@ -71,18 +73,21 @@ inline void optimize_host(const ygzf_sim3_opt_problem &c, double *S12_out, uint8
                     X(c.P1c, i, p1); X(c.P2c, i, p2); O(c.obs1, i, o1); O(c.obs2, i, o2);
                     M::so_error(est, p2, K1, o1, e);
                     chi12[i] = M::so_chi2(e, (double) c.inv_sigma2_1[i]);
-                    M::so_huber(chi12[i], delta, rho0, rho1);
+                    lm::huber(chi12[i], delta, rho0, rho1);
                     tempChi = tempChi + rho0;
                     M::so_error(inv, p1, K2, o2, e);
                     chi21[i] = M::so_chi2(e, (double) c.inv_sigma2_2[i]);
-                    M::so_huber(chi21[i], delta, rho0, rho1);
+                    lm::huber(chi21[i], delta, rho0, rho1);
                     tempChi = tempChi + rho0;
                 }
-                if (!M::so_trial_end(L, est, backup, ok, tempChi)) break;
+                bool restore;
+                const bool again = lm::trial_end(L, ok, tempChi, restore);
+                if (restore) est = backup;
+                if (!again) break;
             }
             r.iterations[rnd]++;
             r.trials[rnd] += L.qmax;
-            const int stop = M::so_iteration_end(L);
+            const int stop = lm::iteration_end(L);
             if (stop >= 0) { reason = stop; break; }
         }
         r.stop[rnd] = reason;

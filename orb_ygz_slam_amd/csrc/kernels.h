@@ -499,10 +499,9 @@ struct PoseProblemDev {             // one frame; device pointers
 struct PoseOut {                    // per problem
     double T[7];                    // the last round's estimate (not written when ret == 0 for want of correspondences)
     double lambda[4], chi2[4];
-    int iters[4], trials[4], stop[4];
+    int iters[4], trials[4], stop[4];   // stop: the values of lm::Stop (lm_math.h)
     int ret, nInitial;
 };
-enum PoseStop { kPoseMaxIter = 0, kPoseTrials = 1, kPoseRhoZero = 2, kPoseNBad = 3, kPoseNotRun = 4 };
 struct PoseArgs {
     const PoseProblemDev *probs;
     PoseOut *out;
@@ -545,7 +544,7 @@ struct Sim3OptProblemDev {          // one loop candidate; device pointers
 struct Sim3OptOut {                 // per problem
     double S[8];                    // the estimate; S12 itself where the function returns before writing g2oS12
     double lambda[2], chi2[2];
-    int iters[2], trials[2], stop[2];   // stop: the values of PoseStop
+    int iters[2], trials[2], stop[2];   // stop: the values of lm::Stop
     int ret, nBad;
 };
 struct Sim3OptArgs {

@@ -1,6 +1,7 @@
 // pose_kernels.hip -- Optimizer::PoseOptimization(Frame *) (src/Optimizer.cc:1656-1842): the single-vertex, motion-only problem with exactly the
-// g2o and Sophus arithmetic it runs (Levenberg: optimization_algorithm_levenberg.cpp:61-189; unary edges with a Huber kernel, weight rho[1] only;
-// the dense pivoted LDLT; the two ...OnlyPose edges of types_six_dof_expmap; SE3d::exp and `*`), in fp64.  Product code.
+// g2o and Sophus arithmetic it runs, in fp64.  Here: the two ...OnlyPose edges of types_six_dof_expmap with their analytic Jacobian (unary
+// edges with a Huber kernel, weight rho[1] only), SE3d::exp and `*`, and the plan of the rounds.  g2o's Levenberg over the dense 6 x 6 system,
+// its pivoted LDLT, Huber's robustify and the quaternion products are csrc/lm_math.h, shared with k_sim3_opt.  Product code.
 //
 // k_pose_opt: one workgroup of 256 threads per problem, all four rounds x <= 10 iterations x <= 10 trials in one launch.  Every loop is bounded by
 // those constants and leaves through them whatever the numbers are (NaN and Inf included); there is no spin wait and no communication between
@@ -14,6 +15,7 @@
 // :1795-1802), and the chi2 of its _error member as of the last computeError lives in `stored` -- computeActiveErrors leaves the errors of the
 // last *trial* there, accepted or not, and that is what the classification at the end of a round reads for level-0 edges (:1793).
 #include "kernels.h"
+#include "lm_math.h"
 #include "wave_ops.h"
 
 namespace ygzf {
@@ -23,41 +25,16 @@ namespace {
 constexpr int kPoseThreads = 256;
 constexpr int kPoseSums = 28;   // 21 + 6 + 1
 
-struct PoseLm {                 // the one lane's solver state (LDS: indexed dynamically)
-    double H[36], Hd[36], b[6], x[6], temp[6];
-    double lambda, ni, currentChi, iniChi, rho;
-    int tr[6];
-    int nBadRule, qmax;
-};
-
 struct PoseShared {
     double pose[7];             // the vertex estimate: q (x y z w), t
     double backup[7];
     double T0[7];               // pFrame->mTcw.cast<double>()
     double red[4][kPoseSums];
     double sum[kPoseSums];
-    PoseLm lm;
+    lm::Lm<6, true> lm;               // the one lane's solver state (LDS: indexed dynamically)
     int nInitial, nBad, ctl;
 };
 
-__device__ __forceinline__ void d_quat_normalize(double q[4]) {
-    const double n = sqrt(q[0] * q[0] + q[1] * q[1] + q[2] * q[2] + q[3] * q[3]);
-    q[0] = q[0] / n; q[1] = q[1] / n; q[2] = q[2] / n; q[3] = q[3] / n;
-}
-__device__ __forceinline__ void d_quat_rotate(const double q[4], const double v[3], double o[3]) {   // Eigen _transformVector
-    double uv[3] = {q[1] * v[2] - q[2] * v[1], q[2] * v[0] - q[0] * v[2], q[0] * v[1] - q[1] * v[0]};
-    uv[0] = uv[0] + uv[0]; uv[1] = uv[1] + uv[1]; uv[2] = uv[2] + uv[2];
-    const double c[3] = {q[1] * uv[2] - q[2] * uv[1], q[2] * uv[0] - q[0] * uv[2], q[0] * uv[1] - q[1] * uv[0]};
-    o[0] = v[0] + q[3] * uv[0] + c[0];
-    o[1] = v[1] + q[3] * uv[1] + c[1];
-    o[2] = v[2] + q[3] * uv[2] + c[2];
-}
-__device__ __forceinline__ void d_quat_mul(const double a[4], const double b[4], double o[4]) {
-    o[0] = a[3] * b[0] + a[0] * b[3] + a[1] * b[2] - a[2] * b[1];
-    o[1] = a[3] * b[1] + a[1] * b[3] + a[2] * b[0] - a[0] * b[2];
-    o[2] = a[3] * b[2] + a[2] * b[3] + a[0] * b[1] - a[1] * b[0];
-    o[3] = a[3] * b[3] - a[0] * b[0] - a[1] * b[1] - a[2] * b[2];
-}
 __device__ __forceinline__ void d_quat_to_R(const double q[4], double R[9]) {
     const double tx = 2 * q[0], ty = 2 * q[1], tz = 2 * q[2];
     const double twx = tx * q[3], twy = ty * q[3], twz = tz * q[3];
@@ -84,7 +61,7 @@ __device__ void d_se3_exp(const double a[6], double q[4], double t[3]) {
         real_factor = cos(half_theta);
     }
     q[0] = imag_factor * om[0]; q[1] = imag_factor * om[1]; q[2] = imag_factor * om[2]; q[3] = real_factor;
-    d_quat_normalize(q);
+    lm::quat_normalize(q);
     const double O[9] = {0, -om[2], om[1], om[2], 0, -om[0], -om[1], om[0], 0};
     double V[9];
     if (small) {
@@ -113,7 +90,7 @@ __device__ __forceinline__ void pose_edge(const PoseArgs &A, const PoseProblemDe
     E.stereo = !(ur < 0);
     const double X[3] = {(double) P.world[3 * (size_t) i], (double) P.world[3 * (size_t) i + 1], (double) P.world[3 * (size_t) i + 2]};
     double r[3];
-    d_quat_rotate(q, X, r);
+    lm::quat_rotate(q, X, r);
     E.p[0] = r[0] + t[0]; E.p[1] = r[1] + t[1]; E.p[2] = r[2] + t[2];
     E.s = (double) A.invSigma2[kp.octave];
     const double ox = (double) kp.x, oy = (double) kp.y;
@@ -131,16 +108,10 @@ __device__ __forceinline__ void pose_edge(const PoseArgs &A, const PoseProblemDe
         E.chi2 = E.e[0] * (E.s * E.e[0]) + E.e[1] * (E.s * E.e[1]);
     }
 }
-// RobustKernelHuber::robustify: rho[0], rho[1]
-__device__ __forceinline__ void pose_huber(double chi2, double delta, bool kernel, double &rho0, double &rho1) {
-    if (!kernel) { rho0 = chi2; rho1 = 1.0; return; }
-    const double dsqr = delta * delta;
-    if (chi2 <= dsqr) { rho0 = chi2; rho1 = 1.0; }
-    else {
-        const double sq = sqrt(chi2);
-        rho0 = 2 * sq * delta - dsqr;
-        rho1 = delta / sq;
-    }
+// robustify with the edge's kernel; setRobustKernel(0) in round 3: rho = (chi2, 1)
+__device__ __forceinline__ void pose_robustify(double chi2, double delta, bool kernel, double &rho0, double &rho1) {
+    if (kernel) lm::huber(chi2, delta, rho0, rho1);
+    else { rho0 = chi2; rho1 = 1.0; }
 }
 
 // One pass over the problem's active edges at S.pose: computeActiveErrors, and either the whole system (linearizeOplus + constructQuadraticForm +
@@ -161,7 +132,7 @@ __device__ void pose_pass(const PoseArgs &A, const PoseProblemDev &P, PoseShared
         pose_edge(A, P, i, q, t, E);
         P.stored[i] = E.chi2;
         double rho0, rho1;
-        pose_huber(E.chi2, E.stereo ? A.deltaStereo : A.deltaMono, kernel, rho0, rho1);
+        pose_robustify(E.chi2, E.stereo ? A.deltaStereo : A.deltaMono, kernel, rho0, rho1);
         if (!kSystem) {
             acc[0] = acc[0] + rho0;
             continue;
@@ -207,105 +178,19 @@ __device__ void pose_pass(const PoseArgs &A, const PoseProblemDev &P, PoseShared
         }
         acc[27] = acc[27] + rho0;
     }
-    const int wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < kN; k++) {
-        const double v = wave_sum_f64(acc[k]);
-        if (lane == 0) S.red[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid == 0)
-        for (int k = 0; k < kN; k++) S.sum[k] = ((S.red[0][k] + S.red[1][k]) + S.red[2][k]) + S.red[3][k];
+    block_sum_f64(acc, S.red, S.sum);
 }
 
-// Eigen's unblocked lower pivoted LDLT of L.Hd in place; true: every pivot > 0
-__device__ bool pose_ldlt(PoseLm &L) {
-    double *m = L.Hd;
-    for (int k = 0; k < 6; k++) {
-        double big = -1.0;
-        int idx = k;
-        for (int j = k; j < 6; j++) {
-            const double v = fabs(m[7 * j]);
-            if (v > big) { big = v; idx = j; }
-        }
-        L.tr[k] = idx;
-        if (idx != k) {
-            for (int j = 0; j < k; j++) { const double a = m[6 * k + j]; m[6 * k + j] = m[6 * idx + j]; m[6 * idx + j] = a; }
-            for (int i = idx + 1; i < 6; i++) { const double a = m[6 * i + k]; m[6 * i + k] = m[6 * i + idx]; m[6 * i + idx] = a; }
-            { const double a = m[7 * k]; m[7 * k] = m[7 * idx]; m[7 * idx] = a; }
-            for (int i = k + 1; i < idx; i++) { const double a = m[6 * i + k]; m[6 * i + k] = m[6 * idx + i]; m[6 * idx + i] = a; }
-        }
-        if (k > 0) {
-            for (int j = 0; j < k; j++) L.temp[j] = m[7 * j] * m[6 * k + j];
-            double s = m[6 * k] * L.temp[0];
-            for (int j = 1; j < k; j++) s = s + m[6 * k + j] * L.temp[j];
-            m[7 * k] = m[7 * k] - s;
-            for (int i = k + 1; i < 6; i++) {
-                double s2 = m[6 * i] * L.temp[0];
-                for (int j = 1; j < k; j++) s2 = s2 + m[6 * i + j] * L.temp[j];
-                m[6 * i + k] = m[6 * i + k] - s2;
-            }
-        }
-        for (int i = k + 1; i < 6; i++) m[6 * i + k] = m[6 * i + k] / m[7 * k];
-    }
-    bool positive = true;
-    for (int k = 0; k < 6; k++) positive = positive && (m[7 * k] > 0);
-    return positive;
-}
-__device__ void pose_ldlt_solve(PoseLm &L) {   // x = P^T L^-T D^-1 L^-1 P b
-    const double *m = L.Hd;
-    double *x = L.x;
-    for (int k = 0; k < 6; k++) x[k] = L.b[k];
-    for (int k = 0; k < 6; k++) { const double a = x[k]; x[k] = x[L.tr[k]]; x[L.tr[k]] = a; }
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < i; j++) x[i] = x[i] - m[6 * i + j] * x[j];
-    for (int i = 0; i < 6; i++) x[i] = x[i] / m[7 * i];
-    for (int i = 5; i >= 0; i--)
-        for (int j = i + 1; j < 6; j++) x[i] = x[i] - m[6 * j + i] * x[j];
-    for (int k = 5; k >= 0; k--) { const double a = x[k]; x[k] = x[L.tr[k]]; x[L.tr[k]] = a; }
-}
-
-// the head of a Levenberg trial (:103-115): push, setLambda, solve, update.  A failed solve leaves x as it was, and update() applies it all the same.
-__device__ bool pose_trial_begin(PoseShared &S) {
-    PoseLm &L = S.lm;
-    for (int k = 0; k < 7; k++) S.backup[k] = S.pose[k];
-    for (int k = 0; k < 36; k++) L.Hd[k] = L.H[k];
-    for (int j = 0; j < 6; j++) L.Hd[7 * j] = L.H[7 * j] + L.lambda;
-    const bool ok = pose_ldlt(L);
-    if (ok) pose_ldlt_solve(L);
-    const double u[6] = {L.x[3], L.x[4], L.x[5], L.x[0], L.x[1], L.x[2]};   // VertexSE3Expmap::oplusImpl
+// the update of a trial, VertexSE3Expmap::oplusImpl: estimate = SE3d::exp(x[3..5], x[0..2]) * estimate
+__device__ void pose_oplus(const double x[6], double pose[7]) {
+    const double u[6] = {x[3], x[4], x[5], x[0], x[1], x[2]};
     double qe[4], te[3], q[4], r[3];
     d_se3_exp(u, qe, te);
-    d_quat_rotate(qe, S.pose + 4, r);            // SE3d::operator*: fastMultiply + normalize
-    d_quat_mul(qe, S.pose, q);
-    d_quat_normalize(q);
-    for (int k = 0; k < 4; k++) S.pose[k] = q[k];
-    for (int k = 0; k < 3; k++) S.pose[4 + k] = te[k] + r[k];
-    return ok;
-}
-// the tail of the trial (:123-149); true: another trial follows
-__device__ bool pose_trial_end(PoseShared &S, bool ok, double tempChi) {
-    PoseLm &L = S.lm;
-    if (!ok) tempChi = 1.7976931348623157e308;
-    double scale = 0.0;
-    for (int j = 0; j < 6; j++) scale = scale + L.x[j] * (L.lambda * L.x[j] + L.b[j]);
-    scale = scale + 1e-3;
-    L.rho = (L.currentChi - tempChi) / scale;
-    if (L.rho > 0 && isfinite(tempChi)) {
-        const double c = 2 * L.rho - 1;
-        double alpha = 1.0 - c * c * c;
-        alpha = (2.0 / 3.0 < alpha) ? 2.0 / 3.0 : alpha;
-        const double scaleFactor = (1.0 / 3.0 < alpha) ? alpha : 1.0 / 3.0;
-        L.lambda = L.lambda * scaleFactor;
-        L.ni = 2;
-        L.currentChi = tempChi;
-    } else {
-        L.lambda = L.lambda * L.ni;
-        L.ni = L.ni * 2;
-        for (int k = 0; k < 7; k++) S.pose[k] = S.backup[k];
-    }
-    L.qmax++;
-    return L.rho < 0 && L.qmax < 10;
+    lm::quat_rotate(qe, pose + 4, r);            // SE3d::operator*: fastMultiply + normalize
+    lm::quat_mul(qe, pose, q);
+    lm::quat_normalize(q);
+    for (int k = 0; k < 4; k++) pose[k] = q[k];
+    for (int k = 0; k < 3; k++) pose[4 + k] = te[k] + r[k];
 }
 
 __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(PoseArgs A) {
@@ -325,14 +210,12 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(PoseArgs A) {
     const int nInitial = S.nInitial;
     if (tid == 0) {
         out.nInitial = nInitial;
-        for (int r = 0; r < 4; r++) { out.iters[r] = 0; out.trials[r] = 0; out.stop[r] = kPoseNotRun; out.lambda[r] = 0; out.chi2[r] = 0; }
+        for (int r = 0; r < 4; r++) { out.iters[r] = 0; out.trials[r] = 0; out.stop[r] = lm::kStopNotRun; out.lambda[r] = 0; out.chi2[r] = 0; }
         double q[4] = {(double) P.Tcw[0], (double) P.Tcw[1], (double) P.Tcw[2], (double) P.Tcw[3]};
-        d_quat_normalize(q);                      // SE3f::cast<double>()
+        lm::quat_normalize(q);                      // SE3f::cast<double>()
         for (int k = 0; k < 4; k++) S.T0[k] = q[k];
         for (int k = 0; k < 3; k++) S.T0[4 + k] = (double) P.Tcw[4 + k];
-        for (int k = 0; k < 6; k++) S.lm.x[k] = 0.0;
-        S.lm.lambda = -1.0;
-        S.lm.ni = 2;
+        lm::init(S.lm);
     }
     if (nInitial < 3) {                           // :1767 -- the pose stays as it is
         if (tid == 0) out.ret = 0;
@@ -344,48 +227,39 @@ __global__ __launch_bounds__(kPoseThreads) void k_pose_opt(PoseArgs A) {
         if (tid == 0)
             for (int k = 0; k < 7; k++) S.pose[k] = S.T0[k];   // :1779, every round
         __syncthreads();
-        int reason = kPoseMaxIter, iters = 0, trials = 0;      // (thread 0's)
+        int reason = lm::kStopMaxIter, iters = 0, trials = 0;      // (thread 0's)
         for (int it = 0; it < 10; it++) {
             pose_pass<true>(A, P, S, kernel);
             if (tid == 0) {
-                PoseLm &L = S.lm;
-                int c = 0;
-                for (int j = 0; j < 6; j++)
-                    for (int k = j; k < 6; k++) { L.H[6 * j + k] = S.sum[c]; L.H[6 * k + j] = S.sum[c]; c++; }
-                for (int j = 0; j < 6; j++) L.b[j] = -S.sum[21 + j];
-                L.currentChi = S.sum[27];
-                L.iniChi = L.currentChi;
-                if (it == 0) {                    // computeLambdaInit
-                    double maxDiagonal = 0.;
-                    for (int j = 0; j < 6; j++) { const double v = fabs(L.H[7 * j]); maxDiagonal = (v < maxDiagonal) ? maxDiagonal : v; }   // std::max(fabs(H_jj), maxDiagonal)
-                    L.lambda = 1e-5 * maxDiagonal;
-                    L.ni = 2;
-                    L.nBadRule = 0;
-                }
-                L.rho = 0;
-                L.qmax = 0;
+                double b[6];
+                for (int j = 0; j < 6; j++) b[j] = -S.sum[21 + j];   // b = -g
+                lm::iteration_begin(S.lm, S.sum, b, S.sum[27], it == 0);
             }
             for (int trial = 0; trial < 10; trial++) {
                 bool ok = false;
-                if (tid == 0) ok = pose_trial_begin(S);
+                if (tid == 0) {
+                    for (int k = 0; k < 7; k++) S.backup[k] = S.pose[k];
+                    ok = lm::trial_solve(S.lm);
+                    pose_oplus(S.lm.x, S.pose);
+                }
                 __syncthreads();
                 pose_pass<false>(A, P, S, kernel);
-                if (tid == 0) S.ctl = pose_trial_end(S, ok, S.sum[0]) ? 1 : 0;
+                if (tid == 0) {
+                    double backup[7];                 // (read before trial_end's LDS writes, not behind them)
+                    lds_read_now(S.backup, backup);
+                    bool restore;
+                    S.ctl = lm::trial_end(S.lm, ok, S.sum[0], restore) ? 1 : 0;
+                    if (restore)
+                        for (int k = 0; k < 7; k++) S.pose[k] = backup[k];
+                }
                 __syncthreads();
                 if (!S.ctl) break;
             }
             __syncthreads();                      // (S.ctl is read by all before thread 0 writes it again)
             if (tid == 0) {
-                PoseLm &L = S.lm;
                 iters++;
-                trials += L.qmax;
-                int stop = -1;
-                if (L.qmax == 10 || L.rho == 0) stop = L.qmax == 10 ? kPoseTrials : kPoseRhoZero;
-                else {
-                    if ((L.iniChi - L.currentChi) * 1e3 < L.iniChi) L.nBadRule++;
-                    else L.nBadRule = 0;
-                    if (L.nBadRule >= 3) stop = kPoseNBad;
-                }
+                trials += S.lm.qmax;
+                const int stop = lm::iteration_end(S.lm);
                 if (stop >= 0) reason = stop;
                 S.ctl = stop >= 0 ? 1 : 0;
             }

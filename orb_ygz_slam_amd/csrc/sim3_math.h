@@ -19,13 +19,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define YGZF_SIM3_HD __host__ __device__
-#define YGZF_SIM3_UNROLL _Pragma("unroll")
-#else
-#define YGZF_SIM3_HD
-#define YGZF_SIM3_UNROLL
-#endif
+#include "lm_math.h"   // for YGZF_HD and YGZF_UNROLL, the one set of these macros; nothing else of it is used here
 
 // The most sweeps of the Jacobi eigen-solver, for the kernel and the restatement alike (tests/sim3_cases.py reads this line).  A sweep is
 // the six rotations (0,1) (0,2) (0,3) (1,2) (1,3) (2,3); the solver stops before a sweep only when all six off-diagonal entries are exactly zero.
@@ -43,14 +37,14 @@ struct Hyp {
 };
 
 // symmetric 4 x 4, eigenvectors in the columns of V
-YGZF_SIM3_HD inline void jacobi4(float A[4][4], float V[4][4]) {
+YGZF_HD inline void jacobi4(float A[4][4], float V[4][4]) {
     for (int r = 0; r < 4; r++)
         for (int c = 0; c < 4; c++) V[r][c] = r == c ? 1.f : 0.f;
     for (int sweep = 0; sweep < YGZF_SIM3_JACOBI_SWEEPS; sweep++) {
         if (A[0][1] == 0.f && A[0][2] == 0.f && A[0][3] == 0.f && A[1][2] == 0.f && A[1][3] == 0.f && A[2][3] == 0.f) break;
-YGZF_SIM3_UNROLL
+YGZF_UNROLL
         for (int p = 0; p < 3; p++) {
-YGZF_SIM3_UNROLL
+YGZF_UNROLL
             for (int q = p + 1; q < 4; q++) {
                 const float apq = A[p][q];
                 if (apq == 0.f) continue;
@@ -64,7 +58,7 @@ YGZF_SIM3_UNROLL
                 A[q][q] = A[q][q] + h;
                 A[p][q] = 0.f;
                 A[q][p] = 0.f;
-YGZF_SIM3_UNROLL
+YGZF_UNROLL
                 for (int r = 0; r < 4; r++) {
                     if (r != p && r != q) {
                         const float arp = A[r][p], arq = A[r][q];
@@ -82,7 +76,7 @@ YGZF_SIM3_UNROLL
 }
 
 // ComputeSim3 on the three correspondences p1[k] / p2[k] (camera-1 / camera-2 coordinates of sample k)
-YGZF_SIM3_HD inline void horn(const float p1[3][3], const float p2[3][3], bool fixScale, Hyp &H) {
+YGZF_HD inline void horn(const float p1[3][3], const float p2[3][3], bool fixScale, Hyp &H) {
     float O1[3], O2[3], Pr1[3][3], Pr2[3][3];   // Pr[k][axis]
     const double third = 1.0 / 3.0;
     for (int a = 0; a < 3; a++) {
@@ -113,7 +107,7 @@ YGZF_SIM3_HD inline void horn(const float p1[3][3], const float p2[3][3], bool f
     jacobi4(N, V);
     // the largest eigenvalue, the first of equals (a NaN never wins)
     float best = N[0][0], w = V[0][0], x = V[1][0], y = V[2][0], z = V[3][0];
-YGZF_SIM3_UNROLL
+YGZF_UNROLL
     for (int k = 1; k < 4; k++)
         if (N[k][k] > best) { best = N[k][k]; w = V[0][k]; x = V[1][k]; y = V[2][k]; z = V[3][k]; }
     if (x == 0.f && y == 0.f && z == 0.f) {
@@ -151,7 +145,7 @@ YGZF_SIM3_UNROLL
 }
 
 // FromCameraToImage: no depth gate, invz may be infinite
-YGZF_SIM3_HD inline void to_image(const float X[3], const float K[4], float uv[2]) {
+YGZF_HD inline void to_image(const float X[3], const float K[4], float uv[2]) {
     const float invz = 1.f / X[2];
     const float x = X[0] * invz, y = X[1] * invz;
     uv[0] = K[0] * x + K[2];
@@ -159,14 +153,14 @@ YGZF_SIM3_HD inline void to_image(const float X[3], const float K[4], float uv[2
 }
 
 // Project: sR X + t, then FromCameraToImage
-YGZF_SIM3_HD inline void project(const float sR[9], const float t[3], const float X[3], const float K[4], float uv[2]) {
+YGZF_HD inline void project(const float sR[9], const float t[3], const float X[3], const float K[4], float uv[2]) {
     float P[3];
     for (int r = 0; r < 3; r++) P[r] = ((sR[3 * r] * X[0] + sR[3 * r + 1] * X[1]) + sR[3 * r + 2] * X[2]) + t[r];
     to_image(P, K, uv);
 }
 
 // dist.dot(dist) of a 2-vector: double accumulation, the result cast to float
-YGZF_SIM3_HD inline float err2(const float a[2], const float b[2]) {
+YGZF_HD inline float err2(const float a[2], const float b[2]) {
     const float d0 = a[0] - b[0], d1 = a[1] - b[1];
     double s = (double) d0 * (double) d0;
     s += (double) d1 * (double) d1;
@@ -174,7 +168,7 @@ YGZF_SIM3_HD inline float err2(const float a[2], const float b[2]) {
 }
 
 // one correspondence under one hypothesis (CheckInliers, :325-336): both errors below their gates with `<`, so a NaN fails
-YGZF_SIM3_HD inline bool inlier(const Hyp &H, const float X1[3], const float X2[3], const float K1[4], const float K2[4], float max1, float max2,
+YGZF_HD inline bool inlier(const Hyp &H, const float X1[3], const float X2[3], const float K1[4], const float K2[4], float max1, float max2,
                                 float *e1 = nullptr, float *e2 = nullptr) {
     float p1im1[2], p2im2[2], p2im1[2], p1im2[2];
     to_image(X1, K1, p1im1);

@@ -1,7 +1,8 @@
 // sim3_opt_kernels.hip -- Optimizer::OptimizeSim3 (src/Optimizer.cc:2409-2594): one free VertexSim3Expmap, a pair of projection edges per
 // correspondence (e12 through K1 at the estimate, e21 through K2 at its inverse), Huber kernels, g2o's Levenberg over the dense 7 x 7 system,
-// optimize(5), the chi2 gate, optimize(nBad > 0 ? 10 : 5), the gate again.  The arithmetic is csrc/sim3_opt_math.h, compiled here and by the
-// host programs alike; this file is the plan around it.  Product code.
+// optimize(5), the chi2 gate, optimize(nBad > 0 ? 10 : 5), the gate again.  The arithmetic is csrc/sim3_opt_math.h (Sim3, the edges) and
+// csrc/lm_math.h (the Levenberg solver, shared with k_pose_opt), compiled here and by the host programs alike; this file is the plan around it.
+// Product code.
 //
 // k_sim3_opt: one workgroup of 256 threads per problem, both rounds x <= 10 iterations x <= 10 trials in one launch.  Every loop is bounded by
 // those constants and leaves through them whatever the numbers are (NaN and Inf included); there is no spin wait and no communication between
@@ -33,9 +34,11 @@ struct SoShared {
     so::S3 est, backup;
     double red[4][so::kSums];
     double sum[so::kSums];
-    so::Lm lm;                      // the one lane's solver state (LDS: indexed dynamically)
+    lm::Lm<so::kDim, false> lm;            // the one lane's solver state (LDS: indexed dynamically)
     int nBad, nIn, ctl;
 };
+
+static_assert(sizeof(so::S3) == 8 * sizeof(double), "k_sim3_opt copies an S3 as 8 doubles");
 
 struct SoPair {
     double p1[3], p2[3], o1[2], o2[2], s1, s2;
@@ -46,19 +49,6 @@ __device__ __forceinline__ void so_load(const Sim3OptProblemDev &P, int c, SoPai
     for (int k = 0; k < 2; k++) { Q.o1[k] = (double) P.obs1[2 * i + k]; Q.o2[k] = (double) P.obs2[2 * i + k]; }
     Q.s1 = (double) P.invSigma2_1[i];
     Q.s2 = (double) P.invSigma2_2[i];
-}
-
-// lanes by wave_sum_f64, the four waves in wave order; the result in S.sum, valid for thread 0 after the call
-template <int kN> __device__ __forceinline__ void so_reduce(SoShared &S, const double (&acc)[kN]) {
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-#pragma unroll
-    for (int k = 0; k < kN; k++) {
-        const double v = wave_sum_f64(acc[k]);
-        if (lane == 0) S.red[wave][k] = v;
-    }
-    __syncthreads();
-    if (tid == 0)
-        for (int k = 0; k < kN; k++) S.sum[k] = ((S.red[0][k] + S.red[1][k]) + S.red[2][k]) + S.red[3][k];
 }
 
 // computeActiveErrors + linearizeOplus + constructQuadraticForm + activeRobustChi2 over the active pairs at the 30 transforms of S.T
@@ -73,7 +63,7 @@ __device__ void so_pass_system(const Sim3OptProblemDev &P, SoShared &S, const so
         P.stored[2 * (size_t) c] = so::so_edge_system(S.T, Q.p2, K1, Q.o1, Q.s1, P.delta, acc);
         P.stored[2 * (size_t) c + 1] = so::so_edge_system(S.T + so::kTransforms, Q.p1, K2, Q.o2, Q.s2, P.delta, acc);
     }
-    so_reduce(S, acc);
+    block_sum_f64(acc, S.red, S.sum);
 }
 // computeActiveErrors + activeRobustChi2 at the trial estimate (S.T[0] and its inverse S.T[15])
 __device__ void so_pass_chi2(const Sim3OptProblemDev &P, SoShared &S, const so::Cam &K1, const so::Cam &K2) {
@@ -86,16 +76,16 @@ __device__ void so_pass_chi2(const Sim3OptProblemDev &P, SoShared &S, const so::
         double e[2], rho0, rho1;
         so::so_error(fwd, Q.p2, K1, Q.o1, e);
         const double c12 = so::so_chi2(e, Q.s1);
-        so::so_huber(c12, P.delta, rho0, rho1);
+        lm::huber(c12, P.delta, rho0, rho1);
         acc[0] = acc[0] + rho0;
         so::so_error(inv, Q.p1, K2, Q.o2, e);
         const double c21 = so::so_chi2(e, Q.s2);
-        so::so_huber(c21, P.delta, rho0, rho1);
+        lm::huber(c21, P.delta, rho0, rho1);
         acc[0] = acc[0] + rho0;
         P.stored[2 * (size_t) c] = c12;
         P.stored[2 * (size_t) c + 1] = c21;
     }
-    so_reduce(S, acc);
+    block_sum_f64(acc, S.red, S.sum);
 }
 
 __global__ __launch_bounds__(kSoThreads) void k_sim3_opt(Sim3OptArgs A) {
@@ -108,15 +98,13 @@ __global__ __launch_bounds__(kSoThreads) void k_sim3_opt(Sim3OptArgs A) {
     const so::Cam K1 = {P.K1[0], P.K1[1], P.K1[2], P.K1[3]}, K2 = {P.K2[0], P.K2[1], P.K2[2], P.K2[3]};
     if (tid == 0) {
         for (int k = 0; k < 8; k++) out.S[k] = P.S12[k];
-        for (int r = 0; r < 2; r++) { out.iters[r] = 0; out.trials[r] = 0; out.stop[r] = so::kStopNotRun; out.lambda[r] = 0; out.chi2[r] = 0; }
+        for (int r = 0; r < 2; r++) { out.iters[r] = 0; out.trials[r] = 0; out.stop[r] = lm::kStopNotRun; out.lambda[r] = 0; out.chi2[r] = 0; }
         out.ret = 0;
         out.nBad = 0;
         for (int k = 0; k < 4; k++) S.est.q[k] = P.S12[k];
         for (int k = 0; k < 3; k++) S.est.t[k] = P.S12[4 + k];
         S.est.s = P.S12[7];
-        for (int k = 0; k < so::kDim; k++) S.lm.x[k] = 0.0;
-        S.lm.lambda = -1.0;
-        S.lm.ni = 2;
+        lm::init(S.lm);
         S.nBad = 0;
         S.nIn = 0;
     }
@@ -125,23 +113,32 @@ __global__ __launch_bounds__(kSoThreads) void k_sim3_opt(Sim3OptArgs A) {
     int nBad = 0;
     for (int rnd = 0; rnd < 2; rnd++) {
         const int maxIt = rnd == 0 ? 5 : (nBad > 0 ? 10 : 5);
-        int reason = so::kStopMaxIter, iters = 0, trials = 0;   // (thread 0's)
+        int reason = lm::kStopMaxIter, iters = 0, trials = 0;   // (thread 0's)
         for (int it = 0; it < maxIt; it++) {
             __syncthreads();
             if (tid < so::kTransforms) so::so_transform(S.est, tid, fix, S.T[tid], S.T[so::kTransforms + tid]);
             __syncthreads();
             so_pass_system(P, S, K1, K2);
-            if (tid == 0) so::so_iteration_begin(S.lm, S.sum, it == 0);
+            if (tid == 0) lm::iteration_begin(S.lm, S.sum, S.sum + 28, S.sum[35], it == 0);
             for (int trial = 0; trial < 10; trial++) {
                 bool ok = false;
                 if (tid == 0) {
-                    ok = so::so_trial_begin(S.lm, S.est, S.backup, fix);
+                    S.backup = S.est;
+                    ok = lm::trial_solve(S.lm);
+                    so::so_oplus(S.lm.x, fix, S.est);
                     S.T[0] = S.est;
                     so::so_inverse(S.est, S.T[so::kTransforms]);
                 }
                 __syncthreads();
                 so_pass_chi2(P, S, K1, K2);
-                if (tid == 0) S.ctl = so::so_trial_end(S.lm, S.est, S.backup, ok, S.sum[0]) ? 1 : 0;
+                if (tid == 0) {
+                    double backup[8];                 // (read before trial_end's LDS writes, not behind them)
+                    lds_read_now(reinterpret_cast<const double *>(&S.backup), backup);
+                    bool restore;
+                    S.ctl = lm::trial_end(S.lm, ok, S.sum[0], restore) ? 1 : 0;
+                    if (restore)
+                        for (int k = 0; k < 8; k++) reinterpret_cast<double *>(&S.est)[k] = backup[k];
+                }
                 __syncthreads();
                 if (!S.ctl) break;
             }
@@ -149,7 +146,7 @@ __global__ __launch_bounds__(kSoThreads) void k_sim3_opt(Sim3OptArgs A) {
             if (tid == 0) {
                 iters++;
                 trials += S.lm.qmax;
-                const int stop = so::so_iteration_end(S.lm);
+                const int stop = lm::iteration_end(S.lm);
                 if (stop >= 0) reason = stop;
                 S.ctl = stop >= 0 ? 1 : 0;
             }

@@ -99,6 +99,29 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
         r[l] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), 16 * l), __builtin_amdgcn_readlane(__double2loint(v), 16 * l));
     return (r[0] + r[1]) + (r[2] + r[3]);
 }
+// kN fp64 sums over a workgroup of 256 threads (all of them call): lanes by wave_sum_f64, then the four waves in wave order through the LDS rows
+// `red`, ((w0 + w1) + w2) + w3, into `sum` -- valid for thread 0 after the call.  k_pose_opt's and k_sim3_opt's "device order".
+template <int kN, int kRow> __device__ __forceinline__ void block_sum_f64(const double (&acc)[kN], double (&red)[4][kRow], double (&sum)[kRow]) {
+    static_assert(kN <= kRow, "block_sum_f64: the LDS rows are too short");
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+#pragma unroll
+    for (int k = 0; k < kN; k++) {
+        const double v = wave_sum_f64(acc[k]);
+        if (lane == 0) red[wave][k] = v;
+    }
+    __syncthreads();
+    if (tid == 0)
+        for (int k = 0; k < kN; k++) sum[k] = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];
+}
+
+// kN doubles of LDS read where the call stands (volatile: the compiler neither sinks the reads to their use nor drops them).  For a value a lane
+// will need after a stretch of LDS writes: read before them the loads travel with the stretch's own; read after them they queue behind it.
+template <int kN> __device__ __forceinline__ void lds_read_now(const double *src, double (&dst)[kN]) {
+    typedef const volatile __attribute__((address_space(3))) double *lds_ptr;   // (a volatile access through a generic pointer would be a flat load)
+    const lds_ptr p = (lds_ptr) src;
+#pragma unroll
+    for (int k = 0; k < kN; k++) dst[k] = p[k];
+}
 
 // LDS hand-off inside one wave: orders this wave's LDS writes before its later LDS reads by other lanes.  Where each wave works on LDS of its
 // own no block barrier is needed -- and none is allowed where waves of a block may exit early.
