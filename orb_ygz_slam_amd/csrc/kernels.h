@@ -175,6 +175,8 @@ struct MatchArgs {
     // splitCnt[pair] gathers all lists and runs the in-order pass.  split <= 1: one workgroup per pair, nothing crosses global memory.
     int handoverFence;             // 1: __threadfence() on both sides of the hand-over as well (A/B runs: YGZF_MATCH_FENCE)
     int fixedLanes;                // 1: eight lanes per query in the multi-workgroup scan whatever its level (A/B runs: YGZF_MATCH_LANES=fixed)
+    int scanFiltered;              // 1: with one workgroup per pair the speculative scan reads a descriptor only after the window filters have passed
+                                   // (k_match_last; YGZF_FORCE=match_scan=filtered|predicated).  Several workgroups per pair always scan predicated.
     int unitWorld;                 // mode 0: the world point of Last keypoint i is ((x - cx) / fx, (y - cy) / fy, 1), not world[3 i ..]
     int serialOrder;               // 1: the one-wave in-order pass instead of the block-wide fixpoint; 2: fixpoint without list extensions, i.e. the
                                    // hand-over to the one-wave pass at the first exhausted list (tests, A/B runs: YGZF_MATCH_SERIAL)
@@ -190,6 +192,8 @@ struct MatchArgs {
 // when non-zero.
 constexpr int kMatchStatFallbacks = 0, kMatchStatRoundCap = 1, kMatchStatExtRoom = 2, kMatchStatExtended = 3, kMatchStatRescans = 4, kMatchStatWords = 5;
 constexpr int kMatchCauseRounds = 1, kMatchCauseExtRoom = 2;   // why a pair left the fixpoint (k_match_last: s_tmp[15])
+constexpr int kMatchScanFilteredDefault = 1;   // MatchArgs::scanFiltered unless YGZF_FORCE=match_scan pins it (profiles/r18_match_scan_ab.txt)
+constexpr int kMatchScanQueue = 8;             // keypoints a lane of the filtered scan holds back before the wave scores them (a register each)
 constexpr int kMatchSplitRec = 56;   // uint4 + uint4 (lists of eight) + ushort4 + ushort4 + float angle + hasObs word
 hipError_t match_prepare(size_t ldsBytes);
 void launch_backproject_unit(hipStream_t st, const ygzf_kp *keys, const int *cnt, long long kpStride, int maxKp, int nFrames, float fx,

@@ -325,12 +325,14 @@ __device__ __forceinline__ void spec_merge8_xor(unsigned (&K)[8], unsigned (&J)[
             }
 }
 
+template <bool kScanFiltered>   // the form of the speculative scan with one workgroup per pair (MatchArgs::scanFiltered)
 __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
     extern __shared__ __attribute__((aligned(16))) unsigned char dyn[];
     __shared__ int s_tmp[20];
     __shared__ int s_hist[HISTO_LENGTH];
     const int tid = threadIdx.x, lane = m_lane(), wave = tid >> 6;
     const int S = A.split > 1 ? A.split : 1;
+    const bool scanFiltered = kScanFiltered && S <= 1;
     const int pair = S > 1 ? (int) blockIdx.x / S : (int) blockIdx.x, part = (int) blockIdx.x - pair * S;
     const int nt = A.curCnt[(long long) pair * A.cntStrideCur + A.cntOffCur];
     const int nq = A.lastCnt[(long long) pair * A.cntStrideLast + A.cntOffLast];
@@ -616,9 +618,41 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
         for (int e = 0; e < 8; e++) { K[e] = 0xFFFFFFFFu; J[e] = 0; }
         if (q.valid) {
             const bool bCheckLevels = (q.minLevel > 0) || (q.maxLevel >= 0);
-            // One candidate = a chain of dependent LDS reads (list -> level / position / owner -> descriptor): the filters are evaluated as
-            // predicates, not as early exits, so that the reads behind them are issued together (three waits per candidate instead of six).
+            // One candidate = a chain of dependent LDS reads (list -> level / position / owner -> descriptor).  Two forms of the scan:
+            //
+            // predicated (eval; several workgroups per pair, S > 1, always): the filters are evaluated as predicates, not as early exits, so
+            // that the reads behind them are issued together (three waits per candidate instead of six).  A workgroup of the one-pair launch
+            // holds a handful of queries and nothing hides an LDS round trip: latency is the whole cost there (35 us per pair).
             // Measured and dropped: four candidates per step (the runs are short: wasted evaluations), whole grid columns per lane.
+            //
+            // filtered (passes / score; one workgroup per pair, MatchArgs::scanFiltered): the sixteen waves of a pair overlap each other's LDS
+            // latency, and what the scan costs is the steps a wave takes.  Four in five keypoints of a cell window are on another level or
+            // outside the box (profiles/r18_match_scan_ab.txt), and a wave of the predicated form's nested loops takes, per grid column, as many steps as
+            // its fullest lane: 80 per wave where the busiest lane visits 40 keypoints.  Here a lane's walk is explicit state (column, li,
+            // e, colBase), so every step takes every lane one keypoint further whatever column it is in, on the filters alone; a keypoint
+            // that passes goes into the lane's queue of kMatchScanQueue registers; when one lane's queue is full, or no lane has a keypoint
+            // left, the wave reads the descriptors of what is queued and inserts, all lanes together.  256 pairs: 148 -> 118 us.
+            // Measured and dropped: scoring as soon as any lane holds one keypoint (a queue of one: 129 us) and every lane stopping at its next
+            // passing keypoint until all have one (each round waits for the longest gap of 64 lanes: 263 us); queues of 2 / 4 / 16 (128 / 122 /
+            // 120 us); the next list entry read a step ahead (127 us).
+            // The two forms fill the same lists.  A key is dist << 16 | ord, ord = the keypoint's position in the reference's visiting order
+            // among ALL keypoints of the window (colBase + (li - s): rejected ones advance it), unique within a query; the filtered form
+            // offers insert() exactly the candidates to which eval() gives a finite key (same filters, same maxDist rule); and the sorted
+            // four (eight) smallest of a set of distinct keys do not depend on the order or grouping in which they are inserted.
+            auto passes = [&](int i2) -> bool {
+                bool ok = true;
+                if (bCheckLevels) {
+                    const int o = L.octave[i2];
+                    ok = !(o < q.minLevel) && !(q.maxLevel >= 0 && o > q.maxLevel);
+                }
+                const float distx = L.cx[i2] - q.u, disty = L.cy[i2] - q.v;
+                ok = ok && (fabsf(distx) < q.radius && fabsf(disty) < q.radius) && L.owner[i2] != 2;
+                if (uRight) {
+                    const float ur2 = uRight[i2];
+                    if (ur2 > 0 && fabsf(q.ur - ur2) > q.radius) ok = false;
+                }
+                return ok;
+            };
             auto eval = [&](int li, unsigned ord, unsigned &jj) -> unsigned {
                 const int i2 = L.list[li];
                 jj = (unsigned) i2;
@@ -666,6 +700,58 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                 }
             };
             unsigned colBase = 0;   // candidates of the grid columns before ix: `ord` is the position in the reference's visiting order
+            if (scanFiltered) {
+                int ix = q.minCx;   // the lane's walk: grid column ix, its list range [s, e), the next entry li (and colBase)
+                int s = L.cellStart[ix * GRID_ROWS + q.minCy], e = L.cellStart[ix * GRID_ROWS + q.maxCy + 1];
+                int li = s + qr;
+                auto score = [&](int i2, unsigned ord) {
+                    unsigned long long d0, d1, d2, d3;
+                    if (A.descInLds) {
+                        lds_desc(L.desc, i2, d0, d1, d2, d3);
+                    } else {
+                        const unsigned long long *d = (const unsigned long long *) (curDesc + (size_t) i2 * 32);
+                        d0 = d[0]; d1 = d[1]; d2 = d[2]; d3 = d[3];
+                    }
+                    const unsigned dist = hamming256(q0, q1, q2, q3, d0, d1, d2, d3);
+                    if ((A.mode == 0 || A.mode == 2) && dist > (unsigned) A.maxDist) return;
+                    insert((dist << 16) | (ord & 0xFFFFu), (unsigned) i2);
+                };
+                constexpr int kQ = kMatchScanQueue;
+                unsigned P[kQ];   // keypoints that passed, not yet scored: index | ord << 16, the latest first
+#pragma unroll
+                for (int k = 0; k < kQ; k++) P[k] = 0;
+                int n = 0;
+                bool more = true;
+                for (;;) {
+                    for (;;) {   // every lane one keypoint further, until one lane's queue is full or no lane has any left
+                        if (more) {
+                            while (li >= e && ix < q.maxCx) {
+                                colBase += (unsigned) (e - s);
+                                ix++;
+                                s = L.cellStart[ix * GRID_ROWS + q.minCy]; e = L.cellStart[ix * GRID_ROWS + q.maxCy + 1];
+                                li = s + qr;
+                            }
+                            if (li < e) {
+                                const int c = L.list[li];
+                                const unsigned o = colBase + (unsigned) (li - s);
+                                li += LPQ;
+                                if (passes(c)) {
+#pragma unroll
+                                    for (int k = kQ - 1; k > 0; k--) P[k] = P[k - 1];
+                                    P[0] = (unsigned) c | (o << 16);
+                                    n++;
+                                }
+                            } else more = false;
+                        }
+                        if (!__any(more) || __any(n >= kQ)) break;
+                    }
+#pragma unroll
+                    for (int k = 0; k < kQ; k++)
+                        if (k < n) score((int) (P[k] & 0xFFFFu), P[k] >> 16);
+                    n = 0;
+                    if (!__any(more)) break;
+                }
+            } else {
             for (int ix = q.minCx; ix <= q.maxCx; ix++) {
                 const int c0 = ix * GRID_ROWS;
                 const int s = L.cellStart[c0 + q.minCy], e = L.cellStart[c0 + q.maxCy + 1];
@@ -675,6 +761,7 @@ __global__ __launch_bounds__(kMatchBlock) void k_match_last(MatchArgs A) {
                     insert(key, jj);
                 }
                 colBase += (unsigned) (e - s);
+            }
             }
         }
         if (LPQ > 1) {   // the lanes of a query fold their lists: pairs, quads, eights, ... (LPQ is the same for the whole wave)
@@ -1999,7 +2086,8 @@ hipError_t launch_proj_search(hipStream_t st, const ProjArgs &A, int maxKeys) {
 }
 
 hipError_t match_prepare(size_t ldsBytes) {
-    return hipFuncSetAttribute((const void *) k_match_last, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    const hipError_t e = hipFuncSetAttribute((const void *) k_match_last<false>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
+    return e != hipSuccess ? e : hipFuncSetAttribute((const void *) k_match_last<true>, hipFuncAttributeMaxDynamicSharedMemorySize, kMaxDynLds);
 }
 
 void launch_backproject_unit(hipStream_t st, const ygzf_kp *keys, const int *cnt, long long kpStride, int maxKp, int nFrames, float fx,
@@ -2009,7 +2097,9 @@ void launch_backproject_unit(hipStream_t st, const ygzf_kp *keys, const int *cnt
 }
 
 void launch_match_last(hipStream_t st, const MatchArgs &A, int nPairs, size_t ldsBytes) {
-    hipLaunchKernelGGL(k_match_last, dim3(nPairs * (A.split > 1 ? A.split : 1)), dim3(kMatchBlock), ldsBytes, st, A);
+    // (the filtered scan is an instantiation of its own: the code of the several-workgroups-per-pair launch does not change with it)
+    if (A.scanFiltered && A.split <= 1) hipLaunchKernelGGL(k_match_last<true>, dim3(nPairs), dim3(kMatchBlock), ldsBytes, st, A);
+    else hipLaunchKernelGGL(k_match_last<false>, dim3(nPairs * (A.split > 1 ? A.split : 1)), dim3(kMatchBlock), ldsBytes, st, A);
 }
 
 }  // namespace ygzf

@@ -50,6 +50,7 @@ static int plan_match_lds(ygzf_ctx *c, MatchArgs &A, int nPairs, size_t *ldsByte
     A.serialOrder = c->matchSerial;
     A.handoverFence = c->matchFence;
     A.fixedLanes = c->matchFixedLanes;
+    A.scanFiltered = c->matchScanFiltered;
     A.split = 1;
     A.splitCnt = nullptr;
     A.splitX = nullptr;

@@ -240,6 +240,9 @@ struct ygzf_ctx {
     size_t uploadKernelBytes = (size_t) forced("upload_kernel_bytes", 16l << 20);
     int matchSplit = (int) forced("match_split", 0);   // 0 automatic, 1 off, n workgroups per pair
     int matchFixedLanes = forced_is("match_lanes", "fixed");   // eight lanes per query whatever the launch
+    // form of the speculative scan in launches with one workgroup per pair: descriptors read for the keypoints that passed the window filters
+    // only (filtered), or for every keypoint of the cell window (predicated: what several workgroups per pair always run)
+    int matchScanFiltered = forced_is("match_scan", "predicated") ? 0 : forced_is("match_scan", "filtered") ? 1 : kMatchScanFilteredDefault;
     int matchFence = (int) forced("match_fence", 0);   // 1: full fences around the matcher's hand-over
     int matchSerial = (int) forced("match_serial", 0);   // 1: the one-wave in-order pass instead of the fixpoint; 2: fixpoint that hands over at the first exhausted list (tests)
     bool siaPerLevel = forced("sia_precompute", 1) != 0;   // reference patches of all levels in a kernel of their own (0: inside k_sia_run, as until round 4)
