@@ -5,6 +5,7 @@
 //   k_octree       K4  DistributeOctTree                      (:533-723) as sort-by-path-key + breadth-first on ranges
 //                      phases: oct_carve | oct_attempt { oct_cell_prefix, oct_key_tables, oct_path_keys, oct_hand_over, oct_order,
 //                      oct_subdivide { oct_head, oct_full_pass, oct_expand_round } } | oct_best_hist / oct_best_sorted | oct_emit_keypoints
+//   k_oct_key_tables   k_octree's key tables, once per geometry (oct_key_tables_write)
 //   k_describe     K5+K6+K7  IC_Angle (:77-101), GaussianBlur 7x7 s=2 (:1010) on the 37x37 patch only,
 //                            computeOrbDescriptor (:105-149)
 //
@@ -165,14 +166,15 @@ __device__ __forceinline__ void block_scan_array3(int *a, int *b, int *c, int n,
     *totA = (int) (total & 0x1FFFFFu); *totB = (int) ((total >> 21) & 0x1FFFFFu); *totC = (int) (total >> 42);
 }
 
-// Stable LSD radix sort (kRadixBits-bit digits) of n (key,val) pairs on `bits` key bits by the whole block.
+// Stable LSD radix sort (kRadixBits-bit digits) of n (key,val) pairs on the key bits [shift0, bits) by the whole block (bits below shift0 are not
+// looked at: equal keys above them keep their input order).
 // k0/v0 hold the input; result is left in *rk/*rv (one of the two buffers).  Buffers may be LDS or global.
 // histT: radix_hist_ints(kWaves) ints of LDS (digit-major, one counter per wave), tmp: 17 ints of LDS.  kWaves = the block's waves (<= 16).
 // Seven-bit digits: the octree's 21-bit path keys take three passes (4-bit digits took six, at ~3.4 us of mostly barrier time each).
 constexpr int kRadixBits = 7;
 constexpr int radix_hist_ints(int waves) { return (1 << kRadixBits) * waves; }
 template <int kWaves>
-__device__ void block_radix_sort(unsigned *k0, unsigned *v0, unsigned *k1, unsigned *v1, int n, int bits,
+__device__ void block_radix_sort(unsigned *k0, unsigned *v0, unsigned *k1, unsigned *v1, int n, int shift0, int bits,
                                  volatile int *histT, int *tmp, unsigned **rk, unsigned **rv) {
     static_assert(kWaves >= 1 && kWaves <= 16, "block_excl_scan's scratch holds up to 16 waves");
     const int lane = lane_id(), wave = wave_id();
@@ -182,7 +184,7 @@ __device__ void block_radix_sort(unsigned *k0, unsigned *v0, unsigned *k1, unsig
     const int end = min(n, start + seg);
     const unsigned long long lt = (1ull << lane) - 1ull;
     constexpr int NB = 1 << kRadixBits;
-    for (int shift = 0; shift < bits; shift += kRadixBits) {
+    for (int shift = shift0; shift < bits; shift += kRadixBits) {
         for (int t = threadIdx.x; t < NB * nw; t += blockDim.x) histT[t] = 0;
         __syncthreads();
         for (int i = start + lane; i < end; i += 64) {
@@ -1334,12 +1336,14 @@ struct OctLevel {
     unsigned long long *tmp64;
     // ---- per attempt ----
     bool hist, inLds;             // this attempt runs the histogram plan; the candidates are sorted in LDS
+    int lowBit;                   // sort plan: the keys are ordered on their bits >= lowBit only (0: on all of them); oct_bounds refuses digits below it
     int M;                        // candidates of the level
     unsigned *skeys, *svals;      // where the ordered keys / values ended up (sort plan)
     int n, cur, nE;               // the tree: nodes of list `cur`, expandable ones among them
 };
 
-// of an attempt: the tree stands / this workgroup is finished with the level (a helper, or no candidates) / once more without helpers / once more on the sorting path
+// of an attempt: the tree stands / this workgroup is finished with the level (a helper, or no candidates) / once more without helpers / once more on the sorting
+// path, every key bit sorted (the sort plan's own restart after its prefix sort stays inside the attempt: oct_attempt)
 enum OctOutcome { kOctDone, kOctLeft, kOctAgainAlone, kOctAgainSorted };
 __device__ __forceinline__ void oct_stamp(const OctLevel &w, long long *dbg, int k) {
     if (dbg && w.tid == 0 && w.f == 0 && w.part == 0) dbg[w.l * 8 + k] = wall_clock64();
@@ -1398,10 +1402,12 @@ template <int kBlock> __device__ __forceinline__ int oct_cell_prefix(const OctAr
 // A workgroup has ONE CU: 2800 candidates x ~300 instructions of cell decode (a division), root (a float division) and ten
 // subdivision steps were 7 us of a 752x480 level 0.  x and y subdivide independently, so the key is the OR of a per-column word
 // (root, x bits spread to the even positions) and a per-row word (y bits on the odd positions): both tables and the cells' origins
-// are built once per workgroup in the node arrays (idle until the tree passes) when they fit there.
-template <int kBlock> __device__ __forceinline__ void oct_key_tables(const OctLevel &w, int lenX, int lenY) {
-    const LevelGeom &g = w.g;
-    unsigned *xTab = w.xTab, *yTab = xTab + lenX, *orgTab = yTab + lenY;
+// lie in the node arrays (idle until the tree passes) when they fit there.  Their inputs are LevelGeom fields only -- the same words for every
+// frame and every call until the geometry changes (each with a depth-long halving loop, a bit spread and a float division: ~1500 entries for a
+// 752x480 level 0, once in each of the 2048 workgroups of a sub-batch): k_oct_key_tables writes them once per geometry (oct_key_tables_write, the one
+// statement of their arithmetic) and a workgroup copies its level's into LDS.
+__device__ __forceinline__ void oct_key_tables_write(const LevelGeom &g, int lenX, int lenY, int nCells, unsigned *xTab, int tid, int stride) {
+    unsigned *yTab = xTab + lenX, *orgTab = yTab + lenY;
     auto spread = [](unsigned v) {
         v = (v | (v << 8)) & 0x00FF00FFu;
         v = (v | (v << 4)) & 0x0F0F0F0Fu;
@@ -1418,7 +1424,7 @@ template <int kBlock> __device__ __forceinline__ void oct_key_tables(const OctLe
         }
         return k;
     };
-    for (int t = w.tid; t < lenX + lenY + w.nCells; t += kBlock) {
+    for (int t = tid; t < lenX + lenY + nCells; t += stride) {
         if (t < lenX) {
             const int root = min((int) ((float) t / g.hX), g.nIni - 1);
             xTab[t] = ((unsigned) root << (2 * g.depth)) | spread(halvings(t, (int) (g.hX * (float) root), (int) (g.hX * (float) (root + 1))));
@@ -1430,6 +1436,20 @@ template <int kBlock> __device__ __forceinline__ void oct_key_tables(const OctLe
             orgTab[c] = (unsigned) (cj * g.wCell) | ((unsigned) (ci * g.hCell) << 16);
         }
     }
+}
+// one workgroup per level; off: the level's first word in tabs (kernels.h: oct_tab_words of them).  The buffer's first kMaxLevels words are the
+// offsets themselves: k_octree finds its level's tables with one scalar load (sixteen more kernel-argument words indexed by the level cost it registers)
+struct OctTabOffsets { int off[kMaxLevels]; };
+__global__ __launch_bounds__(256) void k_oct_key_tables(const LevelGeom *__restrict__ geom, OctTabOffsets offs, unsigned *__restrict__ tabs) {
+    const LevelGeom g = geom[blockIdx.x];
+    if (threadIdx.x == 0) tabs[blockIdx.x] = (unsigned) offs.off[blockIdx.x];
+    if (g.nCols <= 0 || g.nRows <= 0) return;
+    oct_key_tables_write(g, oct_tab_len_x(g), oct_tab_len_y(g), g.nCols * g.nRows, tabs + offs.off[blockIdx.x], (int) threadIdx.x, (int) blockDim.x);
+}
+// the level's tables from the geometry's buffer into this workgroup's LDS
+template <int kBlock> __device__ __forceinline__ void oct_key_tables(const OctArgs &a, const OctLevel &w, int lenX, int lenY) {
+    const unsigned *src = a.keyTabs + a.keyTabs[w.l];
+    for (int t = w.tid; t < lenX + lenY + w.nCells; t += kBlock) w.xTab[t] = src[t];
     __syncthreads();
 }
 
@@ -1549,8 +1569,12 @@ template <int kBlock> __device__ __forceinline__ void oct_order(OctLevel &w) {
         if (w.tid == 0) w.PS[w.nBins] = w.M;
         __syncthreads();
     } else {
+        // Prefix sort (lowBit = keyBits - 2 * kRadixBits > 0): two passes instead of three.  A tree pass reads a key through the root search
+        // (key >> 2 * depth) and through one two-bit digit per depth, from the top down; the sort is stable, so every node whose digits lie at
+        // or above lowBit is the same contiguous range with the same members, in candidate order inside.  A level of 60-220 wanted nodes stops
+        // at depth 4-6 of its 8-10; a tree that goes on below lowBit is refused by oct_bounds and the level sorts again, on every bit.
         unsigned *sk, *sv;
-        block_radix_sort<kBlock / 64>(w.key0, w.val0, w.key1, w.val1, w.M, w.g.keyBits, w.histT, w.tmp, &sk, &sv);
+        block_radix_sort<kBlock / 64>(w.key0, w.val0, w.key1, w.val1, w.M, w.lowBit, w.g.keyBits, w.histT, w.tmp, &sk, &sv);
         w.skeys = sk; w.svals = sv;
         if (w.inLds && w.candB && w.skeys == w.key1) {   // (uniform) an odd number of passes ended over the node arrays: back to the first buffer
             for (int i = w.tid; i < w.M; i += kBlock) { w.key0[i] = w.key1[i]; w.val0[i] = w.val1[i]; }
@@ -1581,8 +1605,15 @@ __device__ __forceinline__ void oct_bounds(const OctLevel &w, int lo, int cnt, i
         const int sh = 2 * (w.dm - dep);       // a node of depth dep spans 2^sh bins, aligned
         const int f0 = oct_first_bin(w.PS, w.nBins, sh, lo), s1 = 1 << (sh - 2);
         *a1 = w.PS[f0 + s1]; *a2 = w.PS[f0 + 2 * s1]; *a3 = w.PS[f0 + 3 * s1];
-    } else
-        digit_bounds3(w.skeys, lo, cnt, 2 * (w.g.depth - (dep + 1)), a1, a2, a3);
+    } else {
+        const int shift = 2 * (w.g.depth - (dep + 1));
+        if (shift < w.lowBit) {                // a digit the prefix sort did not order: start over with the full sort (the same dummy answer)
+            *w.overflow = 1;
+            *a1 = *a2 = *a3 = lo + cnt;
+            return;
+        }
+        digit_bounds3(w.skeys, lo, cnt, shift, a1, a2, a3);
+    }
 }
 // of the four children [lo, a1), [a1, a2), [a2, a3), [a3, hi): k = the non-empty ones, e = those with more than one point (expandable)
 __device__ __forceinline__ void oct_child_counts(int lo, int a1, int a2, int a3, int hi, int *k, int *e) {
@@ -1594,11 +1625,13 @@ __device__ __forceinline__ void oct_child_counts(int lo, int a1, int a2, int a3,
 template <typename T> __device__ __forceinline__ void oct_place_children(const OctNodes &out, int lo, int cnt, int dep, int a1, int a2, int a3, int p, T *ePos, T *eCnt, int es) {
     const int bb[5] = {lo, a1, a2, a3, lo + cnt};
     int epos[4];
+#pragma unroll                       // (both loops: bb[] and epos[] indexed by a loop counter would live in scratch memory)
     for (int c = 3; c >= 0; c--) {   // list order n4,n3,n2,n1
         const int cc2 = bb[c + 1] - bb[c];
         epos[c] = p;
         if (cc2 > 0) { out.lo[p] = bb[c]; out.cnt[p] = cc2; out.dep[p] = dep + 1; p++; }
     }
+#pragma unroll
     for (int c = 0; c < 4; c++) {    // creation order n1..n4
         const int cc2 = bb[c + 1] - bb[c];
         if (cc2 > 1) { ePos[es] = (T) epos[c]; eCnt[es] = (T) cc2; es++; }
@@ -1766,7 +1799,7 @@ template <int kBlock> __device__ __forceinline__ void oct_expand_round(OctLevel 
     unsigned *ek, *ev;
     if (nE <= kBlock) { oct_rank_sort<kBlock>(w, nE); ek = S.sk[1]; ev = S.sv[1]; }
     else
-        block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], nE, seqBits + cntBits, w.histT, w.tmp, &ek, &ev);
+        block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], nE, 0, seqBits + cntBits, w.histT, w.tmp, &ek, &ev);
     // processing order j: descending (size, creation seq)
     for (int j = tid; j < nE; j += kBlock) {
         const int pos = S.Epos[(int) ev[nE - 1 - j]];
@@ -1856,10 +1889,15 @@ template <int kBlock> __device__ __forceinline__ void oct_subdivide(OctLevel &w,
 // One attempt at the level, steps 1 - 4: from the cell counts to the final node list (w.n nodes in list w.cur).
 //   useHist   histogram plan (kHist only); an attempt that had to split a node below depth dm asks for another one on the sorting path
 //   alone     workgroup 0 takes every candidate itself; an attempt whose helpers did not arrive within the spin budget asks for another one alone
-template <bool kHist, int kBlock> __device__ __forceinline__ OctOutcome oct_attempt(const OctArgs &a, OctLevel &w, bool useHist, bool alone) {
+//   fullSort  the sorting path orders the keys on every bit (what follows the histogram plan's overflow); otherwise, where the launch asks for it
+//             (OctArgs::sortPrefix) and the key is longer, on its top 2 * kRadixBits bits first: a tree that had to read a digit below them raises
+//             the overflow flag as the histogram plan's does, and the attempt sorts its keys once more, on every bit, and starts the tree over
+//             (steps 3 and 4 again: the keys themselves stand)
+template <bool kHist, int kBlock> __device__ __forceinline__ OctOutcome oct_attempt(const OctArgs &a, OctLevel &w, bool useHist, bool alone, bool fullSort) {
     const LevelGeom &g = w.g; const int tid = w.tid;
     w.hist = kHist && useHist;
-    if (kHist && tid == 0) *w.overflow = 0;
+    w.lowBit = !kHist && a.sortPrefix && !fullSort && g.keyBits > 2 * kRadixBits ? g.keyBits - 2 * kRadixBits : 0;
+    if (tid == 0) *w.overflow = 0;
     w.M = oct_cell_prefix<kBlock>(a, w);
     if (w.M == 0) { oct_empty_level<kBlock>(a, w); return kOctLeft; }
     oct_stamp(w, a.dbg, 1);
@@ -1869,9 +1907,9 @@ template <bool kHist, int kBlock> __device__ __forceinline__ OctOutcome oct_atte
         if (w.candB) { w.key1 = w.candB; w.val1 = w.candB + a.ldsCand; }
         else { w.key1 = w.S.cand + 2 * a.ldsCand; w.val1 = w.S.cand + 3 * a.ldsCand; }
     }
-    const int lenX = max(g.regW, g.nCols * g.wCell) + 9, lenY = max(g.regH, g.nRows * g.hCell) + 9;
+    const int lenX = oct_tab_len_x(g), lenY = oct_tab_len_y(g);
     const bool useTab = lenX + lenY + w.nCells <= oct_lds_tab_room(kHist, w.nCells, a.cap, a.regionInts) && g.depth <= 15;
-    if (useTab) oct_key_tables<kBlock>(w, lenX, lenY);
+    if (useTab) oct_key_tables<kBlock>(a, w, lenX, lenY);
     if (w.hist) {
         for (int b = tid; b <= w.nBins; b += kBlock) w.PS[b] = 0;
         __syncthreads();
@@ -1884,9 +1922,24 @@ template <bool kHist, int kBlock> __device__ __forceinline__ OctOutcome oct_atte
     }
     __syncthreads();
     oct_stamp(w, a.dbg, 2);
-    oct_order<kBlock>(w);
-    oct_stamp(w, a.dbg, 3);
-    oct_subdivide<kBlock>(w, a.dbg);
+    for (;;) {
+        oct_order<kBlock>(w);
+        oct_stamp(w, a.dbg, 3);
+        oct_subdivide<kBlock>(w, a.dbg);
+        if (w.lowBit == 0 || !*w.overflow) break;   // (uniform, as below)
+        // The tree read a digit below the sorted prefix: the keys once more, on every bit, and the tree from its roots.  The prefix sort left
+        // the (key, value) pairs in the first buffer (two passes), in candidate order among equal prefixes: three stable passes over them end
+        // in the order three passes over the candidates would have ended in -- pair for pair what the full sort alone gives.  The second
+        // buffer (over the cell table and the node arrays when the candidates are in LDS) is free again: the tree starts over.
+        __syncthreads();                       // (everybody has read the flag)
+        if (tid == 0) {
+            *w.overflow = 0;
+            if (a.dbg) atomicAdd((unsigned long long *) &a.dbg[16 * 8 + w.l], 1ull);   // restarts of this level over the launch's frames
+        }
+        w.lowBit = 0;
+        w.key0 = w.skeys; w.val0 = w.svals;
+        __syncthreads();
+    }
     if (w.hist && *w.overflow) {   // (uniform: every write of the flag lies before the barrier that ended the tree passes)
         __syncthreads();
         if (a.dbg && tid == 0) atomicAdd((unsigned long long *) &a.dbg[16 * 8 + w.l], 1ull);   // restarts of this level over the launch's frames
@@ -1955,6 +2008,11 @@ template <int kBlock> __device__ __forceinline__ void oct_best_sorted(const OctL
 template <int kBlock> __device__ __forceinline__ void oct_emit_keypoints(const OctArgs &a, const OctLevel &w) {
     const OctShared &S = w.S; const LevelGeom &g = w.g;
     const int tid = w.tid, n = w.n;
+    // tiles of 64x64 px over the level image, row-major: the compact key (ky >> 6) * tilesX + (kx >> 6) orders as (ky >> 6) << 6 | kx >> 6 does
+    // (kx >> 6 < tilesX <= 64) and needs one radix pass, not two, up to 128 tiles (a 752x480 level has at most 12 x 8)
+    const int tilesX = (g.w + 63) >> 6, tilesY = (g.h + 63) >> 6;
+    int tileBits = 0;
+    while ((1 << tileBits) < tilesX * tilesY) tileBits++;
     unsigned *oxy = a.lvlKpXY + (long long) w.f * a.kpStride + g.kpBase;
     unsigned char *osc = a.lvlKpScore + (long long) w.f * a.kpStride + g.kpBase;
     for (int i = tid; i < n; i += kBlock) {         // a thread per node: the dependent global read of the winner's position, all in flight at once
@@ -1968,14 +2026,14 @@ template <int kBlock> __device__ __forceinline__ void oct_emit_keypoints(const O
         S.b2[i] = (int) (best >> 24);
         // spatial key for the PROCESSING order of k_describe: 64x64-px tile id, stable within a tile (locality of the
         // 43x43 window gathers; the output order is untouched)
-        S.sk[0][i] = ((ky >> 6) << 6) | (kx >> 6);
+        S.sk[0][i] = (ky >> 6) * (unsigned) tilesX + (kx >> 6);
         S.sv[0][i] = (unsigned) i;
     }
     __syncthreads();
     // (launches of a few frames -- one Tracking frame -- keep the list order: the sort buys cache locality across many frames' windows and
-    // costs two block-wide passes of its own)
+    // costs a block-wide pass of its own)
     unsigned *ok = S.sk[0], *ov = S.sv[0];
-    if (gridDim.y > 4) block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], n, 12, w.histT, w.tmp, &ok, &ov);
+    if (gridDim.y > 4) block_radix_sort<kBlock / 64>(S.sk[0], S.sv[0], S.sk[1], S.sv[1], n, 0, tileBits, w.histT, w.tmp, &ok, &ov);
     // k_describe's work list: processing position i -> (x | y << 16, score | list position << 8) in ONE record, so that a describe wave
     // knows its keypoint after a single memory round trip (it used to follow procOrder -> position / score: two dependent ones)
     // (score | list position << 8 | level << 24; positions past the level's count carry kNoKeypoint so that the wave there leaves at once)
@@ -2050,14 +2108,14 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(kHist ? 
     w.nBins = g.nIni << (2 * w.dm);
     w.binShift = 2 * (g.depth - w.dm);
     // what survives an attempt at the level: the plan, and whether workgroup 0 gave up waiting for its helpers
-    bool useHist = kHist && w.dm >= 1, alone = false;
+    bool useHist = kHist && w.dm >= 1, alone = false, fullSort = false;
     if (w.part != 0 && !useHist) { oct_helper_leaves(w); return; }   // (no histogram for this level: workgroup 0 sorts, alone)
     for (;;) {
-        const OctOutcome o = oct_attempt<kHist, kBlock>(a, w, useHist, alone);
+        const OctOutcome o = oct_attempt<kHist, kBlock>(a, w, useHist, alone, fullSort);
         if (o == kOctLeft) return;
         if (o == kOctDone) break;
         if (o == kOctAgainAlone) alone = true;
-        else useHist = false;                  // (kOctAgainSorted)
+        else { useHist = false; fullSort = true; }   // (kOctAgainSorted: from the histogram to the sort on every key bit)
     }
     oct_stamp(w, a.dbg, 4);
     if (w.hist) oct_best_hist<kBlock>(w);
@@ -2740,6 +2798,12 @@ hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist) {
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *) k_octree<false, false, 512>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
     if (e == hipSuccess) e = hipFuncSetAttribute((const void *) k_octree<false, false, 256>, hipFuncAttributeMaxDynamicSharedMemorySize, kOctMaxDyn);
     return e;
+}
+
+void launch_oct_key_tables(hipStream_t st, const LevelGeom *dGeom, int nlevels, const int *offHost, unsigned *tabs) {
+    OctTabOffsets offs{};
+    for (int l = 0; l < nlevels && l < kMaxLevels; l++) offs.off[l] = offHost[l];
+    hipLaunchKernelGGL(k_oct_key_tables, dim3(nlevels), dim3(256), 0, st, dGeom, offs, tabs);
 }
 
 void launch_octree(hipStream_t st, const OctArgs &a, int nLaunchLevels, int nFrames, size_t ldsBytes, int block, int helpers) {

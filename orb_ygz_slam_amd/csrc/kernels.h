@@ -80,6 +80,12 @@ void launch_fast_tab_persist(hipStream_t st, const FrameSet &fs, const FastCellR
                              int totalCells, long long totalSlots, int totalGroups, int smapRows, int nFrames, int winRows, int quadCap, bool iniFirst,
                              unsigned *stats, unsigned *counters, int nWorkgroups);
 constexpr int kFastStatWords = 8 * 64;   // `stats`: 64 x {cells sampled, cells whose keypoints are FAST(minTh)'s, score rounds beyond the first, plan: 1 one pass / 2 iniTh first, corner-bearing quads, quads, -, pass-1 runs}
+// k_octree's key tables of a level: a key word per column (lenX) and per row (lenY) of the level's candidate region, the origin of every cell.  They
+// depend on the geometry alone: k_oct_key_tables writes them once per geometry and k_octree copies them into LDS where they fit (oct_lds_tab_room).
+__host__ __device__ inline int oct_tab_len_x(const LevelGeom &g) { return (g.regW > g.nCols * g.wCell ? g.regW : g.nCols * g.wCell) + 9; }
+__host__ __device__ inline int oct_tab_len_y(const LevelGeom &g) { return (g.regH > g.nRows * g.hCell ? g.regH : g.nRows * g.hCell) + 9; }
+__host__ __device__ inline int oct_tab_words(const LevelGeom &g) { return g.nCols <= 0 || g.nRows <= 0 ? 0 : oct_tab_len_x(g) + oct_tab_len_y(g) + g.nCols * g.nRows; }
+void launch_oct_key_tables(hipStream_t st, const LevelGeom *dGeom, int nlevels, const int *offHost, unsigned *tabs);   // offHost: nlevels word offsets into tabs, behind its kMaxLevels-word header
 int octree_lds_cand(int maxCellsPerLevel, int cap, size_t budget);   // the sort plan's candidate budget within `budget` bytes of LDS node arrays + buffers (0: < 256)
 hipError_t octree_prepare(size_t ldsBytes, bool globalNodes, bool hist);
 // One launch of k_octree: levels [levelBase, levelBase + gridDim.x) of gridDim.y frames, one workgroup per (level, frame) -- the histogram plan
@@ -105,6 +111,11 @@ struct OctArgs {
     // histogram plan); nullable: 19 * cap ints per (frame, level) for the node arrays instead of LDS
     int cap, ldsCand;
     int *nodeArena;
+    // sort plan with LDS node arrays: 1 = a level whose key is longer than two radix digits is sorted on its top two digits only and starts over
+    // with the full sort if its tree reads a digit below them (YGZF_FORCE=oct_sort=prefix|full; the other two plans sort on every bit)
+    int sortPrefix;
+    // the geometry's key tables (launch_oct_key_tables): level l's xTab | yTab | orgTab from word keyTabs[l] on (the first kMaxLevels words are the offsets)
+    const unsigned *keyTabs;
     // histogram plan (histBins > 0): regionInts ints shared by the cell table, the key tables and the node arrays, then histBins + 1 ints of prefix table
     int regionInts, histBins;
     // helper hand-over (gHist non-null: gridDim.z workgroups per (level, frame)): one slice of histBins counts per helper; per (frame, level) the helpers

@@ -79,6 +79,10 @@ int apply_geometry(ygzf_ctx *c, int w, int h, int nFrames) {
         rc = ensure(c, c->dFastCells, std::max<size_t>(G.fastCells.size() * sizeof(FastCellRec), 32));
         if (rc) return rc;
         if (!G.fastCells.empty()) HIPCHECK(c, hipMemcpy(c->dFastCells.p, G.fastCells.data(), G.fastCells.size() * sizeof(FastCellRec), hipMemcpyHostToDevice));
+        rc = ensure(c, c->dOctKeyTabs, std::max<size_t>((size_t) oct.keyTabWords * sizeof(unsigned), 16));
+        if (rc) return rc;
+        launch_oct_key_tables(c->stream, (const LevelGeom *) c->dGeom.p, L, oct.keyTabOff, (unsigned *) c->dOctKeyTabs.p);   // (stream order puts it ahead of every octree launch)
+        HIPCHECK(c, hipGetLastError());
         if (oct.haveSmall || oct.kind == OctPlan::Hist) HIPCHECK(c, octree_prepare(0, false, true));
         if (oct.kind != OctPlan::Hist) HIPCHECK(c, octree_prepare(oct.launches[0].lds, oct.launches[0].arena, false));
         c->oct = oct;
@@ -251,6 +255,8 @@ static OctArgs oct_args(const ygzf_ctx *c, const OctLaunch &grp, long long *odbg
     a.lvlKpXY = (unsigned *) c->dLvlXY.p; a.lvlKpScore = (unsigned char *) c->dLvlScore.p; a.lvlKpCnt = (int *) c->dLvlCnt.p; a.lvlCandCnt = (int *) c->dLvlCand.p;
     a.ldsCand = grp.ldsCand; a.regionInts = grp.regionInts; a.histBins = grp.histBins;
     a.nodeArena = grp.arena ? (int *) c->dOctNodes.p : nullptr;
+    a.sortPrefix = c->pins.octSortPrefix && !grp.arena && grp.histBins == 0;
+    a.keyTabs = (const unsigned *) c->dOctKeyTabs.p;
     return a;
 }
 
@@ -321,6 +327,12 @@ static int report_octree(ygzf_ctx *c, int nFrames, int L, const long long *odbg,
         const OctLaunch &one = plan.launches[0];
         fprintf(stderr, "[ygzf octree single launch: levels 0-%d cap %d candidates %d lds %zu node arrays in %s]\n", L - 1, one.cap, one.ldsCand, one.lds,
                 one.arena ? "the arena" : "lds");
+    }
+    if (!smallHelpers && plan.kind != OctPlan::Hist) {   // (a line of its own: the two above are parsed by their launch lists)
+        const bool prefix = c->pins.octSortPrefix && !plan.launches[0].arena;
+        fprintf(stderr, "[ygzf octree key order: %s; workgroups of %d frames that started over with the full sort, per level:", prefix ? "prefix" : "full", nFrames);
+        for (int l = 0; l < L; l++) fprintf(stderr, " %lld", st[16 * 8 + l]);
+        fprintf(stderr, "]\n");
     }
     if (smallHelpers) {
         fprintf(stderr, "[ygzf octree small plan: %d frames, %d workgroups per level; workgroups 0 that gave up waiting for their helpers, per level:", nFrames, smallHelpers);

@@ -138,6 +138,7 @@ struct ygzf_ctx {
     int octDoneTarget = 0;     // what the launches since that clear have brought every (level, frame) counter of the layout to
     static constexpr int octSmallWgs = 128;   // launches of up to this many workgroups take oct.small (752x480: 16 frames 0.211 against 0.221 ms, 64 frames 0.439 against 0.430)
     Buf dOctNodes;
+    Buf dOctKeyTabs;           // k_octree's key tables of the current geometry (OctPlan::keyTabOff; written by apply_geometry with the geometry's other tables)
     // FAST threshold plan (extract_kernels.hip, fast_cell): 0 = chosen per batch from the statistics the kernel leaves behind, 1 = one pass at
     // minTh, 2 = iniTh first.  Identical results either way.
     int fastPlan = 0;

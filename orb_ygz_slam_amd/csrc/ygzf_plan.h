@@ -46,6 +46,7 @@ struct PlanPins {
     int octBlock = 0;                // ... the workgroup size of every launch (256 / 512 / 1024)
     size_t octLdsBytes = 0;          // oct_lds_kb: ... the LDS of every launch
     enum OctPlanPin { Auto, Hist, Sort } octPlan = Auto;
+    bool octSortPrefix = true;       // oct_sort=prefix|full: the sort plan orders path keys longer than two radix digits on their top two digits first (full: on every bit, always)
     int octHistBins = 0;             // bounds the histogram
     int octHelpers = -1, octHelperSpin = 1 << 16;
     int fastPersist = -1, fastPersistWgs = 8;   // fastPersist: 1 always, 0 never (tests)
@@ -58,6 +59,7 @@ struct PlanPins {
         p.octBlock = (int) forced("oct_block", p.octBlock);
         p.octLdsBytes = (size_t) forced("oct_lds_kb", 0) * 1024;
         p.octPlan = forced_is("oct_plan", "hist") ? Hist : forced_is("oct_plan", "sort") ? Sort : Auto;
+        p.octSortPrefix = forced_is("oct_sort", "full") ? false : forced_is("oct_sort", "prefix") ? true : p.octSortPrefix;
         p.octHistBins = (int) forced("oct_hist_bins", p.octHistBins);
         p.octHelpers = (int) forced("oct_helpers", p.octHelpers);
         p.octHelperSpin = (int) forced("oct_helper_spin", p.octHelperSpin);
@@ -85,6 +87,10 @@ struct OctPlan {
     std::vector<OctLaunch> launches;
     bool haveSmall = false;
     OctLaunch small;
+    // the key tables of the geometry (kernels.h: oct_tab_words per level, every level's first word a multiple of four, behind a header of
+    // kMaxLevels words that repeats the offsets for the kernel): written once when the geometry is planned, read by every launch of every plan
+    int keyTabOff[kMaxLevels] = {0};
+    int keyTabWords = 0;
 };
 // oneGroup: all levels in one launch of kOctBlock threads (YGZF_FORCE=oct_groups=1); block > 0 / ldsBytes > 0 pin every launch's workgroup / LDS
 YGZF_HIDDEN std::vector<OctLaunch> plan_oct_sort(const Geometry &G, int L, bool oneGroup, int block, size_t ldsBytes);

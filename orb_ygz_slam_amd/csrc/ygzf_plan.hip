@@ -474,6 +474,11 @@ int plan_octree(const Geometry &G, int L, const PlanPins &pins, OctPlan &plan, s
     // per level; its tree passes 12 us against 20) wins even where the candidates would fit LDS -- if all levels go in ONE launch, sized for
     // the largest (with a handful of workgroups nobody else wants the LDS).  Launches of up to 128 workgroups take it (ygzf_ctx::octSmallWgs; oct_plan=sort: never).
     if (pins.octPlan != PlanPins::Sort) plan.haveSmall = size_oct_hist_group(G, 0, L, pins.octHistBins, true, &plan.small);
+    plan.keyTabWords = kMaxLevels;   // (the buffer's header: the offsets themselves)
+    for (int l = 0; l < L; l++) {
+        plan.keyTabOff[l] = plan.keyTabWords;
+        plan.keyTabWords += (oct_tab_words(G.lv[l]) + 3) & ~3;
+    }
     return YGZF_OK;
 }
 
