@@ -913,7 +913,7 @@ int ygzf_sim3_ransac(ygzf_ctx *ctx, int n_problems, const ygzf_sim3_problem *pro
  * EdgeInverseSim3ProjectXYZ (P3D1c through its inverse and K2 against kpUn2.pt), Huber kernels of delta float(sqrt(th2)), optimize(5), the
  * gate `e12->chi2() > th2 || e21->chi2() > th2` on the errors of the last Levenberg trial, optimize(nBad > 0 ? 10 : 5), the gate again --
  * g2o's arithmetic in fp64 with the NUMERIC Jacobian this fork runs (central differences of 1e-9 through a projection that is rounded to
- * float: a dither), stated once in csrc/sim3_opt_math.h and restated in tests/sim3_opt_cases.py.  PnPsolver stays the reference's.
+ * float: a dither), stated once in csrc/sim3_opt_math.h and restated in tests/sim3_opt_cases.py.  PnPsolver's hypotheses have a device form of their own (ygzf_pnp_ransac below).
  *
  * n_problems loop candidates per call, each independent of the others: one upload, one launch (a workgroup per problem), one download, one
  * synchronisation.  The caller does the host part of :2421-2536 (host/OptimizerSim3.h): the filter, GetIndexInKeyFrame and the float
@@ -945,6 +945,50 @@ typedef struct ygzf_sim3_opt_info {
 } ygzf_sim3_opt_info;
 int ygzf_optimize_sim3(ygzf_ctx *ctx, int n_problems, const ygzf_sim3_opt_problem *problems, double *S12_out, uint8_t *const *removed, int *ret,
                        ygzf_sim3_opt_info *info);
+
+/* ---- PnPsolver's EPnP RANSAC hypotheses   src/PnPsolver.cc:155-237 (iterate), :239-279 (Refine), :282-308 (CheckInliers), :341-894 (EPnP) -------
+ * The solver of Tracking::Relocalization (src/Tracking.cc:1755-1900), between SearchByBoW and PoseOptimization.  A hypothesis -- EPnP on
+ * min_set correspondences, then CheckInliers over all of them -- depends on nothing but its sample set, so the hypotheses of every candidate
+ * keyframe are evaluated in one call.  Refine (a second EPnP over the best-so-far inlier set, then CheckInliers) depends on the order only
+ * through WHICH set is the best so far: the set changes exactly at a record, a hypothesis h with n_inliers[h] >= min_inliers and
+ * n_inliers[h] > max(n_inliers[0 .. h-1]), and there the set is the record's own mask.  So the call refines every record and nothing else;
+ * the order-dependent rest of iterate (the `||` loop condition, the gates, bNoMore) is replayed on the host from these results.
+ *
+ * The arithmetic is the reference's fp64 (CheckInliers with its float roundings), every sum in the source's order, stated once in
+ * csrc/pnp_math.h and restated in tests/pnp_cases.py; the device equals both bit for bit.  The four OpenCV routines EPnP calls are fixed as
+ * one text there: cvMulTransposed as ordered sums; cvSVD as OpenCV 2.4 / 3.x's one-sided Jacobi for doubles with
+ * gamma = sqrt(p p + beta beta) in the place of libm hypot (which is not correctly rounded), at most max(m, 30) sweeps, a row whose singular
+ * value is <= DBL_MIN scaled by 0 in the place of OpenCV's pseudo-random refill; cvSolve / cvInvert(CV_SVD) as that SVD and a
+ * back-substitution that passes over singular values <= 2 DBL_EPSILON * (their sum).  The x that qr_solve leaves unwritten on a singular
+ * column is 0 on the first Gauss-Newton step.  Parity with a compiled OpenCV is unpinned.  There is no depth gate; non-finite inputs are
+ * legal and end through the bounded loops.
+ *
+ * n_problems solvers per call: one upload, two launches (k_pnp_hyp, k_pnp_refine) on one stream with no host step between them, one
+ * download, one synchronisation.  Per problem k:
+ *   hyp[k]           n_hyp x 12 doubles: mRi row-major, then mti;
+ *   n_inliers[k]     n_hyp ints: mnInliersi;
+ *   inlier_bits[k]   n_hyp x ceil(n / 64) words, bit i of word j = mvbInliersi[64 j + i], the bits beyond n zero.  The array, or any entry, may be NULL;
+ *   refined_n[k]     n_hyp ints: mnRefinedInliers of Refine on hypothesis h's mask where h is a record, -1 elsewhere;
+ *   refined_hyp[k]   n_hyp x 12 doubles, written for records only;
+ *   refined_bits[k]  as inlier_bits, written for records only (other rows zero).  The array, or any entry, may be NULL.
+ * A problem with n_hyp == 0 is legal and nothing of it is read or written.  Any n and n_hyp are accepted: the transfer block is a
+ * grow-on-demand buffer of the context.
+ * YGZF_ERR_INVALID: a NULL argument or array, n_problems <= 0, n_hyp < 0, min_set outside [4, YGZF_PNP_MAX_MIN_SET], n < min_set with
+ * n_hyp > 0, a sample index outside [0, n), an index repeated within a set. */
+#define YGZF_PNP_MAX_MIN_SET 8
+typedef struct ygzf_pnp_problem {
+    int n;                      /* N: the correspondences the constructor kept */
+    const float *P3Dw;          /* mvP3Dw, n x 3 */
+    const float *P2D;           /* mvP2D, n x 2 */
+    const float *max_err;       /* mvMaxError, n: the float product mvSigma2[i] * th2 */
+    double K[4];                /* fu fv uc vc, widened from the frame's floats */
+    int min_set;                /* mRansacMinSet */
+    int min_inliers;            /* mRansacMinInliers as SetRansacParameters adjusted it */
+    int n_hyp;
+    const int *samples;         /* n_hyp x min_set */
+} ygzf_pnp_problem;
+int ygzf_pnp_ransac(ygzf_ctx *ctx, int n_problems, const ygzf_pnp_problem *problems, double *const *hyp, int *const *n_inliers,
+                    uint64_t *const *inlier_bits, int *const *refined_n, double *const *refined_hyp, uint64_t *const *refined_bits);
 
 #ifdef __cplusplus
 }

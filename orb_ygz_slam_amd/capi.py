@@ -92,6 +92,11 @@ class Sim3Problem(C.Structure):   # ygzf_sim3_problem
                 ("K2", C.c_float * 4), ("fix_scale", C.c_int), ("n_hyp", C.c_int), ("samples", C.c_void_p)]
 
 
+class PnpProblem(C.Structure):   # ygzf_pnp_problem
+    _fields_ = [("n", C.c_int), ("P3Dw", C.c_void_p), ("P2D", C.c_void_p), ("max_err", C.c_void_p), ("K", C.c_double * 4), ("min_set", C.c_int),
+                ("min_inliers", C.c_int), ("n_hyp", C.c_int), ("samples", C.c_void_p)]
+
+
 class Sim3OptProblem(C.Structure):   # ygzf_sim3_opt_problem
     _fields_ = [("n", C.c_int), ("P1c", C.c_void_p), ("P2c", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p),
                 ("inv_sigma2_2", C.c_void_p), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("S12", C.c_double * 8), ("th2", C.c_float), ("fix_scale", C.c_int)]
@@ -286,6 +291,7 @@ def load_library(build_if_missing=True):
     L.ygzf_pose_optimization.argtypes = [vp, C.POINTER(Camera), vp, C.c_int, C.POINTER(PoseProblem), vp, vp, C.POINTER(vp), vp, C.POINTER(PoseInfo)]
     L.ygzf_sim3_ransac.argtypes = [vp, C.c_int, C.POINTER(Sim3Problem), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.ygzf_optimize_sim3.argtypes = [vp, C.c_int, C.POINTER(Sim3OptProblem), vp, C.POINTER(vp), vp, C.POINTER(Sim3OptInfo)]
+    L.ygzf_pnp_ransac.argtypes = [vp, C.c_int, C.POINTER(PnpProblem)] + [C.POINTER(vp)] * 6
     L.ygzf_stream.argtypes = [vp]
     L.ygzf_stream.restype = vp
     _lib = L
@@ -1245,6 +1251,32 @@ class Extractor:
         cp = (C.c_void_p * max(B, 1))(*[o["n_inliers"].ctypes.data for o in out])
         bp = (C.c_void_p * max(B, 1))(*[o["bits"].ctypes.data for o in out]) if want_bits else None
         self._ck(self.L.ygzf_sim3_ransac(self.h, B, recs, hp, cp, bp))
+        return out
+
+    def pnp_ransac(self, problems, want_bits=True):
+        """PnPsolver's EPnP RANSAC hypotheses and the Refine of their records over a batch of solvers in one call (ygzf_pnp_ransac).  problems:
+        dicts with P3Dw (n x 3), P2D (n x 2), max_err (n floats: mvSigma2 * th2), K (fu fv uc vc), min_inliers and samples (n_hyp x min_set).
+        -> list of dicts: hyp (n_hyp x 12 float64: R row-major, t), n_inliers (n_hyp), bits (n_hyp x ceil(n / 64) uint64; None without
+        want_bits), refined_n (n_hyp, -1 where the hypothesis is no record), refined_hyp, refined_bits (None without want_bits)."""
+        B = len(problems)
+        recs = (PnpProblem * max(B, 1))()
+        keep, out = [], []
+        for k, q in enumerate(problems):
+            P3, P2 = np.ascontiguousarray(q["P3Dw"], np.float32).reshape(-1, 3), np.ascontiguousarray(q["P2D"], np.float32).reshape(-1, 2)
+            e = np.ascontiguousarray(q["max_err"], np.float32).reshape(-1)
+            smp = np.ascontiguousarray(q["samples"], np.int32)
+            smp = smp.reshape(-1, smp.shape[-1] if smp.ndim == 2 else int(q.get("min_set", 4)))
+            n, nh, ms = len(P3), len(smp), int(q.get("min_set", smp.shape[1]))
+            assert len(P2) == n and len(e) == n and smp.shape[1] == ms
+            keep += [P3, P2, e, smp]
+            recs[k] = PnpProblem(n, _p(P3), _p(P2), _p(e), (C.c_double * 4)(*[float(v) for v in q["K"]]), ms, int(q["min_inliers"]), nh, _p(smp))
+            words = (n + 63) // 64
+            out.append(dict(hyp=np.zeros((nh, 12), np.float64), n_inliers=np.zeros(nh, np.int32), bits=np.zeros((nh, words), np.uint64) if want_bits else None,
+                            refined_n=np.zeros(nh, np.int32), refined_hyp=np.zeros((nh, 12), np.float64),
+                            refined_bits=np.zeros((nh, words), np.uint64) if want_bits else None))
+        arr = lambda key: (C.c_void_p * max(B, 1))(*[o[key].ctypes.data for o in out])
+        self._ck(self.L.ygzf_pnp_ransac(self.h, B, recs, arr("hyp"), arr("n_inliers"), arr("bits") if want_bits else None, arr("refined_n"),
+                                        arr("refined_hyp"), arr("refined_bits") if want_bits else None))
         return out
 
     def optimize_sim3(self, problems):

@@ -199,6 +199,7 @@ public:
     DBoW2::BowVector mBowVec;                     // read by KeyFrameDatabase::DetectRelocalizationCandidates (src/KeyFrameDatabase.cc:180-284)
     // read and written by Optimizer::PoseOptimization (src/Optimizer.cc:1656-1842)
     std::vector<float> mvInvLevelSigma2;
+    std::vector<float> mvLevelSigma2;             // read by PnPsolver's constructor (src/PnPsolver.cc:81)
     void SetPose(const SE3f &Tcw) { mTcw = Tcw; }   // (the reference also refreshes mRcw / mtcw / mOw: src/Frame.cc:338-346)
 };
 inline int MapPoint::PredictScale(const float &currentDist, Frame *pF) {  // src/MapPoint.cc:359-373

@@ -568,5 +568,27 @@ struct Sim3OptArgs {
 };
 void launch_sim3_opt(hipStream_t st, const Sim3OptArgs &A, int nProblems);
 
+// ---- PnPsolver's EPnP RANSAC (pnp_kernels.hip): one wave per hypothesis, four waves per workgroup, all problems in one launch; then one
+// wave per hypothesis again, of which only the records run Refine ----
+struct PnpProblemDev {              // one solver with at least one hypothesis to evaluate; device pointers
+    const float *P3D, *P2D;         // mvP3Dw n x 3, mvP2D n x 2
+    const float *maxErr;            // mvMaxError, n
+    const int *samples;             // nHyp x minSet indices into [0, n), distinct within a set (checked by the host)
+    double *hyp;                    // nHyp x 12: R row-major, t
+    int *nInliers;                  // nHyp
+    uint64_t *bits;                 // nHyp x ceil(n / 64) words (always there: k_pnp_refine reads the records' rows)
+    int *refinedN;                  // nHyp: -1 where the hypothesis is no record
+    double *refinedHyp;             // nHyp x 12, written for records
+    uint64_t *refinedBits;   // nHyp x ceil(n / 64) words (zero rows where no record); null: not wanted
+    int n, nHyp, minSet, minInliers;
+    int firstHyp;                   // the problem's first wave in the launch (ascending over the table)
+    double K[4];                    // fu fv uc vc
+};
+struct PnpArgs {
+    const PnpProblemDev *probs;
+    int nProblems, totalHyp;
+};
+void launch_pnp(hipStream_t st, const PnpArgs &A);   // k_pnp_hyp, then k_pnp_refine
+
 }  // namespace ygzf
 #endif
