@@ -879,7 +879,7 @@ int ygzf_pose_optimization(ygzf_ctx *ctx, const ygzf_camera *cam, const float *i
  * Step 2 of LoopClosing::ComputeSim3 (src/LoopClosing.cc:221-330), between SearchByBoW and SearchBySim3.  A hypothesis -- Horn's closed form
  * on three correspondences, then both projections of every correspondence against the integer gates -- depends on nothing but its triple, so
  * the hypotheses of every loop candidate are evaluated in one call; the order-dependent part of iterate (best-so-far, the strict return rule,
- * bNoMore) is replayed on the host from the counts (host/Sim3Replay.h, host/Sim3Solver.cc).  The arithmetic is fp32 with the cv::Mat
+ * bNoMore) is replayed on the host from the counts (host/Sim3Replay.h over host/RansacReplay.h, host/Sim3Solver.cc).  The arithmetic is fp32 with the cv::Mat
  * roundings of OpenCV 2.4 / 3.2 as this header fixes them above (float gemm left to right, double factor in scalar * Mat, double accumulation
  * in dot); cv::eigen is a cyclic Jacobi solver and the rotation is built from the quaternion without trigonometry (csrc/sim3_math.h,
  * restated in tests/sim3_cases.py).  A triple whose quaternion has an exactly zero imaginary part gives the reference's 0 / 0: hyp is NaN

@@ -1,7 +1,7 @@
 // PnPReplay.h -- the order-dependent part of PnPsolver (src/PnPsolver.cc:111-237), replayed on the host from what the device left behind:
-// SetRansacParameters' arithmetic, the draws of a solver's sample sets, and iterate / find over stored inlier counts, masks, poses and the
-// Refine results of the records.  Nothing of HIP or OpenCV is included, so a stand-alone host program tests it (tests/cpp/pnp_host.cc against
-// tests/pnp_cases.py: pnp_iterate).
+// how SetRansacParameters derives epsilon and minInliers, and iterate / find over stored inlier counts, masks, poses and the Refine results
+// of the records; what it shares with Sim3Solver's replay (the iteration count, the draws, the masks' bits) is host/RansacReplay.h.  Nothing
+// of HIP or OpenCV is included, so a stand-alone host program tests it (tests/cpp/pnp_host.cc against tests/pnp_cases.py: pnp_iterate).
 //
 // Refine (:239-279) always runs on mvbBestInliers, and that set changes only where a hypothesis becomes the best so far: a record.  Its
 // result is therefore a function of the record alone; every later qualifying iteration that is no record repeats the same Refine with the
@@ -9,10 +9,8 @@
 #ifndef YGZF_PNP_REPLAY_H
 #define YGZF_PNP_REPLAY_H
 #include <algorithm>
-#include <cmath>
-#include <cstddef>
-#include <cstdint>
-#include <vector>
+
+#include "RansacReplay.h"
 
 namespace ygz {
 namespace pnp {
@@ -45,46 +43,21 @@ struct Results {
     }
 };
 
-// SetRansacParameters (:111-143): -> mRansacMinInliers, mRansacMaxIts.  nMinInliers = int(N * epsilon) is a float product; epsilon is raised
-// to the float quotient minInliers / N; nIterations = ceil(log(1 - p) / log(1 - pow(epsilon, 3))) in double, 1 when minInliers == N, then
-// max(1, min(nIterations, maxIterations)).  The reference converts the quotient to int, which is undefined beyond INT_MAX and for a NaN
-// (N < minInliers: the logarithm of a negative number): the comparison is made in double here and a NaN takes maxIterations, as
-// host/Sim3Replay.h does -- iterate runs no iteration when N < minInliers.
+// SetRansacParameters (:111-143): -> mRansacMinInliers, mRansacMaxIts.  nMinInliers = int(N * epsilon) is a float product, raised to minInliers
+// and minSet; epsilon is raised to the float quotient nMinInliers / N.
 inline void ransac_parameters(int N, double probability, int minInliers, int maxIterations, int minSet, float epsilon, int &outMinInliers, int &outMaxIts) {
     int nMinInliers = (int) ((float) N * epsilon);
     if (nMinInliers < minInliers) nMinInliers = minInliers;
     if (nMinInliers < minSet) nMinInliers = minSet;
     outMinInliers = nMinInliers;
     if (epsilon < (float) nMinInliers / N) epsilon = (float) nMinInliers / N;
-    double nIterations;
-    if (nMinInliers == N)
-        nIterations = 1;
-    else
-        nIterations = std::ceil(std::log(1 - probability) / std::log(1 - std::pow((double) epsilon, 3)));
-    if (std::isnan(nIterations) || nIterations > (double) maxIterations) nIterations = (double) maxIterations;
-    if (nIterations < 1) nIterations = 1;
-    outMaxIts = (int) nIterations;
+    outMaxIts = ransac::max_iterations(epsilon, nMinInliers == N, probability, maxIterations);
 }
 
-// The sample sets of `count` iterations in the reference's draw order (:175-187): per iteration a fresh copy of mvAllIndices, minSet draws by
-// randomInt(0, size - 1), each swapped with the back and popped.  randomInt: DUtils::Random::RandomInt in the shell, a scripted generator in tests.
+// The sample sets of `count` iterations in the reference's draw order (:175-187), appended: ransac::draw_sets with minSet draws
 template <typename RandomInt> void draw_quads(int N, int minSet, int count, RandomInt &&randomInt, std::vector<int> &samples) {
-    if (N < minSet) return;
-    samples.reserve(samples.size() + (size_t) minSet * count);
-    std::vector<int> all(N), avail;
-    for (int i = 0; i < N; i++) all[i] = i;
-    for (int h = 0; h < count; h++) {
-        avail = all;
-        for (int i = 0; i < minSet; i++) {
-            const int randi = randomInt(0, (int) avail.size() - 1);
-            samples.push_back(avail[randi]);
-            avail[randi] = avail.back();
-            avail.pop_back();
-        }
-    }
+    ransac::draw_sets(N, minSet, count, randomInt, samples);
 }
-
-inline bool bit(const uint64_t *row, int i) { return (row[i >> 6] >> (i & 63)) & 1; }
 
 enum Returned { EMPTY = 0, REFINED = 1, BEST = 2 };   // what iterate hands back: cv::Mat(), mRefinedTcw, mBestTcw
 
@@ -102,8 +75,7 @@ struct Replay {
     }
     void mark(const uint64_t *row, std::vector<bool> &vbInliers) const {
         vbInliers = std::vector<bool>(nMatches, false);
-        for (int i = 0; i < N; i++)
-            if (bit(row, i)) vbInliers[keyIndices[i]] = true;
+        ransac::mark(row, N, keyIndices, vbInliers);
     }
     // -> what is returned and, in `index`, the record whose pose it is (R.refinedHyp for REFINED, R.hyp for BEST).  evaluate(h) must make
     // hypothesis h exist in R when the loop reaches it (h == R.size(): an iteration beyond what was pre-evaluated); refine(h) must fill the

@@ -12,19 +12,6 @@
 #include "PnPHost.h"
 #include "ygzf_pool.h"
 
-#ifdef YGZF_WITH_REFERENCE_HEADERS
-#include "Thirdparty/DBoW2/DUtils/Random.h"
-#else
-namespace DUtils {
-struct Random {   // Thirdparty/DBoW2/DUtils/Random.cpp:47-50
-    static int RandomInt(int min, int max) {
-        int d = max - min + 1;
-        return int(((double) rand() / ((double) RAND_MAX + 1.0)) * d) + min;
-    }
-};
-}  // namespace DUtils
-#endif
-
 static_assert(YGZF_PNP_MAX_MIN_SET == 8, "include/ygzf.h and csrc/pnp_math.h name the same limit");
 
 // The candidates of a PnPsolverBatch call from which it goes to the device.  A device call is bound by latency -- one wave runs one EPnP, and
@@ -84,7 +71,7 @@ void PnPsolver::SetRansacParameters(double probability, int minInliers, int maxI
     // it reports bNoMore with an empty matrix.
     mvSamples.clear();
     const bool usable = minSet >= 4 && minSet <= YGZF_PNP_MAX_MIN_SET && mReplay.N >= mReplay.minInliers;
-    if (usable) pnp::draw_quads(mReplay.N, minSet, mReplay.maxIts, [](int lo, int hi) { return DUtils::Random::RandomInt(lo, hi); }, mvSamples);
+    if (usable) pnp::draw_quads(mReplay.N, minSet, mReplay.maxIts, ransac::random_int, mvSamples);
     mbEvaluated = false;
     mbFailed = !(minSet >= 4 && minSet <= YGZF_PNP_MAX_MIN_SET);
     mResults.resize(mReplay.N, 0);
@@ -185,7 +172,7 @@ cv::Mat PnPsolver::iterate(int nIterations, bool &bNoMore, std::vector<bool> &vb
     const pnp::Returned kind = mReplay.iterate(nIterations, mResults,
         [&](int h) {   // an iteration beyond the pre-evaluated budget: its set is drawn now, unless SetSamples provided it
             if ((size_t) (h + 1) * (size_t) mRansacMinSet > mvSamples.size())
-                pnp::draw_quads(mReplay.N, mRansacMinSet, 1, [](int lo, int hi) { return DUtils::Random::RandomInt(lo, hi); }, mvSamples);
+                pnp::draw_quads(mReplay.N, mRansacMinSet, 1, ransac::random_int, mvSamples);
             pnp::append_hypothesis(P, &mvSamples[(size_t) h * mRansacMinSet], mResults);
         },
         [&](int h) { pnp::refine_record(P, mResults, h); }, bNoMore, vbInliers, nInliers, index);

@@ -4,23 +4,8 @@
 #include "Sim3Solver.h"
 #include "ygz_compat.h"
 
-#include <cstdlib>
-
 #include "../../../include/ygzf.h"
 #include "ygzf_pool.h"
-
-#ifdef YGZF_WITH_REFERENCE_HEADERS
-#include "Thirdparty/DBoW2/DUtils/Random.h"
-#else
-namespace DUtils {
-struct Random {   // Thirdparty/DBoW2/DUtils/Random.cpp:47-50
-    static int RandomInt(int min, int max) {
-        int d = max - min + 1;
-        return int(((double) rand() / ((double) RAND_MAX + 1.0)) * d) + min;
-    }
-};
-}  // namespace DUtils
-#endif
 
 namespace ygz {
 
@@ -68,7 +53,7 @@ void Sim3Solver::SetRansacParameters(double probability, int minInliers, int max
     mReplay.set_parameters(probability, minInliers, maxIterations);
     // the whole budget at once: iterate runs no iteration at all when N < minInliers
     const int budget = mReplay.N >= mReplay.minInliers ? mReplay.maxIts : 0;
-    sim3::draw_triples(mReplay.N, budget, [](int lo, int hi) { return DUtils::Random::RandomInt(lo, hi); }, mvSamples);
+    sim3::draw_triples(mReplay.N, budget, ransac::random_int, mvSamples);
     mbEvaluated = mbFailed = false;
     mReplay.bestIndex = -1;   // (an index into the results that are dropped here; mnBestInliers and mBestHyp stay, as the reference's members do)
 }

@@ -533,7 +533,7 @@ struct Sim3ProblemDev {             // one solver with at least one hypothesis t
     const int *samples;             // nHyp x 3 indices into [0, n), distinct within a triple (checked by the host)
     float *hyp;                     // nHyp x 13: R12 row-major, t12, s12
     int *nInliers;                  // nHyp
-    unsigned long long *bits;       // nHyp x ceil(n / 64) words, bit i of word j = correspondence 64 j + i; null: not wanted
+    uint64_t *bits;                 // nHyp x ceil(n / 64) words, bit i of word j = correspondence 64 j + i; null: not wanted
     int n, nHyp, fixScale;
     int firstHyp;                   // the problem's first wave in the launch (ascending over the table)
     float K1[4], K2[4];             // fx fy cx cy

@@ -10,13 +10,13 @@
 // updates the elements of its two rows (and of the two rows of Vt) one per lane, and every lane sums the three dot products itself in index
 // order from LDS; the 6 x k and 3 x 3 problems run on lane 0.  So every sum has the source's order and the result equals the host's bit for
 // bit.  The work area (pnp::Work, 3 KB) is each wave's own slice of static LDS: waves share nothing, so there is no workgroup barrier, only
-// the wave-level ordering of YGZF_PNP_SYNC, and no atomics.  Then lane l tests correspondences l, l + 64, ..; a ballot makes each step's 64
-// decisions one word, written by lane 0, and the count is the sum of the words' popcounts.  Every loop is bounded by an argument (n, the
-// counts) or a constant of pnp_math.h.
+// the wave-level ordering of YGZF_PNP_SYNC, and no atomics.  Then the wave counts the inliers (ransac_device.h).  Every loop is bounded by
+// an argument (n, the counts) or a constant of pnp_math.h.
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
 #include "pnp_math.h"
+#include "ransac_device.h"
 
 namespace ygzf {
 
@@ -24,30 +24,12 @@ namespace {
 
 constexpr int kPnpWaves = 4, kPnpThreads = 64 * kPnpWaves;
 
-// the problem whose hypotheses [firstHyp, firstHyp + nHyp) hold g: the last one with firstHyp <= g (problems without hypotheses are not in the table)
-__device__ inline const PnpProblemDev &problem_of(const PnpArgs &A, int g) {
-    int lo = 0, hi = A.nProblems - 1;
-    for (int it = 0; it < 32 && lo < hi; it++) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (A.probs[mid].firstHyp <= g) lo = mid; else hi = mid - 1;
-    }
-    return A.probs[lo];
-}
-
 // CheckInliers under the pose in w, and the pose itself: -> the count; row = the mask's words or null
 __device__ inline int check_inliers(const PnpProblemDev &P, const pnp::Points &Pt, const pnp::Work &w, int lane, uint64_t *row, double *out) {
     double R[9], t[3];
     for (int i = 0; i < 9; i++) R[i] = w.R[i];
     for (int i = 0; i < 3; i++) t[i] = w.t[i];
-    const int n = P.n, words = (n + 63) >> 6;
-    int count = 0;
-    for (int j = 0; j < words; j++) {
-        const int i = 64 * j + lane;
-        const bool ok = i < n && pnp::inlier(R, t, Pt, i, P.maxErr[i]);
-        const unsigned long long word = __ballot(ok);   // lanes beyond n vote 0: the tail bits of the last word are zero
-        count += __popcll(word);
-        if (lane == 0 && row) row[j] = (uint64_t) word;
-    }
+    const int count = ransac::count_inliers(P.n, lane, row, [&](int i) { return pnp::inlier(R, t, Pt, i, P.maxErr[i]); });
     if (lane < 9) out[lane] = w.R[lane];
     else if (lane < 12) out[lane] = w.t[lane - 9];
     return count;
@@ -58,7 +40,7 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_hyp(PnpArgs A) {
     const int lane = threadIdx.x & 63, wv = (int) threadIdx.x >> 6;
     const int g = (int) blockIdx.x * kPnpWaves + wv;   // wave-uniform
     if (g >= A.totalHyp) return;
-    const PnpProblemDev &P = problem_of(A, g);
+    const PnpProblemDev &P = ransac::problem_of(A.probs, A.nProblems, g);
     const int h = g - P.firstHyp;
     if (h < 0 || h >= P.nHyp) return;   // (cannot happen with the host's table; a wrong table must not turn into a stray write)
     const pnp::Points Pt = {P.P3D, P.P2D, P.K[0], P.K[1], P.K[2], P.K[3]};
@@ -75,9 +57,9 @@ __global__ __launch_bounds__(kPnpThreads) void k_pnp_refine(PnpArgs A) {
     const int lane = threadIdx.x & 63, wv = (int) threadIdx.x >> 6;
     const int g = (int) blockIdx.x * kPnpWaves + wv;
     if (g >= A.totalHyp) return;
-    const PnpProblemDev &P = problem_of(A, g);
+    const PnpProblemDev &P = ransac::problem_of(A.probs, A.nProblems, g);
     const int h = g - P.firstHyp;
-    if (h < 0 || h >= P.nHyp) return;
+    if (h < 0 || h >= P.nHyp) return;   // (cannot happen with the host's table; a wrong table must not turn into a stray write)
     const int words = (P.n + 63) >> 6;
     // a record: the count reaches min_inliers and beats every earlier count of the problem
     const int mine = P.nInliers[h];

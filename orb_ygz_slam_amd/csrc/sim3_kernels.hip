@@ -4,12 +4,12 @@
 //
 // One wave per hypothesis, four waves per workgroup; wave g of the launch takes hypothesis g of the call's concatenated list, so the waves of
 // one workgroup may belong to different problems.  Horn's closed form runs wave-uniform (every lane the same few hundred fp32 operations:
-// sim3_math.h), then lane l tests correspondences l, l + 64, ..; a ballot makes each step's 64 decisions one word, written by lane 0, and the
-// count is the sum of the words' popcounts.  Nothing is shared between waves: no LDS, no barrier, no atomics.  Every loop is bounded by an
-// argument (n, the problem count) or a constant (YGZF_SIM3_JACOBI_SWEEPS).
+// sim3_math.h), then the wave counts the inliers (ransac_device.h).  Nothing is shared between waves: no LDS, no barrier, no atomics.  Every
+// loop is bounded by an argument (n, the problem count) or a constant (YGZF_SIM3_JACOBI_SWEEPS).
 #include <hip/hip_runtime.h>
 
 #include "kernels.h"
+#include "ransac_device.h"
 #include "sim3_math.h"
 
 namespace ygzf {
@@ -22,13 +22,7 @@ __global__ __launch_bounds__(kSim3Threads) void k_sim3_ransac(Sim3Args A) {
     const int lane = threadIdx.x & 63;
     const int g = (int) blockIdx.x * kSim3Waves + ((int) threadIdx.x >> 6);   // wave-uniform
     if (g >= A.totalHyp) return;
-    // the problem whose hypotheses [firstHyp, firstHyp + nHyp) hold g: the last one with firstHyp <= g among those with nHyp > 0
-    int lo = 0, hi = A.nProblems - 1;
-    for (int it = 0; it < 32 && lo < hi; it++) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (A.probs[mid].firstHyp <= g) lo = mid; else hi = mid - 1;
-    }
-    const Sim3ProblemDev &P = A.probs[lo];
+    const Sim3ProblemDev &P = ransac::problem_of(A.probs, A.nProblems, g);
     const int h = g - P.firstHyp;
     if (h < 0 || h >= P.nHyp) return;   // (cannot happen with the host's table; a wrong table must not turn into a stray write)
     const int n = P.n;
@@ -44,18 +38,10 @@ __global__ __launch_bounds__(kSim3Threads) void k_sim3_ransac(Sim3Args A) {
     sim3::Hyp H;
     sim3::horn(p1, p2, P.fixScale != 0, H);
     const int words = (n + 63) >> 6;
-    int count = 0;
-    for (int j = 0; j < words; j++) {
-        const int i = 64 * j + lane;
-        bool ok = false;
-        if (i < n) {
-            const float X1[3] = {P.X1[3 * i], P.X1[3 * i + 1], P.X1[3 * i + 2]}, X2[3] = {P.X2[3 * i], P.X2[3 * i + 1], P.X2[3 * i + 2]};
-            ok = sim3::inlier(H, X1, X2, K1, K2, P.maxErr1[i], P.maxErr2[i]);
-        }
-        const unsigned long long word = __ballot(ok);   // lanes beyond n vote 0: the tail bits of the last word are zero
-        count += __popcll(word);
-        if (lane == 0 && P.bits) P.bits[(size_t) h * words + j] = word;
-    }
+    const int count = ransac::count_inliers(n, lane, P.bits ? P.bits + (size_t) h * words : nullptr, [&](int i) {
+        const float X1[3] = {P.X1[3 * i], P.X1[3 * i + 1], P.X1[3 * i + 2]}, X2[3] = {P.X2[3 * i], P.X2[3 * i + 1], P.X2[3 * i + 2]};
+        return sim3::inlier(H, X1, X2, K1, K2, P.maxErr1[i], P.maxErr2[i]);
+    });
     if (lane == 0) {
         float *o = P.hyp + (size_t) sim3::kHypFloats * h;
         for (int i = 0; i < 9; i++) o[i] = H.R[i];

@@ -1,6 +1,7 @@
 // ygzf_api_pose.hip -- Optimizer::PoseOptimization(Frame *), batched over frames (C ABI of libygzf, include/ygzf.h; product code: no CPU fallback,
-// nothing from oracle/ is included or linked).  The problems of one call cross the link as one packed upload and one packed download around one
-// launch of k_pose_opt (pose_kernels.hip) and one synchronisation.
+// nothing from oracle/ is included or linked).  The problems of one call cross the link as one packed upload and one packed download
+// (ProblemBlock, ygzf_ctx.h: [records | per problem keys uRight mpValid world] up, [results | per problem flags] down) around one launch of
+// k_pose_opt (pose_kernels.hip) and one synchronisation.
 #include "ygzf_ctx.h"
 
 #include <cmath>
@@ -40,63 +41,48 @@ int ygzf_pose_optimization(ygzf_ctx *c, const ygzf_camera *cam, const float *inv
     int rc;
     // any n goes: the packed transfer's device block and the per-edge scratch are grow-on-demand buffers of the context (dPack, tmp.a)
     if ((rc = ensure(c, c->tmp.a, (total + 1) * sizeof(double)))) return rc;
-    // The problems' arrays are laid out in ONE host block each way, so that a call crosses the link as one copy up and one down whatever the number
-    // of problems (beyond the page-locked staging area's limit PackedTransfer copies segment by segment: 5 copies per problem otherwise).
-    auto al = [](size_t b) { return (b + 63) & ~(size_t) 63; };
-    std::vector<size_t> oKeys(n_problems), oRight(n_problems), oValid(n_problems), oWorld(n_problems), rFlags(n_problems);
-    size_t inBytes = al((size_t) n_problems * sizeof(PoseProblemDev)), outBytes = al((size_t) n_problems * sizeof(PoseOut));
+    struct Slots { ProblemBlock::Slot keys, right, valid, world, flags; };
+    std::vector<Slots> S(n_problems);
+    ProblemBlock B(c, (size_t) n_problems * sizeof(PoseProblemDev), (size_t) n_problems * sizeof(PoseOut));
     for (int k = 0; k < n_problems; k++) {
         const size_t n = (size_t) p[k].n;
-        oKeys[k] = inBytes;  inBytes += al(n * sizeof(ygzf_kp));
-        oRight[k] = inBytes; inBytes += al(p[k].u_right ? n * sizeof(float) : 0);
-        oValid[k] = inBytes; inBytes += al(n);
-        oWorld[k] = inBytes; inBytes += al(n * 3 * sizeof(float));
-        rFlags[k] = outBytes; outBytes += al(n);   // (merged into the caller's mvbOutlier below: only correspondences are written)
+        S[k].keys = B.in(p[k].keys, n * sizeof(ygzf_kp));
+        S[k].right = B.in(p[k].u_right, n * sizeof(float));
+        S[k].valid = B.in(p[k].mp_valid, n);
+        S[k].world = B.in(p[k].mp_world, n * 3 * sizeof(float));
+        S[k].flags = B.out(nullptr, n);   // (merged into the caller's mvbOutlier below: only correspondences are written)
     }
-    std::vector<uint8_t> hin(inBytes), hout(outBytes);
-    PackedTransfer P(c);
-    const size_t oIn = P.add_in(hin.data(), inBytes);
-    const size_t rOutBlock = P.add_out(hout.data(), outBytes);
-    if ((rc = ensure(c, c->dPack, P.inBytes + P.outBytes + 256))) return rc;   // (upload() then finds the block large enough: the base is final)
-    uint8_t *base = (uint8_t *) c->dPack.p + oIn, *obase = (uint8_t *) c->dPack.p + P.inBytes + rOutBlock;
-    PoseProblemDev *probs = (PoseProblemDev *) hin.data();
+    if ((rc = B.commit())) return rc;
+    PoseProblemDev *probs = B.records<PoseProblemDev>();
     size_t at = 0;
     for (int k = 0; k < n_problems; k++) {
-        const size_t n = (size_t) p[k].n;
         PoseProblemDev &d = probs[k];
-        d.keys = (const ygzf_kp *) (base + oKeys[k]);
-        d.uRight = p[k].u_right ? (const float *) (base + oRight[k]) : nullptr;
-        d.mpValid = base + oValid[k];
-        d.world = (const float *) (base + oWorld[k]);
-        d.outlier = obase + rFlags[k];
+        d.keys = B.dev<const ygzf_kp>(S[k].keys);
+        d.uRight = p[k].u_right ? B.dev<const float>(S[k].right) : nullptr;
+        d.mpValid = B.dev<const uint8_t>(S[k].valid);
+        d.world = B.dev<const float>(S[k].world);
+        d.outlier = B.dev<uint8_t>(S[k].flags);
         d.stored = (double *) c->tmp.a.p + at;
         d.n = p[k].n;
         memcpy(d.Tcw, p[k].Tcw, sizeof d.Tcw);
-        if (n) {
-            memcpy(hin.data() + oKeys[k], p[k].keys, n * sizeof(ygzf_kp));
-            if (p[k].u_right) memcpy(hin.data() + oRight[k], p[k].u_right, n * sizeof(float));
-            memcpy(hin.data() + oValid[k], p[k].mp_valid, n);
-            memcpy(hin.data() + oWorld[k], p[k].mp_world, n * 3 * sizeof(float));
-        }
-        at += n;
+        at += (size_t) p[k].n;
     }
-    uint8_t *dIn;
-    if ((rc = P.upload(&dIn))) return rc;
+    if ((rc = B.upload())) return rc;
     PoseArgs A;
     memset(&A, 0, sizeof A);
-    A.probs = (const PoseProblemDev *) (dIn + oIn);
-    A.out = (PoseOut *) obase;
+    A.probs = B.dev_records<PoseProblemDev>();
+    A.out = B.dev_out_records<PoseOut>();
     A.fx = cam->fx; A.fy = cam->fy; A.cx = cam->cx; A.cy = cam->cy; A.bf = cam->mbf;
     A.deltaMono = (double) (float) sqrt(5.991);      // src/Optimizer.cc:1689-1690: `const float deltaMono = sqrt(5.991)`
     A.deltaStereo = (double) (float) sqrt(7.815);
     for (int l = 0; l < kMaxLevels; l++) A.invSigma2[l] = l <= maxOctave ? (inv_level_sigma2 ? inv_level_sigma2[l] : c->tab.invSigma2[l]) : 0.f;
     launch_pose_opt(c->stream, A, n_problems);
     HIPCHECK(c, hipGetLastError());
-    if ((rc = P.download())) return rc;
-    const PoseOut *outs = (const PoseOut *) hout.data();
+    if ((rc = B.download())) return rc;
+    const PoseOut *outs = B.out_records<PoseOut>();
     for (int k = 0; k < n_problems; k++) {
         const PoseOut &o = outs[k];
-        const uint8_t *flags = hout.data() + rFlags[k];
+        const uint8_t *flags = B.host(S[k].flags);
         ret[k] = o.ret;
         if (o.nInitial < 3) {   // src/Optimizer.cc:1767: nothing but mvbOutlier was touched
             memcpy(Tcw_out + 7 * (size_t) k, p[k].Tcw, 7 * sizeof(float));

@@ -1,5 +1,6 @@
 // ygzf_api_sim3.hip -- Sim3Solver's RANSAC hypotheses, batched over solvers (C ABI of libygzf, include/ygzf.h; product code: no CPU fallback,
-// nothing from oracle/ is included or linked).  The problems of one call cross the link as one packed upload and one packed download around one
+// nothing from oracle/ is included or linked).  The problems of one call cross the link as one packed upload and one packed download
+// (ProblemBlock, ygzf_ctx.h: [records | per problem X1 X2 maxErr1 maxErr2 samples] up, [per problem hyp | counts | bits] down) around one
 // launch of k_sim3_ransac (sim3_kernels.hip) and one synchronisation.
 #include "ygzf_ctx.h"
 #include "sim3_math.h"
@@ -30,74 +31,53 @@ int ygzf_sim3_ransac(ygzf_ctx *c, int n_problems, const ygzf_sim3_problem *p, fl
     if (live.empty()) return YGZF_OK;
     if (totalHyp > (1ll << 30)) return fail(c, YGZF_ERR_INVALID, "%lld hypotheses in one call", totalHyp);
     HIPCHECK(c, hipSetDevice(c->device));
-    // one host block each way, as ygzf_pose_optimization lays its problems out: [records | per problem X1 X2 maxErr1 maxErr2 samples] up,
-    // [per problem hyp | counts | bits] down
     const size_t L = live.size();
-    auto al = [](size_t b) { return (b + 63) & ~(size_t) 63; };
-    std::vector<size_t> oX1(L), oX2(L), oE1(L), oE2(L), oS(L), rHyp(L), rCnt(L), rBits(L);
-    size_t inBytes = al(L * sizeof(Sim3ProblemDev)), outBytes = 0;
+    struct Slots { ProblemBlock::Slot X1, X2, e1, e2, samples, hyp, counts, bits; };
+    std::vector<Slots> S(L);
+    ProblemBlock B(c, L * sizeof(Sim3ProblemDev));
     for (size_t j = 0; j < L; j++) {
-        const ygzf_sim3_problem &q = p[live[j]];
+        const int k = live[j];
+        const ygzf_sim3_problem &q = p[k];
         const size_t n = (size_t) q.n, nh = (size_t) q.n_hyp, words = (n + 63) / 64;
-        oX1[j] = inBytes; inBytes += al(3 * n * sizeof(float));
-        oX2[j] = inBytes; inBytes += al(3 * n * sizeof(float));
-        oE1[j] = inBytes; inBytes += al(n * sizeof(float));
-        oE2[j] = inBytes; inBytes += al(n * sizeof(float));
-        oS[j] = inBytes;  inBytes += al(3 * nh * sizeof(int));
-        rHyp[j] = outBytes; outBytes += al(nh * sim3::kHypFloats * sizeof(float));
-        rCnt[j] = outBytes; outBytes += al(nh * sizeof(int));
-        rBits[j] = outBytes;
-        if (inlier_bits && inlier_bits[live[j]]) outBytes += al(nh * words * sizeof(uint64_t));
+        uint64_t *bits = inlier_bits ? inlier_bits[k] : nullptr;
+        S[j].X1 = B.in(q.X3Dc1, 3 * n * sizeof(float));
+        S[j].X2 = B.in(q.X3Dc2, 3 * n * sizeof(float));
+        S[j].e1 = B.in(q.max_err1, n * sizeof(float));
+        S[j].e2 = B.in(q.max_err2, n * sizeof(float));
+        S[j].samples = B.in(q.samples, 3 * nh * sizeof(int));
+        S[j].hyp = B.out(hyp[k], nh * sim3::kHypFloats * sizeof(float));
+        S[j].counts = B.out(n_inliers[k], nh * sizeof(int));
+        S[j].bits = B.out(bits, bits ? nh * words * sizeof(uint64_t) : 0);
     }
-    std::vector<uint8_t> hin(inBytes), hout(outBytes);
-    PackedTransfer P(c);
-    const size_t oIn = P.add_in(hin.data(), inBytes);
-    const size_t rOutBlock = P.add_out(hout.data(), outBytes);
     int rc;
-    if ((rc = ensure(c, c->dPack, P.inBytes + P.outBytes + 256))) return rc;   // (upload() then finds the block large enough: the base is final)
-    uint8_t *base = (uint8_t *) c->dPack.p + oIn, *obase = (uint8_t *) c->dPack.p + P.inBytes + rOutBlock;
-    Sim3ProblemDev *probs = (Sim3ProblemDev *) hin.data();
+    if ((rc = B.commit())) return rc;
+    Sim3ProblemDev *probs = B.records<Sim3ProblemDev>();
     int first = 0;
     for (size_t j = 0; j < L; j++) {
         const ygzf_sim3_problem &q = p[live[j]];
-        const size_t n = (size_t) q.n, nh = (size_t) q.n_hyp;
         Sim3ProblemDev &d = probs[j];
-        d.X1 = (const float *) (base + oX1[j]);
-        d.X2 = (const float *) (base + oX2[j]);
-        d.maxErr1 = (const float *) (base + oE1[j]);
-        d.maxErr2 = (const float *) (base + oE2[j]);
-        d.samples = (const int *) (base + oS[j]);
-        d.hyp = (float *) (obase + rHyp[j]);
-        d.nInliers = (int *) (obase + rCnt[j]);
-        d.bits = inlier_bits && inlier_bits[live[j]] ? (unsigned long long *) (obase + rBits[j]) : nullptr;
+        d.X1 = B.dev<const float>(S[j].X1);
+        d.X2 = B.dev<const float>(S[j].X2);
+        d.maxErr1 = B.dev<const float>(S[j].e1);
+        d.maxErr2 = B.dev<const float>(S[j].e2);
+        d.samples = B.dev<const int>(S[j].samples);
+        d.hyp = B.dev<float>(S[j].hyp);
+        d.nInliers = B.dev<int>(S[j].counts);
+        d.bits = S[j].bits.bytes ? B.dev<uint64_t>(S[j].bits) : nullptr;
         d.n = q.n; d.nHyp = q.n_hyp; d.fixScale = q.fix_scale ? 1 : 0;
         d.firstHyp = first;
         first += q.n_hyp;
         memcpy(d.K1, q.K1, sizeof d.K1);
         memcpy(d.K2, q.K2, sizeof d.K2);
-        memcpy(hin.data() + oX1[j], q.X3Dc1, 3 * n * sizeof(float));
-        memcpy(hin.data() + oX2[j], q.X3Dc2, 3 * n * sizeof(float));
-        memcpy(hin.data() + oE1[j], q.max_err1, n * sizeof(float));
-        memcpy(hin.data() + oE2[j], q.max_err2, n * sizeof(float));
-        memcpy(hin.data() + oS[j], q.samples, 3 * nh * sizeof(int));
     }
-    uint8_t *dIn;
-    if ((rc = P.upload(&dIn))) return rc;
+    if ((rc = B.upload())) return rc;
     Sim3Args A;
-    A.probs = (const Sim3ProblemDev *) (dIn + oIn);
+    A.probs = B.dev_records<Sim3ProblemDev>();
     A.nProblems = (int) L;
     A.totalHyp = (int) totalHyp;
     launch_sim3_ransac(c->stream, A);
     HIPCHECK(c, hipGetLastError());
-    if ((rc = P.download())) return rc;
-    for (size_t j = 0; j < L; j++) {
-        const int k = live[j];
-        const size_t n = (size_t) p[k].n, nh = (size_t) p[k].n_hyp, words = (n + 63) / 64;
-        memcpy(hyp[k], hout.data() + rHyp[j], nh * sim3::kHypFloats * sizeof(float));
-        memcpy(n_inliers[k], hout.data() + rCnt[j], nh * sizeof(int));
-        if (inlier_bits && inlier_bits[k]) memcpy(inlier_bits[k], hout.data() + rBits[j], nh * words * sizeof(uint64_t));
-    }
-    return YGZF_OK;
+    return B.download();
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // ygzf_api_sim3_opt.hip -- Optimizer::OptimizeSim3, batched over loop candidates (C ABI of libygzf, include/ygzf.h; product code: no CPU
 // fallback, nothing from oracle/ is included or linked).  The problems of one call cross the link as one packed upload and one packed download
-// around one launch of k_sim3_opt (sim3_opt_kernels.hip) and one synchronisation.
+// (ProblemBlock, ygzf_ctx.h: [records | per problem one segment of floats] up, [results | per problem flags] down) around one launch of
+// k_sim3_opt (sim3_opt_kernels.hip) and one synchronisation.
 #include "ygzf_ctx.h"
 
 #include <cmath>
@@ -24,34 +25,27 @@ int ygzf_optimize_sim3(ygzf_ctx *c, int n_problems, const ygzf_sim3_opt_problem 
     int rc;
     // any n goes: the packed transfer's device block and the per-edge scratch are grow-on-demand buffers of the context (dPack, tmp.a)
     if ((rc = ensure(c, c->tmp.a, (2 * total + 1) * sizeof(double)))) return rc;
-    auto al = [](size_t b) { return (b + 63) & ~(size_t) 63; };
     // per problem one segment of floats: P1c[3n] P2c[3n] obs1[2n] obs2[2n] inv_sigma2_1[n] inv_sigma2_2[n]
-    std::vector<size_t> oIn(n_problems), rFlags(n_problems);
-    size_t inBytes = al((size_t) n_problems * sizeof(Sim3OptProblemDev)), outBytes = al((size_t) n_problems * sizeof(Sim3OptOut));
+    struct Slots { ProblemBlock::Slot seg, flags; };
+    std::vector<Slots> S(n_problems);
+    ProblemBlock B(c, (size_t) n_problems * sizeof(Sim3OptProblemDev), (size_t) n_problems * sizeof(Sim3OptOut));
     for (int k = 0; k < n_problems; k++) {
-        const size_t n = (size_t) p[k].n;
-        oIn[k] = inBytes;     inBytes += al(12 * n * sizeof(float));
-        rFlags[k] = outBytes; outBytes += al(n);
+        S[k].seg = B.in_own(12 * (size_t) p[k].n * sizeof(float));
+        S[k].flags = B.out(removed[k], (size_t) p[k].n);
     }
-    std::vector<uint8_t> hin(inBytes), hout(outBytes);
-    PackedTransfer P(c);
-    const size_t oBlock = P.add_in(hin.data(), inBytes);
-    const size_t rBlock = P.add_out(hout.data(), outBytes);
-    if ((rc = ensure(c, c->dPack, P.inBytes + P.outBytes + 256))) return rc;   // (upload() then finds the block large enough: the base is final)
-    uint8_t *base = (uint8_t *) c->dPack.p + oBlock, *obase = (uint8_t *) c->dPack.p + P.inBytes + rBlock;
-    Sim3OptProblemDev *probs = (Sim3OptProblemDev *) hin.data();
+    if ((rc = B.commit())) return rc;
+    Sim3OptProblemDev *probs = B.records<Sim3OptProblemDev>();
     size_t at = 0;
     for (int k = 0; k < n_problems; k++) {
         const ygzf_sim3_opt_problem &q = p[k];
         const size_t n = (size_t) q.n;
         Sim3OptProblemDev &d = probs[k];
-        memset(&d, 0, sizeof d);
-        const float *seg = (const float *) (base + oIn[k]);
-        float *h = (float *) (hin.data() + oIn[k]);
+        const float *seg = B.dev<const float>(S[k].seg);
+        float *h = (float *) B.host(S[k].seg);
         d.P1c = seg;               d.P2c = seg + 3 * n;
         d.obs1 = seg + 6 * n;      d.obs2 = seg + 8 * n;
         d.invSigma2_1 = seg + 10 * n; d.invSigma2_2 = seg + 11 * n;
-        d.removed = obase + rFlags[k];
+        d.removed = B.dev<uint8_t>(S[k].flags);
         d.stored = (double *) c->tmp.a.p + 2 * at;
         d.n = q.n;
         d.fixScale = q.fix_scale ? 1 : 0;
@@ -66,20 +60,18 @@ int ygzf_optimize_sim3(ygzf_ctx *c, int n_problems, const ygzf_sim3_opt_problem 
         }
         at += n;
     }
-    uint8_t *dIn;
-    if ((rc = P.upload(&dIn))) return rc;
+    if ((rc = B.upload())) return rc;
     Sim3OptArgs A;
-    A.probs = (const Sim3OptProblemDev *) (dIn + oBlock);
-    A.out = (Sim3OptOut *) obase;
+    A.probs = B.dev_records<Sim3OptProblemDev>();
+    A.out = B.dev_out_records<Sim3OptOut>();
     launch_sim3_opt(c->stream, A, n_problems);
     HIPCHECK(c, hipGetLastError());
-    if ((rc = P.download())) return rc;
-    const Sim3OptOut *outs = (const Sim3OptOut *) hout.data();
+    if ((rc = B.download())) return rc;
+    const Sim3OptOut *outs = B.out_records<Sim3OptOut>();
     for (int k = 0; k < n_problems; k++) {
         const Sim3OptOut &o = outs[k];
         ret[k] = o.ret;
         memcpy(S12_out + 8 * (size_t) k, o.S, 8 * sizeof(double));   // (S12 itself, bit for bit, where g2oS12 is not written)
-        if (p[k].n) memcpy(removed[k], hout.data() + rFlags[k], (size_t) p[k].n);
         if (info) {
             ygzf_sim3_opt_info &f = info[k];
             for (int r = 0; r < 2; r++) {

@@ -400,6 +400,7 @@ struct PackedTransfer {
     struct Seg { const void *src; void *dst; size_t bytes, off; };
     std::vector<Seg> in, out;
     size_t inBytes = 0, outBytes = 0;
+    size_t deviceOnly = 0;   // bytes behind the outputs that live in dPack alone: never staged, never downloaded
     explicit PackedTransfer(ygzf_ctx *c_) : c(c_) {}
     static size_t al(size_t b) { return (b + 255) & ~(size_t) 255; }
     size_t add_in(const void *src, size_t bytes) { const size_t o = inBytes; in.push_back({src, nullptr, bytes, o}); inBytes += al(bytes); return o; }
@@ -410,9 +411,11 @@ struct PackedTransfer {
     bool direct() const { return inBytes + outBytes > kPackedMax; }
     // the packed blocks cross the link by a kernel (the staging area as the device addresses it) unless YGZF_FORCE=fetch_kernel=0
     bool link_kernel() const { return c->hStageDev != nullptr && c->linkKernels; }
+    // what the transfer needs of dPack.  dPack only grows, and upload() asks for exactly this: once dPack holds it, its base is the transfer's
+    size_t device_bytes() const { return inBytes + outBytes + deviceOnly + 256; }
     int upload(uint8_t **dBase) {
         int rc;
-        if ((rc = ensure(c, c->dPack, inBytes + outBytes + 256))) return rc;
+        if ((rc = ensure(c, c->dPack, device_bytes()))) return rc;
         if (direct()) {
             for (const Seg &s : in)
                 if (s.bytes) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->dPack.p + s.off, s.src, s.bytes, hipMemcpyHostToDevice, c->stream));
@@ -441,6 +444,67 @@ struct PackedTransfer {
             if (s.bytes && s.dst) memcpy(s.dst, c->hStage + inBytes + s.off, s.bytes);
         return YGZF_OK;
     }
+};
+
+// The batched solvers (ygzf_api_pose / _sim3 / _sim3_opt / _pnp.hip) lay the problems of one call out in ONE host block each way, so that a call
+// crosses the link as one copy up and one down whatever the number of problems (beyond kPackedMax PackedTransfer copies segment by segment: one
+// segment each way here, several copies per problem otherwise):
+//   up [records | the callers' arrays]     down [result records | result arrays]     behind it, on the device only [arrays nobody downloads]
+// Every array starts on a 64-byte boundary of its part.  Use: reserve the slots; commit(), after which dev() is final; fill the records;
+// upload(); launch; download(), which scatters every output slot that has a destination.
+struct ProblemBlock {
+    enum Part { Up, Down, DeviceOnly };
+    struct Slot { Part part = Up; size_t off = 0, bytes = 0; };
+    ProblemBlock(ygzf_ctx *c, size_t recordBytes, size_t outRecordBytes = 0) : P(c), size{al(recordBytes), al(outRecordBytes), 0} {}
+    Slot in(const void *src, size_t bytes) { return reserve(Up, src ? bytes : 0, src, nullptr); }   // a caller's array; null or empty: an empty slot
+    Slot in_own(size_t bytes) { return reserve(Up, bytes, nullptr, nullptr); }                      // filled by the caller through host()
+    Slot out(void *dst, size_t bytes) { return reserve(Down, bytes, nullptr, dst); }                // dst null: downloaded, read through host()
+    Slot device_only(size_t bytes) { return reserve(DeviceOnly, bytes, nullptr, nullptr); }
+    int commit() {
+        block[Up].assign(size[Up], 0);
+        block[Down].assign(size[Down], 0);
+        P.add_in(block[Up].data(), size[Up]);   // one segment each way, at offset 0 of its side
+        P.add_out(block[Down].data(), size[Down]);
+        P.deviceOnly = size[DeviceOnly];
+        int rc;
+        if ((rc = ensure(P.c, P.c->dPack, P.device_bytes()))) return rc;
+        base[Up] = (uint8_t *) P.c->dPack.p;
+        base[Down] = P.d_out(0);
+        base[DeviceOnly] = base[Down] + size[Down];
+        for (const Copy &k : copies)
+            if (k.src) memcpy(host(k.at), k.src, k.at.bytes);
+        return YGZF_OK;
+    }
+    template <typename T> T *dev(const Slot &s) const { return (T *) (base[s.part] + s.off); }
+    uint8_t *host(const Slot &s) { return block[s.part].data() + s.off; }   // Up: before upload(); Down: after download()
+    // the record tables at the start of the two blocks, as the host and as the device address them
+    template <typename T> T *records() { return (T *) block[Up].data(); }
+    template <typename T> const T *dev_records() const { return (const T *) base[Up]; }
+    template <typename T> const T *out_records() const { return (const T *) block[Down].data(); }
+    template <typename T> T *dev_out_records() const { return (T *) base[Down]; }
+    int upload() { uint8_t *d; return P.upload(&d); }
+    int download() {
+        int rc;
+        if ((rc = P.download())) return rc;
+        for (const Copy &k : copies)
+            if (k.dst) memcpy(k.dst, host(k.at), k.at.bytes);
+        return YGZF_OK;
+    }
+
+private:
+    static size_t al(size_t b) { return (b + 63) & ~(size_t) 63; }
+    struct Copy { const void *src; void *dst; Slot at; };
+    Slot reserve(Part part, size_t bytes, const void *src, void *dst) {
+        const Slot s = {part, size[part], bytes};
+        size[part] += al(bytes);
+        if (bytes && (src || dst)) copies.push_back({src, dst, s});
+        return s;
+    }
+    PackedTransfer P;
+    size_t size[3];
+    std::vector<uint8_t> block[2];
+    uint8_t *base[3] = {nullptr, nullptr, nullptr};
+    std::vector<Copy> copies;
 };
 
 // ---- per-kernel event bracketing ------------------------------------------------------------------------------------

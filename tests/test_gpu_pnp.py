@@ -266,3 +266,21 @@ def test_shell_below_the_device_threshold(ex, tmp_path):
     """with the default ygzf_host_pnp_device_min a batch of three pre-evaluates nothing: every iteration is evaluated when it is reached, on
     the calling thread, and every return is the same"""
     _run_shell(tmp_path, ["groups_a_then_b", "overrun", "refine_exact_min", "scene_n60"], flags=())
+
+
+def test_solver_blocks_beyond_packed_max_bypass_the_staging():
+    """The four batched solvers lay a call's problems out as one block each way (ProblemBlock, csrc/ygzf_ctx.h).  Beyond kPackedMax the blocks
+    cross without the page-locked staging area, one copy each way from / to the block itself (PackedTransfer::direct).  With
+    YGZF_FORCE=packed_max=4096 the small batches of the four suites take that path: n = 0, 1, 2, 3, 63, 64, 65, problems without hypotheses,
+    a problem above 4096 bytes beside one below, and PnP's masks as a device-only tail (test_without_inlier_bits).  They must hold unchanged.
+    The child (20 tests) took 2.4 and 2.8 s in two sessions on an MI355X at the commit before ProblemBlock, interpreter start included; the
+    timeout is ten times that and more, a backstop against a hang and no speed assertion."""
+    import sys
+    from orb_ygz_slam_amd.capi import force_env
+    env = dict(os.environ, YGZF_FORCE=force_env(packed_max=4096))
+    files = [os.path.join(ROOT, "tests", "test_gpu_%s.py" % s) for s in ("pose_opt", "sim3_opt", "sim3", "pnp")]
+    out = subprocess.run([sys.executable, "-m", "pytest", "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider"] + files +
+                         ["-k", "(test_batches or test_mixed_batches or test_without_inlier_bits) and not beyond_packed_max"],
+                         cwd=ROOT, env=env, capture_output=True, text=True, timeout=30)
+    assert out.returncode == 0, out.stdout[-3000:] + out.stderr[-2000:]
+    assert " passed" in out.stdout and "skipped" not in out.stdout, out.stdout[-1000:]
