@@ -990,6 +990,46 @@ typedef struct ygzf_pnp_problem {
 int ygzf_pnp_ransac(ygzf_ctx *ctx, int n_problems, const ygzf_pnp_problem *problems, double *const *hyp, int *const *n_inliers,
                     uint64_t *const *inlier_bits, int *const *refined_n, double *const *refined_hyp, uint64_t *const *refined_bits);
 
+/* ---- LocalMapping::CreateNewMapPoints, the per-pair body   src/LocalMapping.cc:1060-1194, with KeyFrame::UnprojectStereo src/KeyFrame.cc:815-828 ---
+ * What the mapping thread does with every pair ygzf_search_for_triangulation returned: the two rays and the parallax test, the linear
+ * triangulation (Eigen::JacobiSVD<Matrix4f>) or UnprojectStereo, the two depth signs, the two reprojection gates, the scale-consistency gate.
+ * A pair depends on nothing but itself, so the pairs of every neighbour (problem) of the current keyframe kf1 are evaluated in one call; the
+ * map updates of :1197-1214 stay with the caller, in the reference's order (orb_ygz_slam_amd/csrc/host/TriangulateApply.h).
+ *
+ * The arithmetic is fp32 in the source's order, stated once in csrc/tri_math.h and restated in tests/triangulate_cases.py; the device equals both bit
+ * for bit.  The keys are the DISTORTED mvKeys (:1068); KF2's right-eye term uses kf1's mbf (:1168).  cos_stereo[i] is the reference's
+ * cos(2 * atan2(mb / 2, mvDepth[i])) -- cosf(2 * atan2f(mb / 2, depth)) at the widths overload resolution gives it there -- computed by the
+ * caller once per keyframe; it is read only where u_right[i] >= 0.  JacobiSVD is fixed in tri_math.h as Eigen 3.3's two-sided Jacobi; parity with
+ * a compiled Eigen is unpinned, and a pair whose SVD meets YGZF_TRI_MAX_SWEEPS sweeps is rejected with a status of its own.
+ *
+ * Per problem k: x3d[k] (n_pairs x 3 floats; defined for every pair, of use where the pair was accepted) and status[k] (n_pairs bytes):
+ *   low 4 bits   0 accepted; else the `continue` that took the pair, in the source's order: 1 low parallax without stereo (:1117),
+ *                2 V(3,3) == 0, 3 z1 <= 0, 4 z2 <= 0, 5 reprojection in KF1, 6 reprojection in KF2, 7 a zero distance, 8 the scale ratio,
+ *                9 the sweep cap;
+ *   bits 6-7     where x3D came from: 0 nowhere (status 1), 1 the SVD, 2 kf1's UnprojectStereo, 3 kf2's.
+ * One upload, one launch, one download and one synchronisation whatever the number of problems; the arrays of a keyframe that several
+ * problems name (equal pointers) cross once.  A problem with n_pairs == 0 is legal and nothing of it is read or written.  The call uses
+ * scratch buffers only: a context in the middle of a batch keeps its state.
+ * YGZF_ERR_INVALID: a NULL argument or array (u_right without depth or cos_stereo included), n_problems <= 0, n_pairs < 0, an index outside
+ * [0, view.n), a keypoint octave outside [0, nlevels). */
+typedef struct ygzf_tri_kf {
+    ygzf_frame_view view;          /* mvKeys, mvuRight (NULL: monocular), mvScaleFactors (NULL: the context's tables), nlevels; desc is not read */
+    ygzf_camera cam;               /* fx fy cx cy mb mbf; the bounds are not read */
+    float invfx, invfy;            /* as the keyframe holds them */
+    const float *level_sigma2;     /* mvLevelSigma2 (NULL: scale factor squared, as ygzf_search_for_triangulation) */
+    const float *depth;            /* mvDepth, NULL: monocular */
+    const float *cos_stereo;       /* per feature, see above; NULL: monocular */
+    float Rcw[9], tcw[3], Ow[3];   /* GetRotation / GetTranslation / GetCameraCenter, row-major */
+    float Twc_q[4], Twc_t[3];      /* Twc as the keyframe holds it (Sophus SE3f): unit quaternion x y z w, translation */
+} ygzf_tri_kf;
+typedef struct ygzf_tri_problem {
+    ygzf_tri_kf kf2;
+    int n_pairs;
+    const int *idx1, *idx2;        /* vMatchedIndices[i].first / .second */
+} ygzf_tri_problem;
+int ygzf_triangulate_pairs(ygzf_ctx *ctx, const ygzf_tri_kf *kf1, float ratio_factor, int n_problems, const ygzf_tri_problem *problems,
+                           float *const *x3d, uint8_t *const *status);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,8 +7,8 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRCS = ["csrc/extract_kernels.hip", "csrc/match_kernels.hip", "csrc/align_kernels.hip", "csrc/fast10_kernels.hip", "csrc/dso_kernels.hip", "csrc/stereo_kernels.hip", "csrc/direct_kernels.hip", "csrc/kfdb_kernels.hip", "csrc/kfstore_kernels.hip", "csrc/remap_kernels.hip", "csrc/pose_kernels.hip", "csrc/sim3_kernels.hip", "csrc/sim3_opt_kernels.hip", "csrc/pnp_kernels.hip", "csrc/ygzf_plan.hip", "csrc/ygzf_remap_plan.hip", "csrc/ygzf_api.hip", "csrc/ygzf_api_match.hip", "csrc/ygzf_api_align.hip", "csrc/ygzf_api_detect.hip",
-        "csrc/ygzf_api_stereo.hip", "csrc/ygzf_api_kfdb.hip", "csrc/ygzf_api_kfstore.hip", "csrc/ygzf_api_remap.hip", "csrc/ygzf_api_pose.hip", "csrc/ygzf_api_sim3.hip", "csrc/ygzf_api_sim3_opt.hip", "csrc/ygzf_api_pnp.hip", "csrc/ygzf_mgpu.hip"]
+SRCS = ["csrc/extract_kernels.hip", "csrc/match_kernels.hip", "csrc/align_kernels.hip", "csrc/fast10_kernels.hip", "csrc/dso_kernels.hip", "csrc/stereo_kernels.hip", "csrc/direct_kernels.hip", "csrc/kfdb_kernels.hip", "csrc/kfstore_kernels.hip", "csrc/remap_kernels.hip", "csrc/pose_kernels.hip", "csrc/sim3_kernels.hip", "csrc/sim3_opt_kernels.hip", "csrc/pnp_kernels.hip", "csrc/tri_kernels.hip", "csrc/ygzf_plan.hip", "csrc/ygzf_remap_plan.hip", "csrc/ygzf_api.hip", "csrc/ygzf_api_match.hip", "csrc/ygzf_api_align.hip", "csrc/ygzf_api_detect.hip",
+        "csrc/ygzf_api_stereo.hip", "csrc/ygzf_api_kfdb.hip", "csrc/ygzf_api_kfstore.hip", "csrc/ygzf_api_remap.hip", "csrc/ygzf_api_pose.hip", "csrc/ygzf_api_sim3.hip", "csrc/ygzf_api_sim3_opt.hip", "csrc/ygzf_api_pnp.hip", "csrc/ygzf_api_tri.hip", "csrc/ygzf_mgpu.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
          "-ffp-contract=off",                               # bit-exact float paths: no FMA contraction
          "-fhip-fp32-correctly-rounded-divide-sqrt",        # IEEE division in fastAtan2
@@ -19,8 +19,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC",
 # survives a change of FLAGS).  k_sim3_ransac's fp32 operations must each round as tests/sim3_cases.py repeats them, bit for bit: the same.
 # k_sim3_opt's numeric Jacobian is a dither of float roundings (csrc/sim3_opt_math.h): one contracted product would move entries by thousands.
 # k_pnp_hyp / k_pnp_refine: EPnP's null-space basis is decided by rounding (csrc/pnp_math.h), so one contracted product is another pose.
+# k_triangulate: the gates of csrc/tri_math.h are met with equality in tests/triangulate_cases.py, and the Jacobi SVD's stop rule reads single roundings.
 FILE_FLAGS = {"csrc/align_kernels.hip": ["-fno-slp-vectorize"], "csrc/pose_kernels.hip": ["-ffp-contract=off"], "csrc/sim3_kernels.hip": ["-ffp-contract=off"],
-              "csrc/sim3_opt_kernels.hip": ["-ffp-contract=off"], "csrc/pnp_kernels.hip": ["-ffp-contract=off"]}
+              "csrc/sim3_opt_kernels.hip": ["-ffp-contract=off"], "csrc/pnp_kernels.hip": ["-ffp-contract=off"], "csrc/tri_kernels.hip": ["-ffp-contract=off"]}
 
 
 def hipcc():

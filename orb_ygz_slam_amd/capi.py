@@ -97,6 +97,20 @@ class PnpProblem(C.Structure):   # ygzf_pnp_problem
                 ("min_inliers", C.c_int), ("n_hyp", C.c_int), ("samples", C.c_void_p)]
 
 
+class TriKf(C.Structure):   # ygzf_tri_kf
+    _fields_ = [("view", FrameView), ("cam", Camera), ("invfx", C.c_float), ("invfy", C.c_float), ("level_sigma2", C.c_void_p), ("depth", C.c_void_p),
+                ("cos_stereo", C.c_void_p), ("Rcw", C.c_float * 9), ("tcw", C.c_float * 3), ("Ow", C.c_float * 3), ("Twc_q", C.c_float * 4),
+                ("Twc_t", C.c_float * 3)]
+
+
+class TriProblem(C.Structure):   # ygzf_tri_problem
+    _fields_ = [("kf2", TriKf), ("n_pairs", C.c_int), ("idx1", C.c_void_p), ("idx2", C.c_void_p)]
+
+
+TRI_STATUS_MASK, TRI_FROM_SHIFT = 15, 6   # the status byte of ygzf_triangulate_pairs: low bits the gate, bits 6-7 the source of x3D
+TRI_FROM_NONE, TRI_FROM_SVD, TRI_FROM_KF1, TRI_FROM_KF2 = range(4)
+
+
 class Sim3OptProblem(C.Structure):   # ygzf_sim3_opt_problem
     _fields_ = [("n", C.c_int), ("P1c", C.c_void_p), ("P2c", C.c_void_p), ("obs1", C.c_void_p), ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p),
                 ("inv_sigma2_2", C.c_void_p), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("S12", C.c_double * 8), ("th2", C.c_float), ("fix_scale", C.c_int)]
@@ -292,6 +306,7 @@ def load_library(build_if_missing=True):
     L.ygzf_sim3_ransac.argtypes = [vp, C.c_int, C.POINTER(Sim3Problem), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.ygzf_optimize_sim3.argtypes = [vp, C.c_int, C.POINTER(Sim3OptProblem), vp, C.POINTER(vp), vp, C.POINTER(Sim3OptInfo)]
     L.ygzf_pnp_ransac.argtypes = [vp, C.c_int, C.POINTER(PnpProblem)] + [C.POINTER(vp)] * 6
+    L.ygzf_triangulate_pairs.argtypes = [vp, C.POINTER(TriKf), C.c_float, C.c_int, C.POINTER(TriProblem), C.POINTER(vp), C.POINTER(vp)]
     L.ygzf_stream.argtypes = [vp]
     L.ygzf_stream.restype = vp
     _lib = L
@@ -1277,6 +1292,46 @@ class Extractor:
         arr = lambda key: (C.c_void_p * max(B, 1))(*[o[key].ctypes.data for o in out])
         self._ck(self.L.ygzf_pnp_ransac(self.h, B, recs, arr("hyp"), arr("n_inliers"), arr("bits") if want_bits else None, arr("refined_n"),
                                         arr("refined_hyp"), arr("refined_bits") if want_bits else None))
+        return out
+
+    def _tri_kf(self, kf, keep, cache):
+        """kf: dict with keys (KP_DTYPE), cam (Camera), invfx / invfy (None: the float quotients 1 / fx, 1 / fy), u_right / depth / cos_stereo
+        (None: monocular), scale_factors / level_sigma2 (None: the context's tables), Rcw, tcw, Ow, Twc_q (x y z w), Twc_t.  One dict object
+        passed twice names the same arrays both times."""
+        if id(kf) not in cache:
+            opt = lambda key, dt: None if kf.get(key) is None else np.ascontiguousarray(kf[key], dt)
+            cache[id(kf)] = (np.ascontiguousarray(kf["keys"], KP_DTYPE),) + tuple(opt(key, np.float32) for key in ("u_right", "depth", "cos_stereo", "scale_factors", "level_sigma2"))
+            keep.append(cache[id(kf)])
+        keys, u, dp, cs, sf, sg = cache[id(kf)]
+        a = lambda x: None if x is None else x.ctypes.data
+        f = TriKf()
+        f.view = FrameView(len(keys), keys.ctypes.data, None, a(u), a(sf), self.nlevels if sf is None else len(sf))
+        f.cam = kf["cam"]
+        f.invfx = np.float32(1) / np.float32(f.cam.fx) if kf.get("invfx") is None else float(kf["invfx"])
+        f.invfy = np.float32(1) / np.float32(f.cam.fy) if kf.get("invfy") is None else float(kf["invfy"])
+        f.level_sigma2, f.depth, f.cos_stereo = a(sg), a(dp), a(cs)
+        for name, size in (("Rcw", 9), ("tcw", 3), ("Ow", 3), ("Twc_q", 4), ("Twc_t", 3)):
+            getattr(f, name)[:] = [float(x) for x in np.asarray(kf[name], np.float32).reshape(size)]
+        return f
+
+    def triangulate_pairs(self, kf1, ratio_factor, problems):
+        """The per-pair body of LocalMapping::CreateNewMapPoints over the pairs of every neighbour in one call (ygzf_triangulate_pairs).  kf1 and
+        each problem's "kf2": keyframe dicts (see _tri_kf); problems: dicts with kf2, idx1, idx2.  -> list of (x3d n_pairs x 3 float32, status
+        n_pairs uint8: low 4 bits the gate that took the pair (0 accepted), bits 6-7 the source of x3D)."""
+        B = len(problems)
+        keep, cache, out = [], {}, []
+        recs = (TriProblem * max(B, 1))()
+        k1 = self._tri_kf(kf1, keep, cache)
+        for k, q in enumerate(problems):
+            i1, i2 = (np.ascontiguousarray(q[key], np.int32).reshape(-1) for key in ("idx1", "idx2"))
+            assert len(i1) == len(i2)
+            keep += [i1, i2]
+            recs[k].kf2 = self._tri_kf(q["kf2"], keep, cache)
+            recs[k].n_pairs, recs[k].idx1, recs[k].idx2 = len(i1), i1.ctypes.data, i2.ctypes.data
+            out.append((np.zeros((len(i1), 3), np.float32), np.full(len(i1), 255, np.uint8)))
+        xp = (C.c_void_p * max(B, 1))(*[o[0].ctypes.data for o in out])
+        sp = (C.c_void_p * max(B, 1))(*[o[1].ctypes.data for o in out])
+        self._ck(self.L.ygzf_triangulate_pairs(self.h, C.byref(k1), float(ratio_factor), B, recs, xp, sp))
         return out
 
     def optimize_sim3(self, problems):

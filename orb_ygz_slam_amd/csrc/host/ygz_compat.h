@@ -136,8 +136,14 @@ struct SE3f {  // Sophus::SE3f storage: unit quaternion (x,y,z,w) + translation
 };
 class Frame;
 class ORBextractor;
+class Map;
 class MapPoint {  // the accessors the hot path calls (reference include/MapPoint.h)
 public:
+    MapPoint() = default;
+    inline MapPoint(const Vector3f &Pos, KeyFrame *pRefKF, Map *pMap);   // src/MapPoint.cc:32-39 (LocalMapping::CreateNewMapPoints)
+    KeyFrame *mpRefKF = nullptr;
+    Map *mpMap = nullptr;
+    inline void UpdateNormalAndDepth();                                   // :291-331
     Vector3f mWorldPos{};
     cv::Mat mDescriptor;
     int nObs = 1;
@@ -231,6 +237,21 @@ public:
     Matrix3f GetRotation() const { return mRcw; }
     Vector3f GetTranslation() const { return mtcw; }
     Vector3f GetCameraCenter() const { return mOw; }
+    // read by LocalMapping::CreateNewMapPoints (src/LocalMapping.cc:978-1217; include/KeyFrame.h:289-345)
+    float mb = 0, invfx = 0, invfy = 0, mfScaleFactor = 0;
+    std::vector<float> mvDepth;
+    SE3f Twc;
+    SE3f GetPoseInverse() const { return Twc; }
+    float ComputeSceneMedianDepth(const int q) const {                                          // src/KeyFrame.cc:830-857
+        std::vector<float> vDepths;
+        for (int i = 0; i < N; i++)
+            if (mvpMapPoints[i]) {
+                const Vector3f x = mvpMapPoints[i]->GetWorldPos();
+                vDepths.push_back((mRcw(2, 0) * x[0] + mRcw(2, 1) * x[1]) + mRcw(2, 2) * x[2] + mtcw[2]);
+            }
+        std::sort(vDepths.begin(), vDepths.end());
+        return vDepths[(vDepths.size() - 1) / q];
+    }
     // read and written by ORBmatcher::Fuse(KeyFrame*, MapPoints, th) (src/ORBmatcher.cc:748-886; include/KeyFrame.h:289-317)
     float mbf = 0;
     int mnScaleLevels = 0;
@@ -266,6 +287,36 @@ public:
         return std::vector<KeyFrame *>(mvpOrderedConnectedKeyFrames.begin(), mvpOrderedConnectedKeyFrames.begin() + N);
     }
 };
+class Map {  // include/Map.h: what CreateNewMapPoints touches
+public:
+    std::set<MapPoint *> mspMapPoints;
+    long unsigned int nNextPointId = 0;   // (MapPoint::nNextId in the reference)
+    void AddMapPoint(MapPoint *pMP) { mspMapPoints.insert(pMP); }
+};
+inline MapPoint::MapPoint(const Vector3f &Pos, KeyFrame *pRefKF, Map *pMap) : mpRefKF(pRefKF), mpMap(pMap), mWorldPos(Pos), nObs(0) {
+    mnId = pMap ? pMap->nNextPointId++ : 0;
+}
+inline void MapPoint::UpdateNormalAndDepth() {  // src/MapPoint.cc:291-331
+    if (mbBad || mObservations.empty()) return;
+    float normal[3] = {0, 0, 0};
+    int n = 0;
+    for (std::map<KeyFrame *, size_t>::iterator mit = mObservations.begin(), mend = mObservations.end(); mit != mend; mit++) {
+        const Vector3f Owi = mit->first->GetCameraCenter();
+        float d[3] = {mWorldPos[0] - Owi[0], mWorldPos[1] - Owi[1], mWorldPos[2] - Owi[2]};
+        const float nrm = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        for (int a = 0; a < 3; a++) normal[a] = normal[a] + d[a] / nrm;
+        n++;
+    }
+    const Vector3f Or = mpRefKF->GetCameraCenter();
+    const float PC[3] = {mWorldPos[0] - Or[0], mWorldPos[1] - Or[1], mWorldPos[2] - Or[2]};
+    const float dist = std::sqrt((PC[0] * PC[0] + PC[1] * PC[1]) + PC[2] * PC[2]);
+    const int level = mpRefKF->mvKeys[mObservations[mpRefKF]].octave;
+    const float levelScaleFactor = mpRefKF->mvScaleFactors[level];
+    const int nLevels = mpRefKF->mnScaleLevels;
+    mfMaxDistance = dist * levelScaleFactor;
+    mfMinDistance = mfMaxDistance / mpRefKF->mvScaleFactors[nLevels - 1];
+    for (int a = 0; a < 3; a++) mNormalVector[a] = normal[a] / n;
+}
 inline void MapPoint::AddObservation(KeyFrame *pKF, size_t idx) {  // src/MapPoint.cc:84-94
     if (mObservations.count(pKF)) return;
     mObservations[pKF] = idx;

@@ -590,5 +590,34 @@ struct PnpArgs {
 };
 void launch_pnp(hipStream_t st, const PnpArgs &A);   // k_pnp_hyp, then k_pnp_refine
 
+// ---- LocalMapping::CreateNewMapPoints' per-pair triangulation (tri_kernels.hip): one lane per pair, the pairs of all problems of a call as
+// one flat list in one launch ----
+struct TriKfPose {                  // the layout of tri::Kf (tri_math.h; tri_kernels.hip asserts it), stated here so that only the two units of
+    float fx, fy, cx, cy, invfx, invfy, mbf;   // this row include that header
+    float Rcw[9], tcw[3], Ow[3];
+    float q[4], t[3];
+};
+struct TriKfDev {                   // one keyframe: what tri::triangulate_pair reads of it, and its per-feature arrays (device pointers)
+    TriKfPose k;
+    const ygzf_kp *keys;            // mvKeys (distorted)
+    const float *uRight, *depth, *cosStereo;   // null: monocular
+    const float *sigma2, *scale;    // mvLevelSigma2 / mvScaleFactors, nlevels each (resolved by the host)
+};
+struct TriProblemDev {              // one neighbour with at least one pair
+    TriKfDev kf2;
+    const int *idx1, *idx2;         // nPairs each, checked by the host: inside [0, n) of their keyframes
+    float *x3d;                     // nPairs x 3
+    uint8_t *status;                // nPairs
+    int nPairs;
+    int firstHyp;                   // the problem's first pair in the launch (ascending over the table; the name ransac::problem_of reads)
+};
+struct TriPairArgs {
+    TriKfDev kf1;
+    const TriProblemDev *probs;
+    int nProblems, totalPairs;
+    float ratioFactor;
+};
+void launch_triangulate(hipStream_t st, const TriPairArgs &A);
+
 }  // namespace ygzf
 #endif

@@ -1,5 +1,6 @@
 // ransac_device.h -- the device side of a RANSAC launch, shared by k_sim3_ransac (sim3_kernels.hip) and k_pnp_hyp / k_pnp_refine
-// (pnp_kernels.hip): one wave per hypothesis, wave g of the launch takes hypothesis g of the call's concatenated list.  Device only.
+// (pnp_kernels.hip): one wave per hypothesis, wave g of the launch takes hypothesis g of the call's concatenated list; problem_of also serves
+// k_triangulate (tri_kernels.hip), one lane per pair.  Device only.
 #ifndef YGZF_RANSAC_DEVICE_H
 #define YGZF_RANSAC_DEVICE_H
 #include <hip/hip_runtime.h>
@@ -9,9 +10,11 @@
 namespace ygzf {
 namespace ransac {
 
-// The problem whose hypotheses [firstHyp, firstHyp + nHyp) hold g: the last one with firstHyp <= g (problems without hypotheses are not in
-// the table).  g is wave-uniform, and so is everything here.  The caller returns where g - firstHyp is outside [0, nHyp): the test stays at
-// the call, since folded in here (a null result) it cost k_sim3_ransac two VGPRs.
+// The problem whose items [firstHyp, firstHyp + its count) hold g: the last one with firstHyp <= g (problems without items are not in the
+// table).  An item is a hypothesis for the RANSAC kernels, where g is wave-uniform and so is everything here, and a matched pair for
+// k_triangulate (tri_kernels.hip), where g is the lane's own and the search diverges within a wave (at most 32 steps either way); the field
+// keeps the name firstHyp for both.  The caller returns where g - firstHyp is outside the problem's count: the test stays at the call, since
+// folded in here (a null result) it cost k_sim3_ransac two VGPRs.
 template <typename Problem> __device__ __forceinline__ const Problem &problem_of(const Problem *probs, int nProblems, int g) {
     int lo = 0, hi = nProblems - 1;
     for (int it = 0; it < 32 && lo < hi; it++) {
