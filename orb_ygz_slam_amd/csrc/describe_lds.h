@@ -1,7 +1,8 @@
 // describe_lds.h -- the per-wave LDS of describe_window (csrc/extract_kernels.hip): where every row of the raw 43 x 43 window lies, which 16-byte
-// LDS-DMA slot carries which piece of it, how the row-blurred window shares the memory, and which lane takes which work item of the two
-// phases that read the raw window.  Plain constexpr arithmetic, no device code: the kernel computes its addresses with these functions and
-// tests/cpp/describe_lds_cpu.hip prints them for tests/test_describe_lds_layout.py, which counts the bank conflicts they give.
+// LDS-DMA slot carries which piece of it, how the row-blurred window shares the memory, which lane takes which work item of the two
+// phases that read the raw window, and where the column pass keeps its sampled bytes.  Plain constexpr arithmetic, no device code: the kernel
+// computes its addresses with these functions and tests/cpp/describe_lds_cpu.hip prints them for tests/test_describe_lds_layout.py, which
+// counts the bank conflicts they give (the column pass's: tools/describe_column_banks.py, tests/test_describe_column_order.py).
 //
 // The bank rule the layout answers (gfx950): a ds_read_b32 is served in two groups of 32 lanes, the bank of byte address a is (a / 4) mod 32,
 // and every further distinct dword on a bank costs the group one more cycle.  Rows 64 bytes apart start on banks 0, 16, 0, 16, ...: in the row
@@ -108,6 +109,15 @@ constexpr bool desc_overlay_ok(int front) {
 static_assert(desc_overlay_ok(kHbFront) && !desc_overlay_ok(kHbFront - 16), "hb overlays raw rows that are still to be read (or the front is larger than needed)");
 static_assert(kHbFront % 16 == 0 && kDescLdsBytes % 16 == 0 && kHbBytes <= kDescLdsBytes && kDescLdsBytes <= 5120, "per-wave LDS of k_describe");
 static_assert(kDescRawSlots == 3 * 64, "three LDS-DMA instructions carry the raw window");
+
+// ---- the column pass ----------------------------------------------------------------------------------------------------------------------------
+// The column blur is taken only at the pattern's rotated points, each distinct point once: lane l of sample step s holds point 64 s + l of
+// kBriefPoint (orb_pattern_table.h: tile order, so that a group of 32 lanes reads a compact cluster of hb -- neighbouring columns share a dword,
+// neighbouring rows lie kHbP / 2 = 20 banks apart; tools/describe_column_banks.py counts the cycles) and stores the blurred byte at val[64 s + l];
+// the pairs then compare two bytes of val.  val lies right behind hb, over raw rows that are dead once the row blur has run.
+constexpr int kDescSampleSteps = 6, kDescValBytes = 64 * kDescSampleSteps;
+constexpr int kDescValByte = 3440;
+static_assert(kDescValByte >= kHbBytes && kDescValByte % 4 == 0 && kDescValByte + kDescValBytes <= kDescLdsBytes, "val lies behind hb, inside the wave's LDS");
 
 }  // namespace ygzf
 #endif

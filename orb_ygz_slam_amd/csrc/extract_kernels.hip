@@ -2239,7 +2239,31 @@ constexpr DiscBytes make_disc_bytes() {
 }
 __constant__ DiscBytes c_disc = make_disc_bytes();
 
-__constant__ __attribute__((aligned(16))) float4 c_pattern[256];   // (x0, y0, x1, y1) of test pair p, already as floats
+// The rBRIEF pattern as the column pass takes it (describe_lds.h): the distinct end points in the table's tile order, already as floats, and for
+// test pair p the val slots of its two end points (i0 | i1 << 16).
+struct BriefTable { float xy[2 * kBriefPointSlots]; unsigned pair[256]; };
+constexpr BriefTable make_brief_table() {
+    BriefTable t{};
+    for (int i = 0; i < 2 * kBriefPointSlots; i++) t.xy[i] = (float) kBriefPoint[i];
+    for (int p = 0; p < 256; p++) t.pair[p] = (unsigned) kBriefPairPoint[2 * p] | (unsigned) kBriefPairPoint[2 * p + 1] << 16;
+    return t;
+}
+constexpr bool brief_table_ok() {   // every pair's two slots lead back to its own coordinates, and the points are 375 distinct ones
+    for (int p = 0; p < 256; p++)
+        for (int e = 0; e < 2; e++) {
+            const int i = kBriefPairPoint[2 * p + e];
+            if (i >= kBriefPointCount || kBriefPoint[2 * i] != kBriefPattern[4 * p + 2 * e] || kBriefPoint[2 * i + 1] != kBriefPattern[4 * p + 2 * e + 1]) return false;
+        }
+    for (int i = 0; i < kBriefPointCount; i++)
+        for (int j = 0; j < i; j++)
+            if (kBriefPoint[2 * i] == kBriefPoint[2 * j] && kBriefPoint[2 * i + 1] == kBriefPoint[2 * j + 1]) return false;
+    for (int i = kBriefPointCount; i < kBriefPointSlots; i++)   // the padding repeats the last point: its samples stay inside hb
+        if (kBriefPoint[2 * i] != kBriefPoint[2 * kBriefPointCount - 2] || kBriefPoint[2 * i + 1] != kBriefPoint[2 * kBriefPointCount - 1]) return false;
+    return true;
+}
+static_assert(kBriefPointCount == 375 && kBriefPointSlots == kDescValBytes, "the point table fills the sample steps");
+static_assert(brief_table_ok(), "orb_pattern_table.h: the point table and the pattern disagree");
+__constant__ __attribute__((aligned(16))) BriefTable c_brief = make_brief_table();
 __constant__ int c_umax[16];
 
 // One wave: orientation + blurred patch + 256 rBRIEF bits of the keypoint at integer (kx,ky) of a gw x gh level image.
@@ -2260,6 +2284,13 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
     unsigned discM[kDescCenSteps];   // disc membership bytes of this lane's four centroid work items: loaded first, used after the window is staged
 #pragma unroll
     for (int it = 0; it < kDescCenSteps; it++) discM[it] = c_disc.m[it * 64 + lane];
+    // the lane's six pattern points and its four pairs' val slots, for the column pass: requested here so that they arrive behind the window
+    float2 pt[kDescSampleSteps];
+    unsigned pr[4];
+#pragma unroll
+    for (int s = 0; s < kDescSampleSteps; s++) pt[s] = ((const float2 *) c_brief.xy)[64 * s + lane];
+#pragma unroll
+    for (int it = 0; it < 4; it++) pr[it] = c_brief.pair[64 * it + lane];
     const bool interior = kx >= 21 && kx + 21 < gw && ky >= 21 && ky + 22 < gh && ((pitch & 3) == 0);
     int rowOff0 = 0, rowOffStep = 0;
     if (interior) {
@@ -2372,38 +2403,39 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
     }
     wave_lds_handoff();
     pc.mark(3);
-    // vertical pass only where the rotated pattern samples (512 points instead of the 37 x 37 patch): 7 taps straight from hb
+    // vertical pass only where the rotated pattern samples: 7 taps straight from hb, each of the pattern's 375 distinct points once.  Lane l of
+    // step s takes point 64 s + l of the table, whose tile order makes a group of 32 lanes read a compact cluster of hb (describe_lds.h), and
+    // leaves the blurred byte at val[64 s + l]; the pairs then compare two bytes of val.
     float a, b;
     sincos_deg(angle, &a, &b);
 #ifdef YGZF_PHASE_CLOCK
     asm volatile("" :: "v"(a), "v"(b));
 #endif
     pc.mark(4);
+    uint8_t *const val = L.mem + kDescValByte;
 #pragma unroll
-    for (int it = 0; it < 4; it++) {
-        const int p = it * 64 + lane;
-        const float4 pk = c_pattern[p];
-        const float x0 = pk.x, y0 = pk.y, x1 = pk.z, y1 = pk.w;
-        const int r0 = __float2int_rn(x0 * b + y0 * a), q0 = __float2int_rn(x0 * a - y0 * b);
-        const int r1 = __float2int_rn(x1 * b + y1 * a), q1 = __float2int_rn(x1 * a - y1 * b);
-        const unsigned short *p0 = &L.hbp()[(18 + r0) * kHbP + 18 + q0], *p1 = &L.hbp()[(18 + r1) * kHbP + 18 + q1];
-        const int s0 = 18 * (p0[0] + p0[6 * kHbP]) + 34 * (p0[kHbP] + p0[5 * kHbP]) + k2 * (p0[2 * kHbP] + p0[4 * kHbP]) + k3 * p0[3 * kHbP];
-        const int s1 = 18 * (p1[0] + p1[6 * kHbP]) + 34 * (p1[kHbP] + p1[5 * kHbP]) + k2 * (p1[2 * kHbP] + p1[4 * kHbP]) + k3 * p1[3 * kHbP];
-        int t0 = (s0 + 32768) >> 16, t1 = (s1 + 32768) >> 16;
+    for (int s = 0; s < kDescSampleSteps; s++) {
+        const float x = pt[s].x, y = pt[s].y;
+        const int r = __float2int_rn(x * b + y * a), q = __float2int_rn(x * a - y * b);
+        const unsigned short *p = &L.hbp()[(18 + r) * kHbP + 18 + q];
+        const int sum = 18 * (p[0] + p[6 * kHbP]) + 34 * (p[kHbP] + p[5 * kHbP]) + k2 * (p[2 * kHbP] + p[4 * kHbP]) + k3 * p[3 * kHbP];
+        int t = (sum + 32768) >> 16;
         if (CVM == YGZF_CV_LEGACY_SSE2) {
             // exact tie (sum = q*65536 + 32768) inside the SSE2 body: cvtps2dq rounds to even, i.e. the half-up result loses its low bit.
             // A tie is one sample in tens of thousands: the column bookkeeping it needs (ten vector instructions per sample, a tenth of this
-            // phase) runs only when some lane of the wave has one
-            const bool tie0 = (s0 & 0xFFFF) == 0x8000, tie1 = (s1 & 0xFFFF) == 0x8000;
-            if (__builtin_expect(__ballot(tie0 || tie1) != 0ull, 0)) {
-                const int wv = gw & ~3;
-                const int c0 = reflect101(kx + q0, gw), c1 = reflect101(kx + q1, gw);
-                if (tie0 && c0 < wv) t0 &= ~1;
-                if (tie1 && c1 < wv) t1 &= ~1;
+            // phase) runs only when some lane of the wave has one.  The rule reads the point's own image column only, so a point that several
+            // pairs share has one value.
+            const bool tie = (sum & 0xFFFF) == 0x8000;
+            if (__builtin_expect(__ballot(tie) != 0ull, 0)) {
+                if (tie && reflect101(kx + q, gw) < (gw & ~3)) t &= ~1;
             }
         }
-        t0 = min(t0, 255);
-        t1 = min(t1, 255);
+        val[64 * s + lane] = (uint8_t) min(t, 255);
+    }
+    wave_lds_handoff();
+#pragma unroll
+    for (int it = 0; it < 4; it++) {
+        const int t0 = val[pr[it] & 0xFFFFu], t1 = val[pr[it] >> 16];
         bits[it] = __ballot(t0 < t1);
     }
     pc.mark(5);
@@ -2530,10 +2562,6 @@ __global__ void k_hamming_pairs(const unsigned long long *__restrict__ a, const 
 hipError_t upload_constants(const int *umax16) {
     for (int i = 0; i < 16; i++)
         if (umax16[i] != kUmax15[i]) return hipErrorInvalidValue;   // the orientation kernel's disc masks are built for this table
-    float pf[1024];
-    for (int i = 0; i < 1024; i++) pf[i] = (float) kBriefPattern[i];
-    hipError_t e = hipMemcpyToSymbol(HIP_SYMBOL(c_pattern), pf, sizeof pf);
-    if (e != hipSuccess) return e;
     return hipMemcpyToSymbol(HIP_SYMBOL(c_umax), umax16, 16 * sizeof(int));
 }
 
