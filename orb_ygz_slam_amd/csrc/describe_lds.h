@@ -52,6 +52,31 @@ constexpr bool desc_slots_ok() {   // every quarter of every row has exactly the
     return next == kWin * 4;
 }
 static_assert(desc_slots_ok(), "LDS-DMA slots and row offsets disagree");
+// The same for the three slots 64 p + lane of one lane, from ONE division: 64 p = 9 * 7 p + p, so slot 64 p + lane lies in run 7 p + (lane + p) / 9 at
+// place (lane + p) % 9.  With run0 = lane / 9 and k0 = lane % 9 the later pieces' runs are 7 p + run0 + (k0 >= 9 - p) and their pads the lanes with
+// k0 = 8 - p: a compare each instead of a division and a remainder each.
+struct DescLaneSlots { int item[kDescRawSlots / 64]; bool pad[kDescRawSlots / 64]; };   // (a pad's item is not meant)
+constexpr DescLaneSlots desc_lane_slots(int lane) {
+    DescLaneSlots d{};
+    const int run0 = lane / kDescRunSlots, k0 = lane - kDescRunSlots * run0;
+    for (int p = 0; p < kDescRawSlots / 64; p++) {
+        const int s = 64 * p + lane;
+        const int run = (64 / kDescRunSlots) * p + run0 + (k0 >= kDescRunSlots - p ? 1 : 0);
+        const bool regular = 64 * (p + 1) <= kDescRegularSlots || s < kDescRegularSlots;
+        d.item[p] = s - (regular ? run : kDescRegularSlots / kDescRunSlots) - (s > kDescLastPadSlot ? 1 : 0);
+        d.pad[p] = regular ? k0 == kDescRunSlots - 1 - p : s == kDescLastPadSlot;
+    }
+    return d;
+}
+constexpr bool desc_lane_slots_ok() {
+    for (int lane = 0; lane < 64; lane++)
+        for (int p = 0; p < kDescRawSlots / 64; p++) {
+            const DescLaneSlots d = desc_lane_slots(lane);
+            if (d.pad[p] != desc_slot_is_pad(64 * p + lane) || (!d.pad[p] && d.item[p] != desc_slot_item(64 * p + lane))) return false;
+        }
+    return true;
+}
+static_assert(64 % kDescRunSlots == 1 && desc_lane_slots_ok(), "a lane's three slots from one division disagree with desc_slot_item");
 
 // ---- lane mappings of the phases that read the raw window ------------------------------------------------------------------------------------
 // Row blur: 43 rows x 4 segments of 10 columns = 172 items, item t = 64 * step + lane -> row t >> 2, segment t & 3 (three steps, the third

@@ -19,6 +19,7 @@
 #include "kernels.h"
 #include "wave_ops.h"
 #include "describe_lds.h"
+#include "describe_sample.h"
 #include "fast9_quad.h"
 #include "fast_lane_quads.h"
 #include "orb_pattern_table.h"
@@ -2199,6 +2200,7 @@ constexpr int kBl = 37, kBlP = 40;      // blurred 37x37 (u8)
 constexpr int kDescWaves = YGZF_DESC_WAVES;
 
 typedef __attribute__((address_space(3))) unsigned lds_u32_t;
+typedef __attribute__((address_space(3))) unsigned short lds_u16_t;
 // p + bytes as an LDS address the compiler takes as given: what is read or written through it are offsets of the instructions
 template <typename T>
 __device__ __forceinline__ T *lds_at(T *p, unsigned bytes) {
@@ -2300,12 +2302,13 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
         // LDS-DMA: lane s & 63 of piece s >> 6 delivers LDS bytes 16 s .. 16 s + 15.  Which quarter of which row's span that slot holds is
         // the layout's choice (desc_slot_item); the lanes of the pad slots load nothing.  So the 43 x 64 bytes go global memory -> LDS in
         // three instructions without a register round trip or a ds_write
+        const DescLaneSlots slots = desc_lane_slots(lane);   // one division by 9 for the three pieces
 #pragma unroll
         for (int i0 = 0; i0 < kDescRawSlots; i0 += 64) {
-            const int item = desc_slot_item(i0 + lane), r = item >> 2, q = item & 3;
+            const int item = slots.item[i0 >> 6], r = item >> 2, q = item & 3;
             // the 16-byte boundary below the row's first byte, as a 32-bit offset from the one below the window's first byte
             const unsigned off = ((unsigned) rowOff0 + __umul24((unsigned) r, (unsigned) pitch)) & ~15u;
-            if (!desc_slot_is_pad(i0 + lane))
+            if (!slots.pad[i0 >> 6])
                 __builtin_amdgcn_global_load_lds((const unsigned *) ((a00 & ~15ull) + (off + 16u * (unsigned) q)), (lds_void_t *) (L.rawp() + 16 * i0), 16, 0, 0);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -2397,7 +2400,13 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
         out4(e[1], e[2], e[3], ob);
         const unsigned o8 = __builtin_amdgcn_udot4(e[2], T0a, __builtin_amdgcn_udot4(e[3], T0b, 0u, false), false);
         const unsigned o9 = __builtin_amdgcn_udot4(e[2], T1a, __builtin_amdgcn_udot4(e[3], T1b, 0u, false), false);
-        const unsigned O[5] = {oa[0] | (oa[1] << 16), oa[2] | (oa[3] << 16), ob[0] | (ob[1] << 16), ob[2] | (ob[3] << 16), o8 | (o9 << 16)};
+        // two outputs per dword, one v_lshl_or_b32 each (left to itself the compiler takes a shift and an OR for two packs in three)
+        auto pack = [](unsigned lo, unsigned hi) {
+            unsigned d;
+            asm("v_lshl_or_b32 %0, %1, 16, %2" : "=v"(d) : "v"(hi), "v"(lo));
+            return d;
+        };
+        const unsigned O[5] = {pack(oa[0], oa[1]), pack(oa[2], oa[3]), pack(ob[0], ob[1]), pack(ob[2], ob[3]), pack(o8, o9)};
         lds_u32_t *dst = lds_at(hb0, (unsigned) s * (kDescBlurStepRows * kHbP * 2));
         dst[0] = O[0]; dst[1] = O[1]; dst[2] = O[2]; dst[3] = O[3]; dst[4] = O[4];
     }
@@ -2413,24 +2422,27 @@ __device__ __forceinline__ void describe_window(const uint8_t *__restrict__ img,
 #endif
     pc.mark(4);
     uint8_t *const val = L.mem + kDescValByte;
+    // The sample's address is formed in float (describe_sample.h): rounding on the float adder, row pitch and centre by two multiply-adds, and
+    // the integer out of the mantissa by the one subtraction that also adds the wave's LDS base.
+    const unsigned hbBase = (unsigned) (uintptr_t) (lds_u16_t *) L.hbp() - ds::kTwo23Bits;
 #pragma unroll
     for (int s = 0; s < kDescSampleSteps; s++) {
-        const float x = pt[s].x, y = pt[s].y;
-        const int r = __float2int_rn(x * b + y * a), q = __float2int_rn(x * a - y * b);
-        const unsigned short *p = &L.hbp()[(18 + r) * kHbP + 18 + q];
-        const int sum = 18 * (p[0] + p[6 * kHbP]) + 34 * (p[kHbP] + p[5 * kHbP]) + k2 * (p[2 * kHbP] + p[4 * kHbP]) + k3 * p[3 * kHbP];
-        int t = (sum + 32768) >> 16;
+        float R, Q;
+        ds::rotated(pt[s].x, pt[s].y, a, b, &R, &Q);
+        const lds_u16_t *p = (const lds_u16_t *) (uintptr_t) (hbBase + ds::float_bits(ds::hb_byte_f(R, Q)));
+        const unsigned sum = ds::tap_sum<k2, k3>(p[0], p[kHbP], p[2 * kHbP], p[3 * kHbP], p[4 * kHbP], p[5 * kHbP], p[6 * kHbP]);
+        unsigned t = sum >> 16;
         if (CVM == YGZF_CV_LEGACY_SSE2) {
-            // exact tie (sum = q*65536 + 32768) inside the SSE2 body: cvtps2dq rounds to even, i.e. the half-up result loses its low bit.
-            // A tie is one sample in tens of thousands: the column bookkeeping it needs (ten vector instructions per sample, a tenth of this
-            // phase) runs only when some lane of the wave has one.  The rule reads the point's own image column only, so a point that several
-            // pairs share has one value.
-            const bool tie = (sum & 0xFFFF) == 0x8000;
+            // exact tie (sum = q*65536 + 32768 before the rounding half) inside the SSE2 body: cvtps2dq rounds to even, i.e. the half-up result
+            // loses its low bit.  A tie is one sample in tens of thousands: the column bookkeeping it needs (ten vector instructions per sample, a
+            // tenth of this phase) runs only when some lane of the wave has one.  The rule reads the point's own image column only, so a point
+            // that several pairs share has one value.
+            const bool tie = (sum & 0xFFFFu) == 0u;
             if (__builtin_expect(__ballot(tie) != 0ull, 0)) {
-                if (tie && reflect101(kx + q, gw) < (gw & ~3)) t &= ~1;
+                if (tie && reflect101(kx + (int) Q, gw) < (gw & ~3)) t &= ~1u;
             }
         }
-        val[64 * s + lane] = (uint8_t) min(t, 255);
+        val[64 * s + lane] = (uint8_t) min(t, 255u);
     }
     wave_lds_handoff();
 #pragma unroll
