@@ -364,7 +364,7 @@ int run_extract(ygzf_ctx *c, const FrameSet &fs, int nFrames, bool pyramidReady)
         if ((rc = launch_fast(c, fs, nFrames, fast, iniFirst, collect))) return rc;
         long long *odbg = nullptr;
         if (c->octDebug) {
-            if ((rc = ensure(c, c->tmp.a, kOctDbgWords * sizeof(long long)))) return rc;
+            if ((rc = ensure_scratch(c, c->tmp.a, kOctDbgWords * sizeof(long long)))) return rc;
             odbg = (long long *) c->tmp.a.p;
             HIPCHECK(c, hipMemsetAsync(odbg, 0, kOctDbgWords * sizeof(long long), c->stream));
         }
@@ -498,7 +498,7 @@ int pyramid_readback(ygzf_ctx *c, const FrameSet &fs, int w, int h, const uint8_
     offs[1] = first ? 0u : (unsigned) w * (unsigned) h;
     for (int l = 1; l < L; l++) offs[l + 1] = offs[l] + (unsigned) G.lv[l].w * (unsigned) G.lv[l].h;
     const size_t total = offs[L];
-    if ((rc = ensure_stage(c, total + 64)) || (rc = ensure(c, c->tmp.c, total + 64))) return rc;
+    if ((rc = ensure_stage(c, total + 64)) || (rc = ensure_scratch(c, c->tmp.c, total + 64))) return rc;
     // (the page-locked staging area as the device addresses it: the packing kernel -- 16-byte stores -- writes the levels over the link itself, on the
     // stream the copy would have taken; a byte-per-thread packing kernel doing so was slower than the copy engine: ComputePyramid 94 -> 97 us)
     const bool linkPack = c->hStageDev != nullptr && c->linkKernels && c->pyrLink;
@@ -605,6 +605,7 @@ void ygzf_destroy(ygzf_ctx *c) {
     if (c->tStart) (void) hipEventDestroy(c->tStart);
     if (c->tStop) (void) hipEventDestroy(c->tStop);
     if (c->stream) (void) hipStreamDestroy(c->stream);
+    if (c->fill) fprintf(stderr, "[ygzf] fill: %llu allocations, %llu scratch refills, %llu bytes\n", c->fillStats.allocs, c->fillStats.refills, c->fillStats.bytes);
     delete c;   // every Buf frees itself here: on the device selected above, with the stream drained
 }
 
@@ -1021,7 +1022,7 @@ int ygzf_batch_fetch_level(ygzf_ctx *c, int frame, int level, uint8_t *out) {
     const uint8_t *p = level_ptr(c->held.fs, g, level, frame, &pitch);
     // packed on the device, then one linear copy (a pitched copy of an odd-width level is executed row by row)
     const size_t bytes = (size_t) g.w * g.h;
-    int rc = ensure(c, c->tmp.c, bytes + 64);
+    int rc = ensure_scratch(c, c->tmp.c, bytes + 64);
     if (rc) return rc;
     launch_repitch_rows(c->stream, p, (size_t) pitch, (uint8_t *) c->tmp.c.p, (size_t) g.w, g.w, (size_t) g.h);
     HIPCHECK(c, hipGetLastError());
@@ -1106,8 +1107,8 @@ int ygzf_descriptor_distance(ygzf_ctx *c, const uint8_t *a, const uint8_t *b, in
         HIPCHECK(c, hipGetLastError());
         return P.download();
     }
-    if ((rc = ensure(c, c->tmp.a, (size_t) n * 32)) || (rc = ensure(c, c->tmp.b, (size_t) n * 32)) ||
-        (rc = ensure(c, c->tmp.c, (size_t) n * sizeof(int))))
+    if ((rc = ensure_scratch(c, c->tmp.a, (size_t) n * 32)) || (rc = ensure_scratch(c, c->tmp.b, (size_t) n * 32)) ||
+        (rc = ensure_scratch(c, c->tmp.c, (size_t) n * sizeof(int))))
         return rc;
     HIPCHECK(c, hipMemcpyAsync(c->tmp.a.p, a, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));
     HIPCHECK(c, hipMemcpyAsync(c->tmp.b.p, b, (size_t) n * 32, hipMemcpyHostToDevice, c->stream));

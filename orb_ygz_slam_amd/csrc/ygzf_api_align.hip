@@ -130,7 +130,7 @@ static int sia_run_impl(ygzf_ctx *c, const ygzf_sia_frame *ref, const ygzf_sia_f
     A.out = (float *) P.d_out(rOut);
     {
         if (c->siaDebug) {
-            if ((rc = ensure(c, c->tmp.b, 256))) return rc;
+            if ((rc = ensure_scratch(c, c->tmp.b, 256))) return rc;
             HIPCHECK(c, hipMemsetAsync(c->tmp.b.p, 0, 256, c->stream));
             A.dbg = (long long *) c->tmp.b.p;
         }

@@ -68,7 +68,7 @@ static int key_level_position(ygzf_ctx *c, const ygzf_kp &k, int i, int *px, int
 static int describe_list(ygzf_ctx *c, const FrameSet &fs, int frame, int total, float *ang, uint8_t *desc) {
     ygzf_ctx::Grid &D = c->grid;
     int rc;
-    if ((rc = ensure(c, D.angles, 4 * (size_t) total)) || (rc = ensure(c, c->tmp.c, 32 * (size_t) total))) return rc;
+    if ((rc = ensure(c, D.angles, 4 * (size_t) total)) || (rc = ensure_scratch(c, c->tmp.c, 32 * (size_t) total))) return rc;
     {
         ProfScope ps(c, KK_DESCRIBE);
         launch_describe_list(c->stream, fs, (const LevelGeom *) c->dGeom.p, D.list.p, total, frame, (float *) D.angles.p, (uint8_t *) c->tmp.c.p, c->tab.cfg.cv_mode);
@@ -144,7 +144,7 @@ int ygzf_extract_dso(ygzf_ctx *c, const uint8_t *img, int w, int h, int stride, 
     const size_t maxEntries = (size_t) n_existing + 3 * (size_t) maxCells;
     if ((rc = ensure(c, D.occ, occWords * 4)) || (rc = ensure(c, D.occXY_voteKey, 4 * (size_t) (n_existing + 1))) || (rc = ensure(c, D.cellCnt_lvlTotals, 4 * (size_t) maxCells)) ||
         (rc = ensure(c, D.cellXY, 12 * (size_t) maxCells)) || (rc = ensure(c, D.total_lvlOff, 64)) || (rc = ensure(c, D.list, 16 * maxEntries)) ||
-        (rc = ensure(c, D.newXY, 4 * 3 * (size_t) maxCells)) || (rc = ensure(c, D.angles, 4 * maxEntries)) || (rc = ensure(c, c->tmp.c, 32 * maxEntries)))
+        (rc = ensure(c, D.newXY, 4 * 3 * (size_t) maxCells)) || (rc = ensure(c, D.angles, 4 * maxEntries)) || (rc = ensure_scratch(c, c->tmp.c, 32 * maxEntries)))
         return rc;
     HIPCHECK(c, hipMemsetAsync(D.occ.p, 0, occWords * 4, c->stream));
     if (n_existing > 0) {

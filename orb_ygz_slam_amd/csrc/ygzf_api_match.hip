@@ -1088,7 +1088,7 @@ int ygzf_features_in_area(ygzf_ctx *c, const ygzf_camera *cam, int n_keys, const
         A.outN = (int *) P.d_out(oN);
         A.outIdx = (int *) P.d_out(oI);
     } else {
-        if ((rc = ensure(c, c->tmp.a, kBytes + 64)) || (rc = ensure(c, c->tmp.b, qBytes + lBytes + 64)) || (rc = ensure(c, c->tmp.c, nPad + oBytes + 64)))
+        if ((rc = ensure_scratch(c, c->tmp.a, kBytes + 64)) || (rc = ensure_scratch(c, c->tmp.b, qBytes + lBytes + 64)) || (rc = ensure_scratch(c, c->tmp.c, nPad + oBytes + 64)))
             return rc;
         if (n_keys > 0) HIPCHECK(c, hipMemcpyAsync(c->tmp.a.p, keys, kBytes, hipMemcpyHostToDevice, c->stream));
         HIPCHECK(c, hipMemcpyAsync(c->tmp.b.p, xyr, qBytes, hipMemcpyHostToDevice, c->stream));
@@ -1125,8 +1125,8 @@ int ygzf_distinctive_descriptors_batch(ygzf_ctx *c, int n_points, const int *obs
     HIPCHECK(c, hipSetDevice(c->device));
     int rc;
     const size_t offBytes = (4 * (size_t) (n_points + 1) + 15) & ~(size_t) 15;
-    if ((rc = ensure(c, c->tmp.a, offBytes + 4 * large.size() + 16)) || (rc = ensure(c, c->tmp.b, 4 * (size_t) n_points)) ||
-        (rc = ensure(c, c->tmp.c, 32 * (size_t) (total + 1))))
+    if ((rc = ensure_scratch(c, c->tmp.a, offBytes + 4 * large.size() + 16)) || (rc = ensure_scratch(c, c->tmp.b, 4 * (size_t) n_points)) ||
+        (rc = ensure_scratch(c, c->tmp.c, 32 * (size_t) (total + 1))))
         return rc;
     HIPCHECK(c, hipMemcpyAsync(c->tmp.a.p, obs_off, 4 * (size_t) (n_points + 1), hipMemcpyHostToDevice, c->stream));
     if (!large.empty()) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->tmp.a.p + offBytes, large.data(), 4 * large.size(), hipMemcpyHostToDevice, c->stream));

@@ -40,7 +40,7 @@ int ygzf_pose_optimization(ygzf_ctx *c, const ygzf_camera *cam, const float *inv
     HIPCHECK(c, hipSetDevice(c->device));
     int rc;
     // any n goes: the packed transfer's device block and the per-edge scratch are grow-on-demand buffers of the context (dPack, tmp.a)
-    if ((rc = ensure(c, c->tmp.a, (total + 1) * sizeof(double)))) return rc;
+    if ((rc = ensure_scratch(c, c->tmp.a, (total + 1) * sizeof(double)))) return rc;
     struct Slots { ProblemBlock::Slot keys, right, valid, world, flags; };
     std::vector<Slots> S(n_problems);
     ProblemBlock B(c, (size_t) n_problems * sizeof(PoseProblemDev), (size_t) n_problems * sizeof(PoseOut));

@@ -24,7 +24,7 @@ int ygzf_optimize_sim3(ygzf_ctx *c, int n_problems, const ygzf_sim3_opt_problem 
     HIPCHECK(c, hipSetDevice(c->device));
     int rc;
     // any n goes: the packed transfer's device block and the per-edge scratch are grow-on-demand buffers of the context (dPack, tmp.a)
-    if ((rc = ensure(c, c->tmp.a, (2 * total + 1) * sizeof(double)))) return rc;
+    if ((rc = ensure_scratch(c, c->tmp.a, (2 * total + 1) * sizeof(double)))) return rc;
     // per problem one segment of floats: P1c[3n] P2c[3n] obs1[2n] obs2[2n] inv_sigma2_1[n] inv_sigma2_2[n]
     struct Slots { ProblemBlock::Slot seg, flags; };
     std::vector<Slots> S(n_problems);

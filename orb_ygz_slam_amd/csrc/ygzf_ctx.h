@@ -234,6 +234,10 @@ struct ygzf_ctx {
     // debugging aids, read once per context (never on the launch path): synchronise after every kernel and name it on stderr /
     // phase clocks of the octree, matcher and aligner kernels printed to stderr
     bool debugSync = debug_flag("sync");
+    // fill: ensure() fills what it allocates, ensure_scratch() and PackedTransfer::upload() fill the per-call scratch again (ygzf_internal.h);
+    // what they did, for ygzf_destroy's line on stderr
+    bool fill = debug_flag("fill");
+    struct FillStats { unsigned long long allocs = 0, refills = 0, bytes = 0; } fillStats;
     // the plans below are the library's own choice unless YGZF_FORCE pins them (tests: every plan against the oracle; ygzf_internal.h)
     // (per-call switches, read once when the context is created like the ones below)
     bool linkKernels = forced("fetch_kernel", 1) != 0, pyrLink = forced("pyr_link", 1) != 0;
@@ -289,7 +293,28 @@ static int ensure(ygzf_ctx *c, ygzf_ctx::Buf &b, size_t bytes) {
     HIPCHECK(c, b.release());
     HIPCHECK(c, hipMalloc(&b.p, bytes));
     b.bytes = bytes;
+    if (c->fill) {   // (blocking, on the null stream: no ensure() runs inside a stream capture, hipMalloc could not either)
+        HIPCHECK(c, hipMemset(b.p, kDebugFillByte, bytes));
+        HIPCHECK(c, hipStreamSynchronize(nullptr));
+        c->fillStats.allocs++;
+        c->fillStats.bytes += bytes;
+    }
     return YGZF_OK;
+}
+
+// YGZF_DEBUG=fill: a buffer whose contents are dead between calls (dPack, tmp.a/b/c) is filled again over its whole size, on the context's
+// stream, where a call begins to use it
+static int refill_scratch(ygzf_ctx *c, ygzf_ctx::Buf &b) {
+    if (!c->fill || !b.bytes) return YGZF_OK;
+    HIPCHECK(c, hipMemsetAsync(b.p, kDebugFillByte, b.bytes, c->stream));
+    c->fillStats.refills++;
+    c->fillStats.bytes += b.bytes;
+    return YGZF_OK;
+}
+// ensure() for tmp.a/b/c: the call that sizes one of them is about to write it, and nothing it held is valid any more (ygzf_ctx::Scratch)
+static int ensure_scratch(ygzf_ctx *c, ygzf_ctx::Buf &b, size_t bytes) {
+    const int rc = ensure(c, b, bytes);
+    return rc ? rc : refill_scratch(c, b);
 }
 
 // ---- the transitions of ygzf_ctx::held (its only writers) ----------------------------------------------------------------------------
@@ -415,7 +440,7 @@ struct PackedTransfer {
     size_t device_bytes() const { return inBytes + outBytes + deviceOnly + 256; }
     int upload(uint8_t **dBase) {
         int rc;
-        if ((rc = ensure(c, c->dPack, device_bytes()))) return rc;
+        if ((rc = ensure(c, c->dPack, device_bytes())) || (rc = refill_scratch(c, c->dPack))) return rc;   // (every caller clears its outputs after upload())
         if (direct()) {
             for (const Seg &s : in)
                 if (s.bytes) HIPCHECK(c, hipMemcpyAsync((uint8_t *) c->dPack.p + s.off, s.src, s.bytes, hipMemcpyHostToDevice, c->stream));

@@ -123,6 +123,9 @@ int cv_round_host(double v);
 //   YGZF_DEBUG=flag,flag,...   sync     synchronise after every kernel and name it on stderr
 //                              nograph  launch the pyramid chain kernel by kernel instead of replaying its hipGraph
 //                              oct / match / sia   phase clocks of k_octree / k_match_last / k_sia_run printed to stderr (tools/*_phases.py)
+//                              fill     every device allocation of a context starts out as kDebugFillByte, and the per-call scratch (dPack, tmp.a/b/c)
+//                                       is filled again before every use: a word that a call reads without having written it is a NaN / -1 / 255
+//                                       instead of whatever lay there (tests/test_gpu_filled_buffers.py); ygzf_destroy prints the counts to stderr
 //   YGZF_FORCE=key=value,...   pins a plan that the library otherwise chooses itself from the shape of the launch, so that the tests can run EVERY
 //                              plan of a kernel against the oracle on small inputs (INTEGRATION.md lists the keys); a key that is absent leaves the
 //                              library's own choice in place.
@@ -145,6 +148,8 @@ inline bool debug_flag(const char *flag) {
     size_t n;
     return env_find("YGZF_DEBUG", flag, &n) != nullptr;
 }
+// YGZF_DEBUG=fill: a NaN as f16 / f32 / f64, -1 as a signed integer (a bounded loop over it runs zero times), 255 as a byte
+constexpr int kDebugFillByte = 0xFF;
 inline long forced(const char *key, long dflt) {
     size_t n;
     const char *v = env_find("YGZF_FORCE", key, &n);
